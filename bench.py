@@ -16,8 +16,10 @@ With N > 1 (launched by torch.distributed.run, one process per GPU, backend nccl
 and the queries are sharded over ranks (strong scaling of the named 1k-class job); the only data-path
 collectives are one all-gather of classifier rows and one all-reduce of the F1 counters.
 
-The JSON line also carries
-  roofline      the dominant kernel (fp16 MFMA GEMM at the c_fc launch shape of the job: M = batch x 197 = 152675 token
+A plain run sets up, warms up, times --steps steps and prints the line (--dump-outputs DIR: and writes the last timed step's
+outputs).  With --full the line also carries the phase split, the collective timings of a sharded run, the other BASELINE.json
+configurations as `presets` (default invocation), and
+  roofline     the dominant kernel (fp16 MFMA GEMM at the c_fc launch shape of the job: M = batch x 197 = 152675 token
                 rows at batch 775, N = 3072, K = 768, ln_2 fold + bias + QuickGELU epilogue) timed live with HIP events
                 on the stream it is launched on, against the 2.5 PFLOP/s dense fp16 MFMA peak;
   cpu_baseline  the CPU oracle (a torch-CPU port of the reference path, validated against golden vectors of
@@ -121,7 +123,15 @@ def parse(argv=None):
                     "these hosts, gets 2 -- enough to show it is the slower one")
     ap.add_argument("--cpu-procs", type=int, default=0, help="CPU worker processes (0: usable CPUs // --cpu-threads)")
     ap.add_argument("--cpu-timeout", type=float, default=240.0, help="give up on the CPU baseline after this many seconds")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the phase split's extra passes, the roofline probe, the CPU baseline, the "
+                         "collective timings and per-rank skew of a sharded run, and the other BASELINE.json configurations as `presets`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (classifier rows, visual tokens, fusion weights, "
+                         "fused outputs of the queries) as DIR/<name>.npy in float32, at most 64 MB in all (rank 0; its own queries when sharded)")
     args = ap.parse_args(argv)
+    if args.dump_outputs and (PRESETS[args.preset].get("value") in ("zeroshot", "shard") or args.emulate_world > 1):
+        ap.error("--dump-outputs covers the headline job's path (--preset metric, c2, c3, c5), not c1, c4 or --emulate-world")
     given = {a.split("=")[0] for a in argv if a.startswith("--")}
     for key, val in PRESETS[args.preset]["set"].items():          # a preset moves defaults only: explicit flags win
         if "--" + key.replace("_", "-") not in given:
@@ -249,7 +259,8 @@ def main():
         for b in range(0, q_img.shape[0], args.query_batch):
             yield q_img[b:b + args.query_batch]
 
-    def step():
+    def step(keep=None):
+        """keep: a list that receives a copy of every query batch's output (--dump-outputs, last timed step only)."""
         if not infer_only:
             generate()
         outs = None
@@ -260,9 +271,12 @@ def main():
             for b in query_batches():
                 outs = model(b)
                 int(outs.max(1)[1].sum().item())
+                if keep is not None:
+                    keep.append(outs.clone())
         else:
             for outs in model.forward_batches(query_batches(), stable_inputs=True, overlap=None if args.overlap < 0 else bool(args.overlap)):
-                pass                                     # (the reference's loop hands each batch's logits to the evaluator)
+                if keep is not None:                     # (the reference's loop hands each batch's logits to the evaluator)
+                    keep.append(outs.clone())
         model.wait_files()                               # both files complete on disk INSIDE the step
         return outs
 
@@ -277,9 +291,10 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
+    kept = [] if args.dump_outputs else None
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out = step()
+    for i in range(args.steps):
+        out = step(kept if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     t_own = time.perf_counter()
     if sharded:
@@ -292,33 +307,38 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
     assert out is None or bool(torch.isfinite(out).all())
-
-    # phase split (untimed extra pass, informational)
-    barrier()
-    tg = time.perf_counter(); model.forward_prompt(loader, wait_files=False); torch.cuda.synchronize(); tg = time.perf_counter() - tg
-    tf = time.perf_counter(); model.wait_files(); tf = time.perf_counter() - tf    # what is left of the file write once the GPU is idle (in a step it overlaps the queries)
-    ti = time.perf_counter()
-    if args.overlap >= 2:
-        for b in query_batches():
-            int(model(b).max(1)[1].sum().item())
-    else:
-        for _ in model.forward_batches(query_batches(), stable_inputs=True, overlap=None if args.overlap < 0 else bool(args.overlap)):
-            pass
-    torch.cuda.synchronize(); ti = time.perf_counter() - ti
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"mm_classifier": model.mm_classifier, "vision_classifier": model.visual_classifer,
+                                         "text_classifier": model.zero_shot_classifier, "fusion_weight": model.fusion_weight,
+                                         "visual_tokens": model.visual_tokens, "fused_outputs": torch.cat(kept) if kept else None})
 
     images_per_step = Q if infer_only else C * S + Q
     value = images_per_step * args.steps / dt
-    roof = measure_roofline(eng, spec, args, dev, 0 if infer_only else (c1 - c0) * S, q1 - q0) if rank == 0 else None
-    if roof is not None and (args.overlap == 1 or (args.overlap < 0 and args.query_batch <= model.OVERLAP_MAX_BATCH)) and q1 > q0:
-        roof["launches_alone_note"] = ("every shape is timed with its launches running ALONE; in the job the query-batch launches (M = "
-                                       f"{args.query_batch * spec.vision_tokens}) run two at a time (forward_batches), so a profiler's per-kernel-name "
-                                       "average also holds durations of overlapped pairs -- per launch shape: tools/dominant_by_grid.py, "
-                                       "profiles/*_dominant_kernel_by_grid.json")
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(spec, sd, pl, tok, args, n_ctx) if args.cpu_sample_classes > 0 else None   # 0: profiling runs skip the CPU leg
+    roof, cpu = None, None
+    if args.full:
+        # phase split (untimed extra pass, informational)
+        barrier()
+        tg = time.perf_counter(); model.forward_prompt(loader, wait_files=False); torch.cuda.synchronize(); tg = time.perf_counter() - tg
+        tf = time.perf_counter(); model.wait_files(); tf = time.perf_counter() - tf    # what is left of the file write once the GPU is idle (in a step it overlaps the queries)
+        ti = time.perf_counter()
+        if args.overlap >= 2:
+            for b in query_batches():
+                int(model(b).max(1)[1].sum().item())
+        else:
+            for _ in model.forward_batches(query_batches(), stable_inputs=True, overlap=None if args.overlap < 0 else bool(args.overlap)):
+                pass
+        torch.cuda.synchronize(); ti = time.perf_counter() - ti
 
-    if sharded and dist_info is not None:
+        roof = measure_roofline(eng, spec, args, dev, 0 if infer_only else (c1 - c0) * S, q1 - q0) if rank == 0 else None
+        if roof is not None and (args.overlap == 1 or (args.overlap < 0 and args.query_batch <= model.OVERLAP_MAX_BATCH)) and q1 > q0:
+            roof["launches_alone_note"] = ("every shape is timed with its launches running ALONE; in the job the query-batch launches (M = "
+                                           f"{args.query_batch * spec.vision_tokens}) run two at a time (forward_batches), so a profiler's per-kernel-name "
+                                           "average also holds durations of overlapped pairs -- per launch shape: tools/dominant_by_grid.py, "
+                                           "profiles/*_dominant_kernel_by_grid.json")
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(spec, sd, pl, tok, args, n_ctx) if args.cpu_sample_classes > 0 else None   # 0: profiling runs skip the CPU leg
+
+    if sharded and dist_info is not None and args.full:
         dist_info["collective_times_us"] = time_collectives(dist, dev, C, spec.embed_dim, n_ctx)
         # one SCALE line shows the skew between ranks: every rank's own time per step (its steps done, before the closing barrier) and
         # its phase split, gathered over the group itself (host objects: any backend)
@@ -337,6 +357,10 @@ def main():
         fl = sum(eng.flops_executed(min(lb, n_ex - s0)) for s0 in range(0, 0 if infer_only else n_ex, lb))
         fl += sum(eng.flops_executed(min(args.query_batch, n_q - s0)) for s0 in range(0, n_q, args.query_batch))
         flops_run = fl / max(1, (0 if infer_only else n_ex) + n_q)
+        split = {"generation_images_per_s_rank0": round((c1 - c0) * S / tg, 1),
+                 "generation_ms_rank0": round(1000 * tg, 3),
+                 "files_join_ms_after_generation_alone": round(1000 * tf, 3) if out_dir else None,
+                 "inference_images_per_s_rank0": round((q1 - q0) / ti, 1) if q1 > q0 else None} if args.full else {}
         line = {
             "metric": "images/sec ViT-B/16 encode+fusion, 1k-class×16-shot, 1/2/4/8 MI355X" if args.preset == "metric" else
                       f"images/sec, BASELINE.json configuration {args.preset}: {PRESETS[args.preset]['about']}",
@@ -354,11 +378,8 @@ def main():
             "dist": dist_info,
             "roofline": roof,
             "cpu_baseline": cpu,
-            "phases": {"generation_images_per_s_rank0": round((c1 - c0) * S / tg, 1),
-                       "generation_ms_rank0": round(1000 * tg, 3),
-                       "files_join_ms_after_generation_alone": round(1000 * tf, 3) if out_dir else None,
+            "phases": {**split,
                        "files_written_by": "a worker thread behind a side stream (CustomCLIP._write_files), joined at the end of every step",
-                       "inference_images_per_s_rank0": round((q1 - q0) / ti, 1) if q1 > q0 else None,
                        "inference_query_batch": args.query_batch,
                        "inference_batches_in_flight": 2 if (args.overlap == 1 or (args.overlap < 0 and args.query_batch <= model.OVERLAP_MAX_BATCH)) else 1,
                        "encoder_tflops_e2e_algorithmic": round(value * flops_img / 1e12, 1),
@@ -366,7 +387,7 @@ def main():
                        "e2e_frac_of_fp16_mfma_peak": round(value * flops_run / 1e12 / (2500.0 * world), 4)},
         }
         headline_job = (args.model, args.classes, args.shots, args.queries) == ("ViT-B/16", 1000, 16, 4096)
-        if args.presets and args.preset == "metric" and headline_job and world == 1 and not args.force_dist:
+        if args.full and args.presets and args.preset == "metric" and headline_job and world == 1 and not args.force_dist:
             torch.cuda.empty_cache()                    # (the children need at most ~40 GB of the 288: this process keeps its ~10 GB)
             line["presets"] = run_presets(args)
         if cpu and cpu.get("value"):
@@ -387,7 +408,7 @@ def run_presets(args):
     plan = (("c1", 3, 1), ("c2", 3, 1), ("c3", 3, 1), ("c4", 2, 1), ("c5", 2, 1))
     out = {}
     for name, steps, warm in plan:
-        cmd = [sys.executable, os.path.abspath(__file__), "--preset", name, "--steps", str(steps), "--warmup", str(warm),
+        cmd = [sys.executable, os.path.abspath(__file__), "--preset", name, "--steps", str(steps), "--warmup", str(warm), "--full",
                "--presets", "0", "--gelu-exact", str(args.gelu_exact), "--ln-fold", str(args.ln_fold)]
         # (c1's own CPU leg -- the reference's CPU-runnable configuration -- on a smaller sample than the headline's: 32 images, 3 repetitions, ~20 s)
         cmd += ["--cpu-reps", "3", "--cpu-sample-classes", "2"] if name == "c1" and not args.no_cpu_baseline else ["--no-cpu-baseline"]
@@ -413,6 +434,24 @@ def run_presets(args):
         except Exception as e:                               # noqa: BLE001
             out[name] = {"error": repr(e)[:300]}
     return out
+
+
+DUMP_BYTES = 60 << 20                                        # (under 64 MB however a megabyte is counted, .npy headers included)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: every array of `arrays` (None entries skipped) as <out_dir>/<name>.npy in float32.  Where they exceed `budget`
+    bytes in all, every array keeps the same fraction of its rows, picked by a fixed seeded sample (in row order): two builds run with
+    the same arguments write the same rows."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > budget and a.ndim and a.shape[0] > 1:
+            rows = np.random.default_rng(seed).choice(a.shape[0], max(1, a.shape[0] * budget // total), replace=False)
+            a = a[np.sort(rows)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ------------------------------------------------------------------------------------------
@@ -481,9 +520,9 @@ def zeroshot_config(args, dev):
     dt = time.perf_counter() - t0
     assert int(n_label.sum()) == Q and int(n_pred.sum()) == Q
     value = Q * args.steps / dt
-    roof = measure_roofline(eng, spec, args, dev, 0, Q)
+    roof = measure_roofline(eng, spec, args, dev, 0, Q) if args.full else None
     cpu = None
-    if not args.no_cpu_baseline and args.cpu_sample_classes > 0:
+    if args.full and not args.no_cpu_baseline and args.cpu_sample_classes > 0:
         cpu = cpu_baseline_zeroshot(spec, sd, ids, args)
     flops_img = eng.flops_per_image()
     fl = sum(eng.flops_executed(min(args.query_batch, Q - s0)) for s0 in range(0, Q, args.query_batch)) / Q
@@ -885,25 +924,28 @@ def shard_of_world(args, model, spec, dev, keep=None, peers=None):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
 
-    # phase split and the cross-validation step alone (untimed extra passes)
-    tg = time.perf_counter(); model.forward_prompt(loader, wait_files=False); torch.cuda.synchronize(); tg = time.perf_counter() - tg
-    model.wait_files()
+    # the query outputs the checks below read; with --full also the phase split and the cross-validation step alone (untimed extra passes)
+    tg = xval_ms = head_us = None
+    if args.full:
+        tg = time.perf_counter(); model.forward_prompt(loader, wait_files=False); torch.cuda.synchronize(); tg = time.perf_counter() - tg
+        model.wait_files()
     ti = time.perf_counter(); out = queries(collect=True); torch.cuda.synchronize(); ti = time.perf_counter() - ti
-    own = torch.arange(c0, c1, device=dev)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    model._xval_fusion_weight(own, model.mm_classifier, model.visual_classifer, model.zero_shot_classifier, 10.0)
-    e1.record()
-    torch.cuda.synchronize()
-    xval_ms = e0.elapsed_time(e1)
-    h0, h1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    feats = eng.encode_image(q[:args.query_batch], normalize=True)
-    h0.record()
-    for _ in range(10):
-        eng.fused_logits(feats, model.mm_classifier, model.visual_classifer, model.zero_shot_classifier, model.fusion_weight, "fusion")
-    h1.record()
-    torch.cuda.synchronize()
-    head_us = h0.elapsed_time(h1) * 100.0
+    if args.full:
+        own = torch.arange(c0, c1, device=dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        model._xval_fusion_weight(own, model.mm_classifier, model.visual_classifer, model.zero_shot_classifier, 10.0)
+        e1.record()
+        torch.cuda.synchronize()
+        xval_ms = e0.elapsed_time(e1)
+        h0, h1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        feats = eng.encode_image(q[:args.query_batch], normalize=True)
+        h0.record()
+        for _ in range(10):
+            eng.fused_logits(feats, model.mm_classifier, model.visual_classifer, model.zero_shot_classifier, model.fusion_weight, "fusion")
+        h1.record()
+        torch.cuda.synchronize()
+        head_us = h0.elapsed_time(h1) * 100.0
     # the emulated rank ends with the WHOLE job's bits: every classifier row (its own recomputed, the peers' gathered), the fusion weights
     # from the summed votes, and its query outputs finite
     eq = {k: bool(torch.equal(getattr(model, k), ref[k])) for k in ref}
@@ -912,7 +954,7 @@ def shard_of_world(args, model, spec, dev, keep=None, peers=None):
     n_rank = (c1 - c0) * S + (q1 - q0)
     if keep is not None:
         keep.update(local_counts=emu.local_counts, exemplars=buf[:(c1 - c0) * S], queries=q, out=out, classes=(c0, c1), model=model)
-    roof = measure_roofline(eng, spec, args, dev, (c1 - c0) * S, q1 - q0)
+    roof = measure_roofline(eng, spec, args, dev, (c1 - c0) * S, q1 - q0) if args.full else None
     flops_img = eng.flops_per_image()
     lb = args.classes_per_batch * S
     fl = sum(eng.flops_executed(min(lb, (c1 - c0) * S - s0)) for s0 in range(0, (c1 - c0) * S, lb))
@@ -939,11 +981,11 @@ def shard_of_world(args, model, spec, dev, keep=None, peers=None):
                        "rank_reproduces_whole_job_bits": eq},
         "roofline": roof,
         "cpu_baseline": None,
-        "phases": {"generation_images_per_s": round((c1 - c0) * S / tg, 1), "generation_ms": round(1000 * tg, 2),
+        "phases": {**({"generation_images_per_s": round((c1 - c0) * S / tg, 1), "generation_ms": round(1000 * tg, 2)} if args.full else {}),
                    "inference_images_per_s": round((q1 - q0) / ti, 1), "inference_ms": round(1000 * ti, 2),
-                   "xval_counts_fusion_weights_ms": round(xval_ms, 3),
-                   "xval_tflops": round(xval_flops / (xval_ms * 1e-3) / 1e12, 1),
-                   "fusion_head_us_per_query_batch": round(head_us, 1),
+                   **({"xval_counts_fusion_weights_ms": round(xval_ms, 3),
+                       "xval_tflops": round(xval_flops / (xval_ms * 1e-3) / 1e12, 1),
+                       "fusion_head_us_per_query_batch": round(head_us, 1)} if args.full else {}),
                    "encoder_tflops_e2e_algorithmic": round(value * flops_img / 1e12, 1),
                    "encoder_tflops_e2e_executed": round(value * flops_run / 1e12, 1),
                    "e2e_frac_of_fp16_mfma_peak": round(value * flops_run / 1e12 / 2500.0, 4)},

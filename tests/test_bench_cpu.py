@@ -66,3 +66,30 @@ def test_preflight_sets_the_environment_of_the_multi_process_gpu_tests(monkeypat
     assert os.environ["HSA_ENABLE_IPC_MODE_LEGACY"] == "1"
     for f in ("tests/test_hip_distributed.py", "tests/test_hip_parity.py", "scripts/generate_classifier.sh"):
         assert "HSA_ENABLE_IPC_MODE_LEGACY" in open(os.path.join(REPO, f)).read(), f
+
+
+def test_plain_run_options_and_output_dump(tmp_path):
+    """A plain line leaves the extras to --full; --dump-outputs is refused where it has no headline path, writes float32 .npy files, and
+    past its byte budget keeps the same seeded rows of every array, run after run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True and bench.parse([]).dump_outputs is None
+    for bad in (["--preset", "c1"], ["--preset", "c4"], ["--emulate-world", "2"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad + ["--dump-outputs", str(tmp_path)])
+    arrays = {"rows": torch.arange(4000 * 64, dtype=torch.float32).reshape(4000, 64), "w": torch.rand(4000, 3), "none": None}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == ["rows.npy", "w.npy"]
+    got = np.load(tmp_path / "all" / "rows.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, arrays["rows"].float().numpy())
+    budget = 100_000
+    for tag in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / tag), arrays, budget=budget)
+    size = sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1"))
+    assert size <= budget + 2 * 128                                                      # (+ the .npy headers)
+    a, b = np.load(tmp_path / "s1" / "rows.npy"), np.load(tmp_path / "s2" / "rows.npy")
+    assert np.array_equal(a, b) and 1 < a.shape[0] < 4000 and a.shape[1] == 64
+    idx = (a[:, 0] / 64).astype(np.int64)                                                # rows of the sample, in row order, unaltered
+    assert (np.diff(idx) > 0).all() and np.array_equal(a, arrays["rows"].float().numpy()[idx])

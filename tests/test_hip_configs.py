@@ -236,7 +236,7 @@ def test_config_c4_vitb16_sixty_four_shots_one_rank_of_eight(O):
     dev = torch.device("cuda:0")
     C, S, N = 5040, 64, 8
     args = bench.parse(["--preset", "c4", "--classes", str(C), "--classes-per-batch", str(C // N), "--queries", "2048",
-                        "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
+                        "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"])
     assert args.shots == S and args.emulate_world == N and args.model == "ViT-B/16"
     spec, sd, pl, tok, model = bench.make_model(args, dev)
     assert model.zero_shot_classifier is None or model._text_streamed
@@ -492,7 +492,7 @@ def test_config_c1_zeroshot_bench_line():
     fields, the evaluator's invariants on the device-counted test pass, and the logits of the timed loop against a plain model_inference."""
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import bench
-    args = bench.parse(["--preset", "c1", "--queries", "640", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"])
+    args = bench.parse(["--preset", "c1", "--queries", "640", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline"])
     assert (args.model, args.classes, args.query_batch) == ("ViT-B/16", 10, 256)
     line = bench.zeroshot_config(args, torch.device("cuda:0"))
     assert line["unit"] == "images/s" and line["value"] > 0 and line["dtype"] == "f16" and line["config"]["preset"] == "c1"

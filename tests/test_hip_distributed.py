@@ -92,7 +92,7 @@ def test_bench_line_proves_its_process_group(tmp_path):
     import json
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     base = [sys.executable, os.path.join(repo, "bench.py"), "--classes", "12", "--shots", "4", "--queries", "32", "--query-batch", "16",
-            "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--presets", "0"]
+            "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--presets", "0"]
     lines = {}
     for tag, extra in (("dist", ["--force-dist", "--dist-timeout", "120"]), ("plain", [])):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -106,6 +106,32 @@ def test_bench_line_proves_its_process_group(tmp_path):
     assert lines["dist"]["n_gpus"] == 1 and lines["dist"]["value"] > 0
     ct = d["collective_times_us"]                                                    # the two collectives at their real payloads, on this group
     assert ct["all_gather_rows"] > 0 and ct["all_reduce_counts"] > 0 and ct["payload_bytes"]["all_reduce_counts"] == 3 * 2 * 12 * 4
+
+
+@pytest.mark.timeout(900)
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """`bench.py` without --full: the headline fields only (no roofline, CPU baseline or presets), ms_per_step of exactly --steps timed
+    steps, and with --dump-outputs the last timed step's classifier rows, fusion weights and fused outputs as float32 .npy files -- the
+    same bits from a second run with the same arguments.  Small job: 12 classes x 4 shots + 32 queries."""
+    import json
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for tag in ("a", "b"):
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--classes", "12", "--shots", "4", "--queries", "32", "--query-batch", "16",
+               "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / tag)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric')][-1]))
+    d = lines[0]
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "images/s" and d["dtype"] == "f16"
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "presets" not in d and "generation_ms_rank0" not in d["phases"]
+    shapes = {"mm_classifier": (12, 512), "vision_classifier": (12, 512), "text_classifier": (12, 512), "fusion_weight": (12, 3),
+              "visual_tokens": (12, 2, 512), "fused_outputs": (32, 12)}
+    for name, shape in shapes.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), f"{name} differs between two runs with the same arguments"
 
 
 @pytest.mark.timeout(900)
