@@ -194,14 +194,8 @@ __global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ 
 }  // namespace
 
 int launch_attention_f16_v1(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s);  // attention_v1.hip
-
-
 int launch_attention_f16_v3(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s);  // attention_v3.hip
-int launch_attention_f16_v5(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, int mode, hipStream_t s);  // attention_v5.hip
-#ifdef OVMR_EXPERIMENTS
-int launch_attention_f16_v6(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, int mode, hipStream_t s);  // attention_v6.hip
-int launch_attention_f16_v4(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, int mode, hipStream_t s);  // attention_v4.hip
-#endif
+int launch_attention_f16_v5(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s);  // attention_v5.hip
 
 int launch_attention_f16(const half_t* qkv, half_t* out, int B, int L, int H, int causal, int variant, hipStream_t s) {
     return launch_attention_f16_q(qkv, out, B, L, L, H, causal, variant, s);
@@ -215,37 +209,16 @@ int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq,
         const int rc = launch_attention_f16_short(qkv, out, 1, &B, &L, &row0, H, causal, s);
         if (rc != -100) return rc;
     }
-#ifdef OVMR_EXPERIMENTS   // variant 4: variant 3's arithmetic with free-running producer / consumer waves (LDS flags instead of the barrier),
-    // the vehicle of the r02 ablations (400 + mode: timing-only); same speed as 3, so only the experiment build carries it
-    if (variant == 4 || (variant >= 400 && variant < 1000)) {
-        const int rc = launch_attention_f16_v4(qkv, out, B, L, Lq, H, causal, variant == 4 ? 0 : variant - 400, s);
-        if (rc != -100) return rc;
-        variant = 1;
-    }
-#else
     if (variant == 4) variant = 3;
-#endif
     if (variant == 3) {               // single-pass kernel for the ViT-B/16 image shape; long sequences (ViT-L: L = 257 / 577) as variant 5
         int rc = launch_attention_f16_v3(qkv, out, B, L, Lq, H, causal, s);
         if (rc != -100) return rc;
-        rc = launch_attention_f16_v5(qkv, out, B, L, Lq, H, causal, 0, s);
+        rc = launch_attention_f16_v5(qkv, out, B, L, Lq, H, causal, s);
         if (rc != -100) return rc;
         variant = 1;
     }
-#ifdef OVMR_EXPERIMENTS
-    if (variant == 6 || (variant >= 60 && variant < 68)) {   // two query tiles per wave (60 + mode: attention_v6.hip; slower than variant 5)
-        const int rc = launch_attention_f16_v6(qkv, out, B, L, Lq, H, causal, variant == 6 ? 0 : variant - 60, s);
-        if (rc != -100) return rc;
-        variant = 1;
-    }
-    if (variant >= 50 && variant < 306) {   // variant 5's scheduling experiments (50 + mode; 66 = the folded exponent)
-        const int rc = launch_attention_f16_v5(qkv, out, B, L, Lq, H, causal, variant - 50, s);
-        if (rc != -100) return rc;
-        variant = 1;
-    }
-#endif
     if (variant == 5) {               // 32x32x16 flash kernel (non-causal, L >= 256); other shapes as variant 1
-        const int rc = launch_attention_f16_v5(qkv, out, B, L, Lq, H, causal, 0, s);
+        const int rc = launch_attention_f16_v5(qkv, out, B, L, Lq, H, causal, s);
         if (rc != -100) return rc;
         variant = 1;
     }

@@ -19,7 +19,6 @@
 #include "common.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace {
 
@@ -294,10 +293,7 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
 }  // namespace
 
 int launch_attention_f16_v1(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s) {
-    int tpw = 8;                                           // query tiles per workgroup: 8 (4 waves x 2 tiles) measured best: 16 -> 198 us, 8 -> 193 us, 4 -> 321 us at B = 512
-#ifdef OVMR_EXPERIMENTS
-    if (const char* e = getenv("OVMR_ATTN_TPW")) { tpw = atoi(e); if (tpw < 2 || tpw > 16) tpw = 8; }
-#endif
+    const int tpw = 8;                                     // query tiles per workgroup: 8 (4 waves x 2 tiles) measured best: 16 -> 198 us, 8 -> 193 us, 4 -> 321 us at B = 512
     const int nT = (Lq + 15) / 16, nWG = (nT + tpw - 1) / tpw;
     const int per = (nT + nWG - 1) / nWG;                  // most tiles any workgroup gets
     const dim3 block(64 * std::max(4, (per + 1) / 2));      // at least 4 waves: the spare ones only help staging K / V

@@ -47,7 +47,6 @@ struct GemmArgs {
     int rows_in, rows_out;      // EPI_PATCH: patches per image (G*G) and tokens per image (G*G+1)
     float scale;                // EPI_SCALE
     int n_group;                // N tiles per L2 group (tile order, set by the launcher; 0 = all)
-    int a_blocked, w_blocked;   // operand stored as [rows/128][K/64][128][64] (16 KiB contiguous per (row block, K-tile))
     // LayerNorm folding (see EPI_LN_BIAS).  Row statistics travel as per-row PARTIAL sums [M][slots][2] fp32
     // (sum, sum of squares), one slot per 256-column tile of the producing GEMM, summed in slot order by the consumer
     // (deterministic: no atomics).
@@ -71,34 +70,11 @@ __device__ __forceinline__ float quick_gelu_h(float u) {
     return (float)(half_t)(u * (float)s);
 }
 
-// The same rounding points on a PAIR of fp16 values, written so that hipcc selects packed / mixed-precision instructions:
-// t = h(1.702 u) (v_fma_mixlo/hi), e = exp2(-log2e * t) with the fp16 -> fp32 conversion folded into v_fma_mix_f32,
-// s = h(1 / (1 + e)) as one v_cvt_pk_f16_f32, u * s as one v_pk_mul_f16: ~9.5 issue slots per element instead of 12.5
-// (the epilogue's vector instructions are exposed time: nothing overlaps a tile's epilogue, profiles/r01g_gemm_epilogue.md).
-__device__ __forceinline__ half2_t quick_gelu_h2(half2_t u) {
-    half2_t t;
-    t[0] = (half_t)(1.702f * (float)u[0]);
-    t[1] = (half_t)(1.702f * (float)u[1]);
-    // The epilogue's QuickGELU is bound by the TRANSCENDENTAL unit (2 per element: ~3.2 us of a ~30 us c_fc tile, unchanged
-    // when 25 % of the other vector instructions were removed), so the pair shares ONE reciprocal:
-    // 1/a = b / (a b), 1/b = a / (a b).  The exponent argument is clamped at 60 (sigmoid < 2^-60 is 0 in fp16 either way),
-    // which keeps a * b finite.
-    float2_t e;
-    e[0] = __builtin_amdgcn_exp2f(fminf(__builtin_fmaf((float)t[0], -1.4426950408889634f, 0.0f), 60.0f));
-    e[1] = __builtin_amdgcn_exp2f(fminf(__builtin_fmaf((float)t[1], -1.4426950408889634f, 0.0f), 60.0f));
-    const float a = 1.0f + e[0], b = 1.0f + e[1];
-    const float rab = __builtin_amdgcn_rcpf(a * b);
-    float2_t r;
-    r[0] = b * rab;
-    r[1] = a * rab;
-    const half2_t s = __builtin_convertvector(r, half2_t);
-    return u * s;
-}
-
-// Four values at a time: the four denominators a b c d share ONE reciprocal, R = 1 / (abcd); 1/(ab) = cd R, 1/(cd) = ab R,
-// 1/a = b / (ab) ...: 1.25 transcendental + 1.25 packed-fp32 multiplies per element instead of 1.5 + 1.5 (the transcendental unit
-// is what bounds QuickGELU: quarter rate).  Exponent arguments are clamped at 30 (a sigmoid below 2^-25 rounds to fp16 zero either
-// way), which keeps abcd below 2^124.
+// The same rounding points on four fp16 values at a time (the epilogue's vector instructions are exposed time: nothing overlaps
+// a tile's epilogue, profiles/r01g_gemm_epilogue.md).  The four denominators a b c d share ONE reciprocal, R = 1 / (abcd);
+// 1/(ab) = cd R, 1/(cd) = ab R, 1/a = b / (ab) ...: 1.25 transcendental + 1.25 packed-fp32 multiplies per element instead of
+// 1.5 + 1.5 (the transcendental unit is what bounds QuickGELU: quarter rate).  Exponent arguments are clamped at 30 (a sigmoid
+// below 2^-25 rounds to fp16 zero either way), which keeps abcd below 2^124.
 __device__ __forceinline__ half4_t quick_gelu_h4(half4_t u) {
     half4_t t;
     float4_t e;

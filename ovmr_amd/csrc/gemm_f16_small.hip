@@ -125,7 +125,7 @@ int launch_s64(const GemmArgs& a, hipStream_t s) {
 // -100: shape / epilogue not taken (the caller falls back to the tile kernels).
 int launch_gemm_f16_small(const GemmArgs& a, hipStream_t s) {
     if (a.K < 128 || (a.K & 127) || (a.lda & 7) || (a.ldw & 7) || ((uintptr_t)a.A & 15) || ((uintptr_t)a.W & 15) ||
-        a.im2col_R || a.stats_out || a.a_blocked || a.w_blocked)
+        a.im2col_R || a.stats_out)
         return -100;
     switch (a.epi) {
         case EPI_NONE: return launch_s64<EPI_NONE>(a, s);

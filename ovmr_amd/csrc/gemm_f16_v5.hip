@@ -28,17 +28,8 @@
 #include "common.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace {
-
-// A/B switches of tools/gemm_bench.py exist only in experiment builds (python -m ovmr_amd.build --experiments ->
-// libovmr_hip_exp.so); the product library reads no environment variable and carries no timing-only kernel.
-#ifdef OVMR_EXPERIMENTS
-inline int exp_env(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
-#else
-inline int exp_env(const char*) { return 0; }
-#endif
 
 constexpr int BK5 = 64, BN5 = 256;
 typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -49,15 +40,14 @@ __device__ __forceinline__ float dpp_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 
-// OPT bits: 1 / 2 nontemporal LDS-DMA for the A / W operand, 4 K loop with the iteration boundary inside the MFMA stream,
-// 16 the ping-pong K loop (256-row tiles), 32 pairwise QuickGELU (experiment A/B), 64 NOSTORE / 128 NOEPI (timing-only ablations, experiment builds only),
-// 512 NT (nontemporal C stores)
+// OPT bits: 1 nontemporal LDS-DMA for the A operand, 4 K loop with the iteration boundary inside the MFMA stream,
+// 16 the ping-pong K loop (256-row tiles), 512 NT (nontemporal C stores), 2048 the fp32 QuickGELU form
 template <int EPI, int MT, int OPT>
 __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_m, int tiles_n) {
     constexpr int BM = MT * 32;
     constexpr int A_BYTES = BM * 128, STAGE = (BM + BN5) * 128;
     constexpr int AJ = BM / 64;
-    constexpr bool NOSTORE = OPT & 64, NOEPI = OPT & 128, NT = OPT & 512;
+    constexpr bool NT = OPT & 512;
     constexpr int EP = 128;                            // epilogue staging tile: 128-byte rows, swizzled 8-byte units (below)
     constexpr bool GFAST = (OPT & 2048) != 0;          // QuickGELU: the one-rounding fp32 form (common.h quick_gelu_f32x2) instead of the reference's three fp16 rounding points
     constexpr bool LNF = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_QGELU;   // LayerNorm folded into this GEMM (common.h)
@@ -97,7 +87,6 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     const int m0 = tm * BM, n0 = tn * BN5;
 
     const int nk = a.K / BK5;
-    const int a_step = a.a_blocked ? 16384 : 128, w_step = a.w_blocked ? 16384 : 128;
     const half_t* A = (const half_t*)a.A;
     const half_t* W = (const half_t*)a.W;
 
@@ -105,12 +94,8 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     const int srow = lane >> 3, slot = lane & 7;
     const int schunk = (slot ^ srow) * 8;
     unsigned oa[AJ], ob[4];                            // byte offsets of this lane's source rows
-    // row-major: row * ld * 2 + chunk, K-tile step 128 B.  blocked [rows/128][K/64][128][64]: one (row block, K-tile)
-    // is 16 KiB contiguous, so every LDS-DMA instruction reads 1 KiB of consecutive addresses
-    auto src_off = [&](int row, int ld, int blocked) -> unsigned {
-        return blocked ? (unsigned)(((long)(row >> 7) * nk) * 16384 + (row & 127) * 128 + schunk * 2)
-                       : (unsigned)(((long)row * ld + schunk) * 2);
-    };
+    // row-major: row * ld * 2 + chunk, K-tile step 128 B
+    auto src_off = [&](int row, int ld) -> unsigned { return (unsigned)(((long)row * ld + schunk) * 2); };
     // EPI_PATCH with a.im2col_R: the A operand is the image tensor [B, 3, R, R] (fp16) and row r = patch (b, gy, gx) of the 16 x 16
     // grid cells.  K-tile kt holds k = kt*64 .. +63 = channel kt >> 2, pixel rows 4 (kt & 3) .. +3 of the patch, 16 pixels each: the
     // 16-byte chunk c8 of a row is pixel row c8 >> 1, pixels 8 (c8 & 1) .. +7.  So a lane's source is (row part + chunk part) + a
@@ -122,11 +107,11 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
             const int c8 = schunk >> 3;
             return (unsigned)(2 * (((long)b * 3 * imR + gy * 16 + (c8 >> 1)) * imR + gx * 16 + (c8 & 1) * 8));
         }
-        return src_off(a.a_blocked ? row : min(row, a.M - 1), a.lda, a.a_blocked);
+        return src_off(min(row, a.M - 1), a.lda);
     };
     auto a_tile = [&](int kt) -> const char* {           // wave-uniform
         if (EPI == EPI_PATCH && imR) return (const char*)A + 2 * ((long)(kt >> 2) * imR * imR + (kt & 3) * 4 * imR);
-        return (const char*)A + (long)kt * a_step;
+        return (const char*)A + (long)kt * 128;
     };
 #pragma unroll
     for (int j = 0; j < AJ; ++j) {
@@ -136,7 +121,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int r = n0 + wave * 32 + j * 8 + srow;
-        ob[j] = src_off(a.w_blocked ? r : min(r, a.N - 1), a.ldw, a.w_blocked);
+        ob[j] = src_off(min(r, a.N - 1), a.ldw);
     }
     const int ldsA_w = wave * (BM / 8) * 128;
     const int ldsB_w = A_BYTES + wave * 32 * 128;
@@ -148,19 +133,10 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
             __builtin_amdgcn_global_load_lds((gptr_t)(a_tile(kt) + oa[j]), (lptr_t)(base + ldsA_w + j * 1024), 16, 0, (OPT & 1) ? 2 : 0);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_global_load_lds((gptr_t)((const char*)W + ob[j] + (long)kt * w_step), (lptr_t)(base + ldsB_w + j * 1024), 16, 0, (OPT & 2) ? 2 : 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)((const char*)W + ob[j] + (long)kt * 128), (lptr_t)(base + ldsB_w + j * 1024), 16, 0, 0);
     };
 
     float4_t acc[MT][4];
-    // (OPT & 16384, below: the timing-only 32x32x16 form of the ping-pong K loop)
-    typedef float float16v __attribute__((ext_vector_type(16)));
-    [[maybe_unused]] float16v acc32[8];
-    if constexpr ((OPT & 16384) != 0) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int k = 0; k < 16; ++k) acc32[i][k] = 0.f;
-    }
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -214,7 +190,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     //     once per K-tile, in M2, never 0 inside the loop): the two half-tiles just issued stay in flight across the barriers;
     //   * the two wave rows run ONE barrier apart: while wm = 0 issues its MFMAs, wm = 1 reads fragments and issues DMA,
     //     then they swap -- each SIMD holds one wave of either row, so its matrix pipe and its LDS / VMEM issue alternate.
-    // Where a K-tile's ~3100 cycles go (r03s, tools/gemm_stamps.py, shader-clock stamps of one workgroup): per phase and wave, load work
+    // Where a K-tile's ~3100 cycles go (r03s, shader-clock stamps of one workgroup, profiles/r03s_gemm_stamps_*.log): per phase and wave, load work
     // (fragment reads + DMA issue + counted wait) 360-600, wait at the mid barrier for the other row's MFMAs 120-400, the 32 MFMAs 590-640
     // (512 back to back), phase-end barrier turn-around ~130: the half-period is MFMA segment + barrier turn-around ~ 770, the load work
     // hides.  Taking the phase-end barrier 3 or 8 MFMAs early (so that the other row is released while this one still feeds the pipe)
@@ -234,7 +210,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
             const int ra = m0 + (lr >> 6) * 128 + hf * 64 + (lr & 63);
             const int rb = n0 + (lr >> 5) * 64 + hf * 32 + (lr & 31);
             sa8[hf][j] = a_off(ra);
-            sb8[hf][j] = src_off(a.w_blocked ? rb : min(rb, a.N - 1), a.ldw, a.w_blocked);
+            sb8[hf][j] = src_off(min(rb, a.N - 1), a.ldw);
         }
     const unsigned smem_lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lptr_t)smem);
     const unsigned wave_lds = (unsigned)__builtin_amdgcn_readfirstlane(wave * 2048);
@@ -246,7 +222,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
         // M = 151 296: qkv 479 -> 468 us, c_fc 698 -> 691, c_proj 582 -> 578, K loop alone +0.6-1.3 %).  The compiler does not see these
         // loads: every wait for them is one of the counted s_waitcnt of the loop (tests/test_isa_sync_templates.py).
         const char* ak = a_tile(kt);
-        const char* wk = (const char*)W + (long)kt * w_step;
+        const char* wk = (const char*)W + (long)kt * 128;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const unsigned dst = smem_lds + (unsigned)(buf * KBUF + which * SLOT + j * 1024) + wave_lds;   // scalar arithmetic only
@@ -254,8 +230,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
                 if constexpr ((OPT & 1) != 0) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" :: "v"(sa8[hf][j]), "s"(ak), "s"(dst) : "memory", "m0");
                 else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(sa8[hf][j]), "s"(ak), "s"(dst) : "memory", "m0");
             } else {
-                if constexpr ((OPT & 2) != 0) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" :: "v"(sb8[hf][j]), "s"(wk), "s"(dst) : "memory", "m0");
-                else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(sb8[hf][j]), "s"(wk), "s"(dst) : "memory", "m0");
+                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(sb8[hf][j]), "s"(wk), "s"(dst) : "memory", "m0");
             }
         }
     };
@@ -275,24 +250,8 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
             fb[jj][1] = *(const half8_t*)(buf + 2 * g * SLOT + b_lane + jj * 2048 + ch1);
         }
     };
-    // OPT & 16384 (experiment builds, timing only, with NOEPI): the K loop's matrix work as v_mfma_f32_32x32x16_f16 -- the same fragment
-    // reads, half as many MFMA instructions (8 of 32 cycles on the issue port instead of 8 of 16); the products are meaningless.
     auto quadrant = [&](int hf, int g, half8_t (&fb)[2][2]) {
         __builtin_amdgcn_s_setprio(1);
-        if constexpr ((OPT & 16384) != 0) {
-#pragma unroll
-            for (int st = 0; st < 2; ++st)
-#pragma unroll
-                for (int ip = 0; ip < 2; ++ip)
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) {
-                        asm volatile("" :: "v"(fa[2 * ip + 1][st]));      // the fragment a real 32x32 layout would fold into its A operand
-                        acc32[(hf * 2 + g) * 2 + jj] =
-                            __builtin_amdgcn_mfma_f32_32x32x16_f16(fb[jj][st], fa[2 * ip][st], acc32[(hf * 2 + g) * 2 + jj], 0, 0, 0);
-                    }
-            __builtin_amdgcn_s_setprio(0);
-            return;
-        }
 #pragma unroll
         for (int st = 0; st < 2; ++st)
 #pragma unroll
@@ -306,23 +265,6 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     __builtin_amdgcn_sched_barrier(0);                                    \
     __builtin_amdgcn_s_barrier();                                         \
     __builtin_amdgcn_sched_barrier(0);
-    // OPT & 8192 (experiment builds, tools/gemm_stamps.py): shader-clock stamps of ONE workgroup at the points of a phase where no LDS
-    // read is outstanding (s_memtime returns through lgkmcnt) -- phase start, MFMA start (behind lgkmcnt(0) + barrier), MFMA end.
-    long long* stamp_p = nullptr;
-    if constexpr ((OPT & 8192) != 0) {
-        if (a.argmax_out && blockIdx.x == 300) stamp_p = (long long*)a.argmax_out + (long)wave * 4096;
-    }
-    int stamp_i = 0;
-#define OVMR_STAMP()                                                                                   \
-    if constexpr ((OPT & 8192) != 0) {                                                                 \
-        if (stamp_p) {                                                                                 \
-            const long long t_ = __builtin_amdgcn_s_memtime();                                         \
-            if (lane == 0) stamp_p[stamp_i] = t_;                                                      \
-            ++stamp_i;                                                                                 \
-        }                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                             \
-    }
-
     // prologue: tile 0 complete, two half-tiles of tile 1 in flight
     stage_half(0, hB0, 0); stage_half(0, hA0, 0); stage_half(0, hB1, 0); stage_half(0, hA1, 0);
     // epilogue constants -> LDS (the compiler waits for their global loads with vmcnt(0), i.e. also for tile 0, which the first
@@ -360,26 +302,21 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
 #define OVMR_P4_MID()                                                     \
     __builtin_amdgcn_sched_barrier(0);                                    \
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                    \
-    OVMR_STAMP()                                                          \
     __builtin_amdgcn_s_barrier();                                         \
     __builtin_amdgcn_sched_barrier(0);
     for (int kt = 0; kt < nk; kt += 2) {
         const bool more = kt + 2 < nk;
         // M1 even: stage B1, A1 of the odd tile
-        OVMR_STAMP()
         read_b(bufE, 0, fb0);
         read_a(bufE, 0);
         read_b(bufE, 1, fb1);
         __builtin_amdgcn_sched_barrier(0);
         stage_half(1, hB1, kt + 1); stage_half(1, hA1, kt + 1);
         OVMR_P4_MID()
-        OVMR_STAMP()
         quadrant(0, 0, fb0);
         quadrant(0, 1, fb1);
-        OVMR_STAMP()
         OVMR_PH_END()
         // M2 even: stage B0, A0 of tile kt+2; the odd tile must have landed
-        OVMR_STAMP()
         read_a(bufE, 1);
         __builtin_amdgcn_sched_barrier(0);
         if (more) { stage_half(0, hB0, kt + 2); stage_half(0, hA0, kt + 2); }
@@ -387,43 +324,34 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
         if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         OVMR_P4_MID()
-        OVMR_STAMP()
         quadrant(1, 1, fb1);
         quadrant(1, 0, fb0);
-        OVMR_STAMP()
         OVMR_PH_END()
         // M1 odd: stage B1, A1 of tile kt+2
-        OVMR_STAMP()
         read_b(bufO, 0, fb0);
         read_a(bufO, 0);
         read_b(bufO, 1, fb1);
         __builtin_amdgcn_sched_barrier(0);
         if (more) { stage_half(0, hB1, kt + 2); stage_half(0, hA1, kt + 2); }
         OVMR_P4_MID()
-        OVMR_STAMP()
         quadrant(0, 0, fb0);
         quadrant(0, 1, fb1);
-        OVMR_STAMP()
         OVMR_PH_END()
         // M2 odd: stage B0, A0 of tile kt+3; tile kt+2 must have landed
-        OVMR_STAMP()
         read_a(bufO, 1);
         __builtin_amdgcn_sched_barrier(0);
         if (more) { stage_half(1, hB0, kt + 3); stage_half(1, hA0, kt + 3); }
         __builtin_amdgcn_sched_barrier(0);
         if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         OVMR_P4_MID()
-        OVMR_STAMP()
         quadrant(1, 1, fb1);
         quadrant(1, 0, fb0);
-        OVMR_STAMP()
         OVMR_PH_END()
     }
 #undef OVMR_P4_MID
     if (wm == 0) __builtin_amdgcn_s_barrier();          // balances the extra barrier of the second wave row
     __builtin_amdgcn_sched_barrier(0);
 #undef OVMR_PH_END
-#undef OVMR_STAMP
     } else
     if (OPT & 4) {
     // K loop with the iteration boundary moved INSIDE the MFMA stream.  All of a K-tile's fragment reads are issued two steps
@@ -541,21 +469,6 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     }
     // ---------------------------------------------------------------- epilogue through LDS
     half_t* C = (half_t*)a.C;
-    if (NOEPI) {            // timing-only ablation: the K loop alone (the store below never happens on real data)
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) sum += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-        if constexpr ((OPT & 16384) != 0) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int k = 0; k < 16; ++k) sum += acc32[i][k];
-        }
-        if (sum == 12345.678f) C[tid] = (half_t)sum;
-        return;
-    }
     if constexpr (EPI == EPI_SCALE_ARGMAX) {
         // Logits that are never stored: u = h(h(acc) * scale) exactly as EPI_SCALE, then per row the maximum of this tile's
         // columns and the LOWEST column holding it.  A row's 64 columns of one wave sit in four lanes (fg) x 16 values;
@@ -604,14 +517,6 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
         }
         return;
     }
-    auto gelu4 = [](half4_t v) -> half4_t {
-        if constexpr ((OPT & 32) != 0) {                // experiment builds: round 1's pairwise form, for the same-process A/B
-            const half2_t lo = quick_gelu_h2((half2_t){v[0], v[1]}), hi = quick_gelu_h2((half2_t){v[2], v[3]});
-            return (half4_t){lo[0], lo[1], hi[0], hi[1]};
-        } else {
-            return quick_gelu_h4(v);
-        }
-    };
     char* et = smem + wave * (64 * EP);                 // this wave's 64-row x 64-column staging tile
     const int er = lane >> 3, ec = (lane & 7) * 8;     // phase 2: row within an 8-row group, first column
     // The staging tile has 128-byte rows of sixteen 8-byte units; unit u of row r is stored at u ^ f(r & 15),
@@ -689,7 +594,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
                         o[r] = u2[0];
                         o[r + 1] = u2[1];
                     }
-                    if (EPI == EPI_LN_BIAS_QGELU && !GFAST) o = gelu4(o);
+                    if (EPI == EPI_LN_BIAS_QGELU && !GFAST) o = quick_gelu_h4(o);
                 } else {
                     // float2 sums and __builtin_convertvector: v_pk_add_f32 + v_cvt_pk_f16_f32 (round to nearest even), two
                     // elements per instruction; element-wise casts made hipcc emit cvt + pack + alignbit chains (3.8 -> ~1.6
@@ -708,7 +613,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
                         o[r] = u2[0];
                         o[r + 1] = u2[1];
                     }
-                    if (EPI == EPI_BIAS_QGELU && !GFAST) o = gelu4(o);
+                    if (EPI == EPI_BIAS_QGELU && !GFAST) o = quick_gelu_h4(o);
                 }
                 *(half4_t*)(et + i * 16 * EP + wr_off[j]) = o;
             }
@@ -752,7 +657,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
             for (int it = 0; it < 8; ++it) {
                 const half8_t v = finish(vv[it], it, it * 8 + er);
                 if (NT) __builtin_nontemporal_store(v, (half8_t*)(dst + it * step));
-                else if (!NOSTORE || (float)v[0] == 12345.678f) *(half8_t*)(dst + it * step) = v;
+                else *(half8_t*)(dst + it * step) = v;
             }
         } else {
 #pragma unroll
@@ -771,7 +676,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
                     }
                     half8_t* dst = (half8_t*)(C + crow * a.ldc + nn);
                     if (NT) __builtin_nontemporal_store(v, dst);
-                    else if (!NOSTORE || (float)v[0] == 12345.678f) *dst = v;   // NOSTORE: timing-only ablation
+                    else *dst = v;
                 }
             }
         }
@@ -810,12 +715,11 @@ int launch_v5(const GemmArgs& a, hipStream_t s) {
     const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN5 - 1) / BN5;
     GemmArgs b = a;
     if (b.n_group <= 0) {
-        static const int force = exp_env("OVMR_N_GROUP");
         // measured (profiles/r01e_gemm_experiments.md): groups of 4-6 raise the L2 hit rate of qkv / c_fc from 65-68 %
         // to 72-73 % but move the run time by < 2 %, and hurt c_proj; the default therefore stays row-major (G = all)
         // with the ping-pong K loop (r02c, same-process A/B at batch 512): groups of 4 N tiles take 1.5-2.5 % off qkv / c_fc
         // (c_fc_ln 496 -> 484 us, qkv_ln 329 -> 325 us), nothing off the N = 768 shapes
-        b.n_group = force > 0 ? std::min(force, tiles_n) : (((OPT & 16) && MT == 8 && tiles_n >= 8) ? 4 : tiles_n);
+        b.n_group = ((OPT & 16) && MT == 8 && tiles_n >= 8) ? 4 : tiles_n;
     }
     if (b.nt_store == 0) {
         // C written with the nontemporal hint does not evict the A / W panels the other tiles of the XCD are streaming from
@@ -823,30 +727,19 @@ int launch_v5(const GemmArgs& a, hipStream_t s) {
         // slower) nor for small outputs the next kernel reads straight back (logits for the argmax).  The hint has to be
         // a template parameter: a run-time branch around two stores of the same value is merged by the compiler, which
         // drops the hint.
-        static const int force = exp_env("OVMR_NT_STORE");
-        b.nt_store = force ? force : (b.epi != EPI_BIAS_RES && (size_t)b.M * b.N * 2 >= ((size_t)48 << 20) ? 2 : 1);
+        b.nt_store = b.epi != EPI_BIAS_RES && (size_t)b.M * b.N * 2 >= ((size_t)48 << 20) ? 2 : 1;
     }
     constexpr int XB = OPT & 2048;                      // QuickGELU form: carried into every K-loop choice below
-    constexpr int P8 = OPT & (16 | 32 | XB);            // (32: experiment bit, rides along) ping-pong K loop (256-row tiles; it replaces the OPT & 4 loop there)
-    constexpr bool PLAIN = (OPT & ~(16 | 32 | XB)) == 0;
+    constexpr int P8 = OPT & (16 | XB);                 // ping-pong K loop (256-row tiles; it replaces the OPT & 4 loop there)
+    constexpr bool PLAIN = (OPT & ~(16 | XB)) == 0;
     constexpr bool OV_OK = !((OPT & 16) && MT == 8);
     if constexpr (PLAIN && OV_OK && (EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_QGELU)) {
         // the LayerNorm-folding launches also run the K loop with the boundary inside the MFMA stream (qkv_ln 354 -> 343 us,
         // c_fc_ln 525 -> 518 us; the plain bias / QuickGELU launches of the same shapes do not gain)
-        static const int ov_force = exp_env("OVMR_K_OVERLAP");
-        if (ov_force != 1) {
-            if (b.nt_store == 2) return launch_v5_k<EPI, MT, XB | 4 | 512>(b, tiles_m, tiles_n, s);
-            return launch_v5_k<EPI, MT, XB | 4>(b, tiles_m, tiles_n, s);
-        }
+        if (b.nt_store == 2) return launch_v5_k<EPI, MT, XB | 4 | 512>(b, tiles_m, tiles_n, s);
+        return launch_v5_k<EPI, MT, XB | 4>(b, tiles_m, tiles_n, s);
     }
     if constexpr (PLAIN && EPI != EPI_BIAS_RES) {
-#ifdef OVMR_EXPERIMENTS
-        static const bool a_nt_all = exp_env("OVMR_A_NT") == 3;   // nontemporal A stream on every epilogue: measured slower (r02c)
-        if (a_nt_all) {
-            if (b.nt_store == 2) return launch_v5_k<EPI, MT, P8 | 1 | 512>(b, tiles_m, tiles_n, s);
-            return launch_v5_k<EPI, MT, P8 | 1>(b, tiles_m, tiles_n, s);
-        }
-#endif
         if (b.nt_store == 2) return launch_v5_k<EPI, MT, P8 | 512>(b, tiles_m, tiles_n, s);
     }
     if constexpr (PLAIN && EPI == EPI_BIAS_RES) {
@@ -856,9 +749,8 @@ int launch_v5(const GemmArgs& a, hipStream_t s) {
         //     9-12 N tiles per A panel the same hint costs 6-11 %, and on the W operand it always costs.
         // (2) K >= 2048: the K loop with the iteration boundary inside the MFMA stream (OPT & 4): c_proj 467 -> 449 us; at
         //     K = 768 (12 K-tiles) it is neutral to 2 % slower.
-        static const int a_nt_force = exp_env("OVMR_A_NT"), ov_force = exp_env("OVMR_K_OVERLAP");   // 1 = never, 2 = always
-        const bool a_nt = a_nt_force != 1 && (a_nt_force == 2 || (tiles_n <= 4 && tiles_m * tiles_n >= 512));
-        const bool ov = OV_OK && ov_force != 1 && (ov_force == 2 || b.K >= 2048);
+        const bool a_nt = tiles_n <= 4 && tiles_m * tiles_n >= 512;
+        const bool ov = OV_OK && b.K >= 2048;
         if (a_nt && ov) return launch_v5_k<EPI, MT, XB | 5>(b, tiles_m, tiles_n, s);
         if (ov) return launch_v5_k<EPI, MT, XB | 4>(b, tiles_m, tiles_n, s);
         if (a_nt) return launch_v5_k<EPI, MT, P8 | 1>(b, tiles_m, tiles_n, s);
@@ -868,15 +760,13 @@ int launch_v5(const GemmArgs& a, hipStream_t s) {
 
 template <int EPI, int OPT>
 int pick_v5(const GemmArgs& a, hipStream_t s) {
-    static const int g_force_mt = exp_env("OVMR_FORCE_MT");   // experiment builds: 4 | 8 pins the M tile
     auto eff = [&](int bm) {
         const double t = (double)((a.M + bm - 1) / bm) * ((a.N + BN5 - 1) / BN5);
         return t / (ceil(t / 256.0) * 256.0);
     };
     const double t256 = (double)((a.M + 255) / 256) * ((a.N + BN5 - 1) / BN5);
     bool big;
-    if (g_force_mt) big = g_force_mt == 8;
-    else if ((OPT & 16) && (a.K % 128) == 0) {
+    if ((OPT & 16) && (a.K % 128) == 0) {
         // ping-pong K loop on 256-row tiles against the double-buffered loop on 128-row tiles: a round of 128-row tiles takes
         // ~0.74 of a round of 256-row tiles (r02d, batch 256: out_proj 19.8 vs 26.6 us, c_proj 59 vs 78 us per round), so the
         // big tile wins unless the small one saves a whole round -- e.g. 591 tiles (batch 256, N = 768): 3 rounds against
@@ -938,15 +828,6 @@ int launch_gemm_f16_v5(const GemmArgs& a, int variant, hipStream_t s) {
     if (lnf && ((a.N & 63) || !a.ln_stats || a.ln_slots < 1 || !a.ln_g || !a.ln_b)) return -2;
     if (a.stats_out && (a.epi != EPI_BIAS_RES || (a.N & 255))) return -2;
     switch (variant) {
-#ifdef OVMR_EXPERIMENTS   // timing-only ablations (their outputs are wrong by construction): no stores / no epilogue at all
-        case 18: return a.epi == EPI_BIAS_QGELU ? pick_v5<EPI_BIAS_QGELU, 64>(a, s) : pick_v5<EPI_BIAS, 64>(a, s);
-        case 19: return pick_v5<EPI_BIAS, 128>(a, s);
-        case 28: return a.epi == EPI_BIAS_QGELU ? pick_v5<EPI_BIAS_QGELU, 16 | 64>(a, s) : pick_v5<EPI_BIAS, 16 | 64>(a, s);
-        case 29: return pick_v5<EPI_BIAS, 16 | 128>(a, s);
-        case 38: return (a.K % 128) == 0 ? dispatch_v5<16 | 32>(a, s) : dispatch_v5<32>(a, s);   // variant 8 with the pairwise QuickGELU
-        case 59: return pick_v5<EPI_BIAS, 16 | 128 | 16384>(a, s);   // variant 29 (K loop alone) with 32x32x16 MFMAs: timing only
-        case 58: return pick_v5<EPI_BIAS, 16 | 8192>(a, s);   // variant 8 with shader-clock stamps of workgroup 300 (a.argmax_out = stamp buffer; tools/gemm_stamps.py)
-#endif
         case 6: return dispatch_v5<0>(a, s);
         case 8: return (a.K % 128) == 0 ? dispatch_v5<16>(a, s) : dispatch_v5<0>(a, s);   // ping-pong K loop: two K-tiles per iteration
         default: return -5;                                                                // unknown variant

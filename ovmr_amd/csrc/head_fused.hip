@@ -32,29 +32,14 @@
 #include "common.h"
 
 #include <algorithm>
-#ifdef OVMR_EXPERIMENTS
-#include <cstdlib>
-#endif
 
 namespace {
-
-#ifdef OVMR_EXPERIMENTS
-inline int exp_env(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
-#endif
 
 typedef float float16_t __attribute__((ext_vector_type(16)));
 
 constexpr int HF_BN = 128;                 // classes per tile: 4 waves x 32
 enum { HF_TICKET = 0, HF_DONE = 1, HF_LEFT_N = 2, HF_LEFT_POP = 3, HF_EXIT = 4, HF_DUTY_TICKET = 5, HF_DUTY_DONE = 6, HF_SYNC_INTS = 16 };
 constexpr int HF_LOCAL_MERGE_MAX = 16;     // class tiles up to which every workgroup merges its rows' per-tile statistics itself (C <= 2048)
-
-#ifdef OVMR_EXPERIMENTS
-// shader-clock stamps of workgroup 0 (tools/head_bench.py --stamps): where a launch spends its time
-__device__ long long g_head_stamps[16];
-#define HF_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_head_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define HF_STAMP(i)
-#endif
 
 __device__ __forceinline__ int aload(int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void astore(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -63,26 +48,19 @@ __device__ __forceinline__ int aadd(int* p, int v) { return __hip_atomic_fetch_a
 
 // "This tile / unit is done" and "everything is done": the orderings of the device-wide phases.  The data they order (per-tile statistics,
 // merged statistics, the recompute queue) are written and read with agent-scope atomic accesses, which on gfx950 go to device-coherent
-// memory by themselves; the product build orders them against the counters the way the ISA does -- every thread drains its stores
+// memory by themselves; the kernel orders them against the counters the way the ISA does -- every thread drains its stores
 // (s_waitcnt vmcnt(0)), the workgroup meets at a barrier, one thread bumps the counter; readers spin on the counter, meet at a barrier,
 // then issue their loads -- with RELAXED atomics, i.e. without the cache-wide write-back / invalidate a release / acquire pair at agent
 // scope compiles to (buffer_wbl2 sc1 / buffer_inv sc1: measured 3 us of a 30 us launch at 1000 classes, 33 us at 10 000, round 5).
-// ACQREL = true is that formally ordered form (C++ memory model: release on the increments, acquire after the spins); the experiment
-// build selects it with OVMR_HEAD_ACQREL=1 so that its cost stays measurable (tools/head_bench.py --acqrel; profiles/r06*_head_acqrel.log)
-// and tools/race_screen.py screens the relaxed form the product ships.
-template <bool ACQREL>
-__device__ __forceinline__ void hf_signal(int* counter) {
-    if constexpr (ACQREL) __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    else aadd(counter, 1);
-}
-template <bool ACQREL>
+// The formally ordered form (C++ memory model: release on the increments, acquire after the spins) cost 2-18 % of a launch
+// (r06c: profiles/r06c_head_bench_acqrel.log against r06c_head_bench_relaxed.log); tools/race_screen.py screens the relaxed form.
+__device__ __forceinline__ void hf_signal(int* counter) { aadd(counter, 1); }
 __device__ __forceinline__ void hf_wait(int* counter, int target) {
     while (aload(counter) < target) __builtin_amdgcn_s_sleep(2);
-    if constexpr (ACQREL) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 
 // BM: query rows per tile (32 or 64).  RAW: one classifier, fp16 logits out, no softmax.
-template <int BM, bool RAW, bool ACQREL = false>
+template <int BM, bool RAW>
 __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __restrict__ feats, int B, int D, float scale,
                                                          const half_t* __restrict__ c0, const half_t* __restrict__ c1,
                                                          const half_t* __restrict__ c2, int n_mod, int C,
@@ -332,7 +310,6 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __rest
         };
 
         // ---- phase 1: tiles by ticket; the last one taken stays in registers, earlier ones are queued for phase 2
-        HF_STAMP(0);
         int held = -1;
         for (;;) {
             __syncthreads();
@@ -341,20 +318,15 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __rest
             const int t = sh_t;
             if (t >= n_tiles) break;
             if (held >= 0 && tid == 0) __hip_atomic_store(leftover + aadd(sync + HF_LEFT_N, 1), held, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            HF_STAMP(1);
             compute(t);
-            HF_STAMP(2);
             stats(t);
-            HF_STAMP(3);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every thread: its pairs (and the queue entry) have reached device-coherent memory ...
             __syncthreads();
-            if (tid == 0) hf_signal<ACQREL>(sync + HF_DONE);          // ... before the tile counts as done
+            if (tid == 0) hf_signal(sync + HF_DONE);          // ... before the tile counts as done
             held = t;
         }
-        HF_STAMP(4);
-        if (tid == 0) hf_wait<ACQREL>(sync + HF_DONE, n_tiles);
+        if (tid == 0) hf_wait(sync + HF_DONE, n_tiles);
         __syncthreads();                                              // (the pairs are read with device-coherent loads: nothing to invalidate)
-        HF_STAMP(5);
         if (Tc > HF_LOCAL_MERGE_MAX) {
             // Many class tiles: every workgroup of a row tile merging ALL of that row tile's pairs itself re-reads O(tiles^2) pairs
             // (256 x 10 000: 74 us of uncached loads).  Instead the (row, classifier) statistics are merged ONCE: units of four of
@@ -393,15 +365,13 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __rest
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
-                if (tid == 0) hf_signal<ACQREL>(sync + HF_DUTY_DONE);
+                if (tid == 0) hf_signal(sync + HF_DUTY_DONE);
             }
-            if (tid == 0) hf_wait<ACQREL>(sync + HF_DUTY_DONE, n_units);
+            if (tid == 0) hf_wait(sync + HF_DUTY_DONE, n_units);
             __syncthreads();
         }
-        HF_STAMP(6);
         // ---- phase 2
         if (held >= 0) emit(held);
-        HF_STAMP(7);
         for (;;) {
             __syncthreads();
             if (tid == 0) {
@@ -420,7 +390,6 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __rest
 #pragma unroll
             for (int i = 0; i < 8; ++i) __hip_atomic_store(sync + i, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        HF_STAMP(8);
     }
 }
 
@@ -429,10 +398,6 @@ int launch_one(const half_t* feats, int B, int D, float scale, const half_t* con
                float* out, half_t* raw_out, float* partial, float* merged, int* leftover, int* sync, int Tc, size_t lds, int max_grid, hipStream_t s) {
     const int Tr = (B + BM - 1) / BM, n_tiles = Tr * Tc;
     auto kern = head_fused_kernel<BM, RAW>;
-#ifdef OVMR_EXPERIMENTS
-    static const bool acqrel = exp_env("OVMR_HEAD_ACQREL") == 1;      // the release / acquire form of the phase counters (A/B: its cost)
-    if (acqrel && !RAW) kern = head_fused_kernel<BM, RAW, true>;
-#endif
     static size_t lds_set[OVMR_MAX_DEVICES] = {};            // per (BM, RAW) and device: the largest dynamic LDS size granted so far
     if (lds > 64 * 1024) {
         int dev = 0;
@@ -440,9 +405,6 @@ int launch_one(const half_t* feats, int B, int D, float scale, const half_t* con
         if (dev < 0 || dev >= OVMR_MAX_DEVICES) return -100;
         if (lds > lds_set[dev]) {
             HIP_CHECK_RET(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#ifdef OVMR_EXPERIMENTS
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)head_fused_kernel<BM, RAW, !RAW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-#endif
             lds_set[dev] = lds;
         }
     }
@@ -487,9 +449,3 @@ int launch_head_fused(const half_t* feats, int B, int D, float scale, const half
     return BM == 32 ? launch_one<32, false>(feats, B, D, scale, clf, n_mod, C, w, out, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s)
                     : launch_one<64, false>(feats, B, D, scale, clf, n_mod, C, w, out, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s);
 }
-
-#ifdef OVMR_EXPERIMENTS
-extern "C" int ovmr_debug_head_stamps(long long* host_out) {
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_head_stamps), 16 * sizeof(long long));
-}
-#endif

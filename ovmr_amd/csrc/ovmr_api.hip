@@ -14,11 +14,6 @@
 #include <string>
 #include <vector>
 
-#ifdef OVMR_EXPERIMENTS
-int launch_qkv_attn_fused(const half_t* x, const half_t* wf, const float* ln_g, const float* ln_b, const float* stats, half_t* out,
-                          int B, int L, int W, hipStream_t s);     // csrc/experiments/qkv_attn_fused.hip
-#endif
-
 namespace {
 
 struct Buf {
@@ -55,7 +50,6 @@ struct ovmr_handle {
     int xval_fused = 1;                       // cross-validation logits: row argmax fused into the GEMM epilogue (never stored)
     int fused_head = 1;                       // ovmr_fused_logits / ovmr_zeroshot_logits as ONE launch (head_fused.hip); 0: scale + GEMMs + softmax
     int head_max_grid = 0;                    // > 0 caps the fused head's grid (tests: workgroups then take several tiles)
-    int fuse_qkv_attn = 0;                    // experiment build only: in_proj + attention of the vision blocks as ONE launch per block (csrc/experiments/qkv_attn_fused.hip)
     int* head_sync = nullptr;                 // the fused head's device counters (zero between launches)
     float logit_scale_exp = 100.f;
     bool have_logit_scale = false;
@@ -217,15 +211,6 @@ int run_block_f16(ovmr_handle* h, const Block& k, half_t* x, half_t* y, half_t* 
     int M = nseq * L;
     if (groups) { M = 0; for (auto& g : *groups) M += g.nseq * g.L; }
     const int H = W / 64, slots = W / 256;
-#ifdef OVMR_EXPERIMENTS
-    if (stats && h->fuse_qkv_attn && !groups && !causal) {             // experiment: qkv never leaves the CU (bit-equal to the two launches below)
-        const int rc = launch_qkv_attn_fused(x, k.in_wf, k.in_g, k.in_bf, stats, y, nseq, L, W, s);
-        if (rc != -100) {
-            CK(rc);
-            goto attention_done;
-        }
-    }
-#endif
     if (stats) {
         CK(launch_gemm_f16(gemm_ln(gemm(x, W, k.in_wf, W, qkv, 3 * W, M, 3 * W, W, EPI_LN_BIAS), stats, slots, k.in_g, k.in_bf), h->gemm_variant, s));
     } else {
@@ -247,9 +232,6 @@ int run_block_f16(ovmr_handle* h, const Block& k, half_t* x, half_t* y, half_t* 
                 CK(launch_attention_f16(qkv + g.row0 * 3 * W, y + g.row0 * W, g.nseq, g.L, H, causal, h->attn_variant, s));
     } else
         CK(launch_attention_f16(qkv, y, nseq, L, H, causal, h->attn_variant, s));
-#ifdef OVMR_EXPERIMENTS
-attention_done:
-#endif
     CK(launch_gemm_f16(gemm_stats(gemm(y, W, k.out_w, W, x, W, M, W, W, EPI_BIAS_RES, k.out_b, x, W), stats), h->gemm_variant, s));
     if (stats) {
         CK(launch_gemm_f16(gemm_ln(gemm(x, W, k.fc_wf, W, hid, 4 * W, M, 4 * W, W, EPI_LN_BIAS_QGELU), stats, slots, k.fc_g, k.fc_bf), h->gemm_variant + (h->gelu_exact ? 0 : 100), s));
@@ -463,9 +445,6 @@ int ovmr_set_option(ovmr_handle* h, const char* key, int value) {
     else if (!strcmp(key, "fused_head")) h->fused_head = value;
     else if (!strcmp(key, "head_max_grid")) h->head_max_grid = value;
     else if (!strcmp(key, "gelu_exact")) h->gelu_exact = value;
-#ifdef OVMR_EXPERIMENTS
-    else if (!strcmp(key, "fuse_qkv_attn")) h->fuse_qkv_attn = value;
-#endif
     else return fail(h, OVMR_E_NAME, "unknown option '%s'", key);
     return 0;
 }
@@ -1004,16 +983,6 @@ int ovmr_debug_gemm(int f32, int variant, const void* A, const void* W, const vo
                     const void* pos, void* C, int M, int N, int K, int ldc, int epi, float scale,
                     int rows_in, int rows_out, ovmr_stream stream) {
     GemmArgs a = gemm(A, K, W, K, C, ldc, M, N, K, epi, bias, res, ldc);
-#ifdef OVMR_EXPERIMENTS
-    if (const char* e = getenv("OVMR_DEBUG_LDPAD")) {   // stride experiment (tools/gemm_bench.py --ldpad): operands have padded rows
-        a.lda = K + atoi(e);
-        a.ldw = K + atoi(e);
-    }
-    if (const char* e = getenv("OVMR_DEBUG_BLOCKED")) {   // timing-only layout experiment (operands are random anyway)
-        a.a_blocked = atoi(e) & 1;
-        a.w_blocked = (atoi(e) >> 1) & 1;
-    }
-#endif
     a.pos = pos; a.scale = scale; a.rows_in = rows_in; a.rows_out = rows_out;
     if (epi == EPI_LN_BIAS || epi == EPI_LN_BIAS_QGELU) {   // LN-folding epilogues: bias = ln_b fp32 [N], pos = ln_g fp32 [N], res = statistics fp32 [M][K/256][2]
         a.ln_b = (const float*)bias; a.ln_g = (const float*)pos; a.ln_stats = (const float*)res; a.ln_slots = K / 256;
@@ -1023,12 +992,6 @@ int ovmr_debug_gemm(int f32, int variant, const void* A, const void* W, const vo
         a.argmax_out = (float*)C;
         a.C = nullptr;
     }
-#ifdef OVMR_EXPERIMENTS
-    if (variant == 58) {                                    // shader-clock stamps of the ping-pong K loop: pos = int64 [8 waves][4096] (tools/gemm_stamps.py)
-        a.argmax_out = (float*)pos;
-        a.pos = nullptr;
-    }
-#endif
     if (epi == EPI_BIAS_RES && pos) {                       // statistics epilogue: pos = fp32 [M][N/256][2] output
         a.stats_out = (float*)pos;
         a.pos = nullptr;

@@ -59,6 +59,14 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in src.replace("no CPU fallback", ""), f"{f} mentions the oracle"
 
 
+def test_product_library_reads_no_environment():
+    """the library has no environment switches and no experiment build."""
+    csrc = os.path.join(REPO, "ovmr_amd", "csrc")
+    bad = [os.path.relpath(os.path.join(root, f), csrc) for root, _, files in os.walk(csrc) for f in files
+           if any(w in open(os.path.join(root, f), errors="replace").read() for w in ("OVMR_EXPERIMENTS", "getenv"))]
+    assert not bad, f"environment switches or experiment code in {bad}"
+
+
 def test_shard_helpers():
     from ovmr_amd.shard import shard_batches, shard_range
     for n in (1, 7, 8, 1000, 1001):

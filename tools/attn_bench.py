@@ -3,10 +3,7 @@
 import ctypes, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# variant 4's timing-only ablations (400 + mode, attention_v4.hip) live in the experiment build only
-# The product library is timed unless --exp is given (experiment build: ablation variants and A/B switches); the library loaded is printed.
-if "--exp" in sys.argv:
-    os.environ.setdefault("OVMR_HIP_LIB", os.path.join(ROOT, "ovmr_amd", "lib", "libovmr_hip_exp.so"))
+# The library loaded (OVMR_HIP_LIB, else the product build) is printed.
 import torch
 from ovmr_amd import runtime
 
@@ -16,7 +13,6 @@ ap.add_argument("--only", default="")
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--batch", type=int, default=512, help="images of the image-tower shape")
 ap.add_argument("--variants", type=int, nargs="+", default=[0, 1, 3])
-ap.add_argument("--exp", action="store_true", help="time libovmr_hip_exp.so (experiment build: variant 4 and its ablation modes) instead of the product library")
 args = ap.parse_args()
 lib = runtime.load_library()
 print("library:", os.environ.get("OVMR_HIP_LIB", runtime.LIB_PATH), flush=True)

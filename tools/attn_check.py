@@ -1,19 +1,16 @@
 #!/usr/bin/env python3
-"""Attention variants (experiment build) against the fp64 statement of clip/model.py:184-188 at the ViT-L shapes, with the spiked keys of
+"""Attention variants against the fp64 statement of clip/model.py:184-188 at the ViT-L shapes, with the spiked keys of
 tests/test_hip_kernels.py:test_attention_f16 (rescale path, late-block reference move) and a row whose scores are all far below zero."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if "--exp" in sys.argv:
-    os.environ.setdefault("OVMR_HIP_LIB", os.path.join(ROOT, "ovmr_amd", "lib", "libovmr_hip_exp.so"))
 import torch
 from ovmr_amd import runtime
 lib = runtime.load_library()
 variants = [int(a) for a in sys.argv[1:] if a.lstrip("-").isdigit()] or [1, 3]
 p = lambda t: ctypes.c_void_p(t.data_ptr())
 s = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-# (330 % 64 = 10, 268 % 64 = 12: the peeled tail block of attention_v5.hip holds 9-16 keys -- with the spike on key L - 3 the tail's row maxima
-#  exceed 8, the FOLD variant's rescale threshold: ADVICE round 5)
+# (330 % 64 = 10, 268 % 64 = 12: the peeled tail block of attention_v5.hip holds 9-16 keys, with the spike on key L - 3 in it)
 for B, L, H in ((2, 577, 16), (3, 257, 16), (1, 300, 4), (2, 1025, 2), (1, 330, 4), (2, 268, 2)):
     g = torch.Generator().manual_seed(B * L + H)
     qkv = torch.randn(B * L, 3 * H * 64, generator=g).half()

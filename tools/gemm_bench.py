@@ -12,10 +12,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# The product library is timed unless --exp is given: the experiment build (python -m ovmr_amd.build --experiments) carries the A/B
-# environment switches and the timing-only ablation variants; the library actually loaded is printed.
-if "--exp" in sys.argv:
-    os.environ.setdefault("OVMR_HIP_LIB", os.path.join(ROOT, "ovmr_amd", "lib", "libovmr_hip_exp.so"))
 import torch
 from ovmr_amd import runtime
 
@@ -27,13 +23,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--zeros", action="store_true", help="zero-filled operands: shows how much of the time is clock/power (cdna guide rule 25)")
-    ap.add_argument("--ldpad", type=int, default=0, help="row padding (halves) of A and W: stride experiment")
     ap.add_argument("--shapes", default="", help="comma-separated shape names to run (default: all) -- one name per profiler pass gives per-shape "
                     "counters for launches that share a kernel instantiation AND a grid (out_proj / c_proj: tools/pmc_gemm.sh)")
-    ap.add_argument("--exp", action="store_true", help="time libovmr_hip_exp.so (experiment build) instead of the product library")
     args = ap.parse_args()
-    if args.ldpad:
-        os.environ["OVMR_DEBUG_LDPAD"] = str(args.ldpad)
     lib = runtime.load_library()
     print("library:", os.environ.get("OVMR_HIP_LIB", runtime.LIB_PATH), flush=True)
     dev = "cuda"
@@ -50,8 +42,8 @@ def main():
         if only and name not in only:
             continue
         g = torch.Generator(device=dev).manual_seed(1)
-        A = (torch.randn((m + 256, k + args.ldpad), generator=g, device=dev) * 0.5).half()   # slack rows: blocked-layout experiment
-        W = (torch.randn((n + 256, k + args.ldpad), generator=g, device=dev) * k ** -0.5).half()
+        A = (torch.randn((m + 256, k), generator=g, device=dev) * 0.5).half()   # (256 slack rows: the operands of the recorded runs)
+        W = (torch.randn((n + 256, k), generator=g, device=dev) * k ** -0.5).half()
         if args.zeros:
             A.zero_(); W.zero_()
         b = (torch.randn((n,), generator=g, device=dev) * 0.1).half()
@@ -67,8 +59,6 @@ def main():
             call = lambda v: lib.ovmr_debug_gemm(0, v, p(A), p(W), p(b), p(C), p(st), p(C), m, n, k, n, 3, 100.0, 0, 0, s())
         else:
             call = lambda v: lib.ovmr_debug_gemm(0, v, p(A), p(W), p(b), p(C) if epi == 3 else None, None, p(C), m, n, k, n, epi, 100.0, 0, 0, s())
-        if epi in (6, 7, 13) and any(12 <= v <= 19 or v in (28, 29, 59) for v in args.variants):
-            continue                                  # timing-only ablation variants carry no LN-folding epilogues
         for v in args.variants:
             for _ in range(3):
                 assert call(v) == 0

@@ -4,10 +4,6 @@ into a hipGraph, 10 replays timed with HIP events (device time per call, no per-
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-if "--acqrel" in sys.argv:      # experiment build: release / acquire on the phase counters of the one-launch head (head_fused.hip hf_signal / hf_wait)
-    os.environ["OVMR_HEAD_ACQREL"] = "1"
-if "--stamps" in sys.argv or "--acqrel" in sys.argv or "--exp" in sys.argv:
-    os.environ.setdefault("OVMR_HIP_LIB", os.path.join(ROOT, "ovmr_amd", "lib", "libovmr_hip_exp.so"))
 import torch
 from ovmr_amd import synth
 from ovmr_amd.runtime import Engine
@@ -48,14 +44,4 @@ for name, B, C in (("ViT-B/16", 256, 1000), ("ViT-B/16", 256, 10000), ("ViT-B/16
             e1.record(st)
             torch.cuda.synchronize()
         res[tag + "_us"] = round(e0.elapsed_time(e1) * 1000.0 / 200, 1)
-    if "--stamps" in sys.argv:
-        import ctypes
-        e.set_option("fused_head", 2)
-        e.fused_logits(f, *clf, w, "fusion")
-        torch.cuda.synchronize()
-        buf = (ctypes.c_longlong * 16)()
-        e.lib.ovmr_debug_head_stamps.argtypes = [ctypes.c_void_p]
-        e.lib.ovmr_debug_head_stamps(buf)
-        names = ["start", "ticket", "compute", "stats", "release+done", "all done", "acquire", "emit", "exit"]
-        res["stamps_shader_cycles"] = {names[i + 1]: int(buf[i + 1] - buf[i]) for i in range(8)}
     print(json.dumps({"embed_dim": D, "queries": B, "classes": C, **res}), flush=True)
