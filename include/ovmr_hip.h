@@ -149,6 +149,16 @@ typedef struct {
 } ovmr_text_group;
 int ovmr_encode_text_groups(ovmr_handle* h, const ovmr_text_group* groups, int n_groups, ovmr_stream stream);
 
+/* ZeroshotCLIP2.build_model (trainers/zsclip.py:85-96): the prompt-ensembled zero-shot text classifier.  ids: [T, C, context_length]
+ * int64, template-major (the reference's loop order, :89-91).  seq_lens: HOST array [T], each template's exact length (max EOT
+ * position + 1), or NULL for context_length.  out: [C, embed_dim] fp16 = normalise(mean_t normalise(encode_text(ids[t]))) with the
+ * reference's fp16 rounding points (:92-96; csrc/text_ensemble.hip lists them).  Per chunk of classes, all T templates go through ONE
+ * pass of the text tower as T groups (as ovmr_encode_text_groups with normalize = 0: bit-identical raw rows), then one launch
+ * ensembles them; the chunk is sized so that the tower's rows plus a [T, chunk, embed_dim] scratch fit the workspace, so any
+ * vocabulary runs without allocation.  OVMR_E_SHAPE when one class's T prompts do not fit; C == 0 returns 0. */
+int ovmr_encode_text_ensemble(ovmr_handle* h, const int64_t* ids, int T, int C, const int32_t* seq_lens,
+                              void* out_f16, ovmr_stream stream);
+
 /* token_embedding(ids).type(fp16) (trainers/mm_classifier_one_prompt.py:129-130): ids [N, L] int64
  * -> out [N, L, transformer_width] fp16. */
 int ovmr_embed_tokens(ovmr_handle* h, const int64_t* ids, int N, int L, void* out_f16, ovmr_stream stream);

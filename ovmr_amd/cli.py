@@ -5,6 +5,11 @@
         --model-dir ./checkpoints --load-epoch 30 --output-dir output_ovmr/generated_classifiers \\
         --eval_mode fusion --eval_tau 10 --n_ctx 2  DATASET.NUM_SHOTS 16
 
+    python -m ovmr_amd.cli --eval-only --trainer ZeroshotCLIP2 --root DATA --clip-weights ViT-B-16.pt \\
+        --bpe-path bpe_simple_vocab_16e6.txt.gz --output-dir output/zsclip2 DATASET.NAME Caltech101
+
+runs the zero-shot trainers of trainers/zsclip.py on the same folder data set (main_zeroshot), and
+
 takes the command line of `scripts/mm_cls/generate_classifier.sh:30-44` / `train.py:183-255` as it is: `--dataset-config-file` and
 `--config-file` (YAML, read with PyYAML), the flags `reset_cfg` copies (`--root --output-dir --seed --trainer --backbone --init_weight
 --n_ctx --eval_mode --eval_tau`) and the trailing `KEY VALUE` opts, merged in train.py's order by `ovmr_amd.config.setup_cfg` with the
@@ -260,10 +265,14 @@ BACKBONES = {"ViT-B/16": (768, 16, 12), "ViT-B/32": (768, 32, 12), "ViT-L/14": (
 
 def main(argv=None) -> Dict[str, float]:
     from . import config
+    from .templates import ZEROSHOT_TRAINERS
     args = parse(argv)
     cfg = config.setup_cfg(args)                              # train.py:134-155
-    if cfg.TRAINER.NAME != "MM_CLS_OP" or not args.eval_only:
-        raise SystemExit("only `--eval-only --trainer MM_CLS_OP` (classifier generation / evaluation) is on the hot path")
+    if cfg.TRAINER.NAME not in ("MM_CLS_OP",) + ZEROSHOT_TRAINERS or not args.eval_only:
+        raise SystemExit("only `--eval-only --trainer MM_CLS_OP` (classifier generation / evaluation) and `--eval-only --trainer "
+                         "ZeroshotCLIP | ZeroshotCLIP2` (zero-shot evaluation) are on the hot path")
+    if cfg.TRAINER.NAME in ZEROSHOT_TRAINERS:
+        return main_zeroshot(args, cfg)
     out_dir = cfg.OUTPUT_DIR
     if osp.isdir(out_dir) and osp.exists(osp.join(out_dir, "mm_classifiers.pt")):
         print(f"Oops! The results exist at {out_dir} (so skip this job)")       # generate_classifier.sh:27-28
@@ -377,6 +386,80 @@ def main(argv=None) -> Dict[str, float]:
     if own_group:
         dist.barrier()
         dist.destroy_process_group()
+    return results
+
+
+def main_zeroshot(args, cfg) -> Dict[str, float]:
+    """`--eval-only --trainer ZeroshotCLIP | ZeroshotCLIP2` (trainers/zsclip.py): the classes and test items of the MM_CLS_OP job on the
+    same folder data set and command line (build_splits; no exemplar is decoded), the text classifier from DATASET.NAME's template(s),
+    the test set through inference_batches into the on-device evaluator; the result block and acc_per_class.csv / f1_per_class.csv
+    land in OUTPUT_DIR, no model file is written."""
+    import copy
+    from . import templates
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit(f"--trainer {cfg.TRAINER.NAME} runs in one process: sharding the zero-shot test pass over ranks is not implemented")
+    try:
+        templates.check_dataset(cfg.DATASET.NAME)
+    except KeyError as e:
+        raise SystemExit(e.args[0]) from None
+    batch = cfg.DATALOADER.TEST.BATCH_SIZE
+    # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set); nothing of the draw is decoded
+    split_cfg = copy.deepcopy(cfg)
+    split_cfg.DATASET.NUM_SHOTS = max(1, cfg.DATASET.NUM_SHOTS)
+    classnames, _, test_items = build_splits(split_cfg, args.eval_split, args.test_split, args.exemplar_list)
+
+    import torch
+    from . import checkpoint, modules
+    from .evaluator import Classification
+    from .tokenizer import BPETokenizer
+    if cfg.SEED >= 0:
+        print(f"Setting fixed seed: {cfg.SEED}")              # train.py:157-159
+        torch.manual_seed(cfg.SEED)
+    name = cfg.MODEL.BACKBONE.NAME
+    print(f"Loading CLIP (backbone: {name})")                # trainers/zsclip.py:38
+    clip_model = modules.build_model(checkpoint.load_clip_state_dict(args.clip_weights), device=args.device)
+    spec = clip_model.spec
+    size = spec.image_resolution
+    if name:
+        if name not in BACKBONES:
+            raise SystemExit(f"MODEL.BACKBONE.NAME {name!r}: only the ViT CLIP models are on the hot path ({sorted(BACKBONES)})")
+        if (spec.vision_width, spec.vision_patch_size, spec.vision_layers) != BACKBONES[name]:
+            raise SystemExit(f"--clip-weights holds a ViT of width {spec.vision_width}, patch {spec.vision_patch_size}, {spec.vision_layers} layers: "
+                             f"not MODEL.BACKBONE.NAME {name!r}")
+    if tuple(cfg.INPUT.SIZE) != (size, size):
+        raise SystemExit(f"INPUT.SIZE {tuple(cfg.INPUT.SIZE)} does not match the model's input resolution {size}")
+    normalize = "normalize" in tuple(cfg.INPUT.TRANSFORMS)
+    tfm = dict(interpolation=cfg.INPUT.INTERPOLATION, mean=tuple(cfg.INPUT.PIXEL_MEAN) if normalize else None,
+               std=tuple(cfg.INPUT.PIXEL_STD) if normalize else None)
+    workers = cfg.DATALOADER.NUM_WORKERS if args.workers is None else args.workers
+    if workers > 0:
+        from .loader import PipelinedFolderLoader
+        test_loader = PipelinedFolderLoader(test_items, batch, size, workers=workers, prefetch=args.prefetch, device=args.device,
+                                            fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
+        test_loader.warm()                                    # the decode workers start while the text classifier is built
+    else:
+        test_loader = FolderLoader(test_items, batch, size, **tfm)
+    module = modules.ZeroshotCLIP2 if cfg.TRAINER.NAME == "ZeroshotCLIP2" else modules.ZeroshotCLIP
+    model = module.from_classnames(clip_model, classnames, cfg.DATASET.NAME, BPETokenizer(args.bpe_path),
+                                   reserve=(batch, 256, max(1024, len(classnames))))
+    evaluator = Classification(len(classnames), classnames, device=args.device)
+    print("Evaluate on the *test* set")
+    labels = collections.deque()
+
+    def test_images():
+        for b in test_loader:
+            labels.append(b["label"])
+            yield b["img"]
+
+    for out in model.inference_batches(test_images()):       # two test batches in flight (modules.py)
+        evaluator.process(out, labels.popleft())
+    results = dict(evaluator.evaluate(cfg.OUTPUT_DIR or None))
+    st = getattr(test_loader, "stats", None)
+    if st:
+        print(f"input pipeline, test set: {st['images']} images in {st['wall_s']:.2f} s = {st['images_per_s']:.0f} img/s end to end "
+              f"({st['workers']} decode workers), host blocked on decode {st['decode_wait_s']:.2f} s")
+        results["pipeline_test"] = st
+    results["classnames"] = classnames
     return results
 
 

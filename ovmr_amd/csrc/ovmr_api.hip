@@ -14,6 +14,9 @@
 #include <string>
 #include <vector>
 
+// text_ensemble.hip (declared here, not in common.h: that header's hash stamps the committed counter summaries, build.source_sha16)
+int launch_text_ensemble(const half_t* feats, int T, int rows, int E, half_t* out, hipStream_t s);
+
 namespace {
 
 struct Buf {
@@ -748,6 +751,45 @@ int ovmr_encode_text_groups(ovmr_handle* h, const ovmr_text_group* groups, int n
     hipStream_t s = (hipStream_t)stream;
     if (text_groups_ws_bytes(h, M, N) <= h->ws_bytes) return run_text_groups(h, gs, s);      // one pass over all groups
     for (auto& g : gs) CK(run_text_group_chunked(h, g, s));                                    // too many rows for the workspace
+    return 0;
+}
+
+int ovmr_encode_text_ensemble(ovmr_handle* h, const int64_t* ids, int T, int C, const int32_t* seq_lens, void* out_f16,
+                              ovmr_stream stream) {
+    if (!h || T < 1 || C < 0) return OVMR_E_ARG;
+    if (C == 0) return 0;
+    if (!ids || !out_f16) return OVMR_E_ARG;
+    const int Lc = h->d.context_length, E = h->d.embed_dim;
+    size_t sumL = 0;
+    for (int t = 0; t < T; ++t) {
+        if (int rc = check_text_call(h, seq_lens ? seq_lens[t] : Lc, 0)) return rc;
+        sumL += seq_lens ? seq_lens[t] : Lc;
+    }
+    // chunk of classes: the tower's rows for all T templates of c classes, then the [T, c, E] scratch of raw rows behind them
+    auto need = [&](size_t c) { return text_groups_ws_bytes(h, c * sumL, c * T) + align_up(c * T * E * 2); };
+    if (need(1) > h->ws_bytes)
+        return fail(h, OVMR_E_SHAPE, "the %d prompts of one class (%zu token rows) do not fit the workspace of %zu bytes: finalize with a "
+                    "larger reserve", T, sumL, h->ws_bytes);
+    size_t lo = 1, hi = (size_t)C;                       // largest c with need(c) <= ws_bytes (need grows with c)
+    while (lo < hi) {
+        const size_t mid = (lo + hi + 1) / 2;
+        if (need(mid) <= h->ws_bytes) lo = mid; else hi = mid - 1;
+    }
+    const int n_chunks = (int)((C + lo - 1) / lo);       // balanced chunks of at most `lo` classes
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<TextGroup> gs(T);
+    for (int i = 0, c0 = 0; i < n_chunks; ++i) {
+        const int cc = C / n_chunks + (i < C % n_chunks ? 1 : 0);
+        half_t* raw = (half_t*)(h->ws + text_groups_ws_bytes(h, (size_t)cc * sumL, (size_t)cc * T));
+        for (int t = 0; t < T; ++t) {                    // ids are template-major: [T, C, context_length]
+            TextGroup& g = gs[t];
+            g.ids = ids + ((size_t)t * C + c0) * Lc; g.N = cc; g.Ls = seq_lens ? seq_lens[t] : Lc; g.normalize = 0;
+            g.out = raw + (size_t)t * cc * E;
+        }
+        CK(run_text_groups(h, gs, s));
+        CK(launch_text_ensemble(raw, T, cc, E, (half_t*)out_f16 + (size_t)c0 * E, s));
+        c0 += cc;
+    }
     return 0;
 }
 

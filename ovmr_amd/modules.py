@@ -804,6 +804,8 @@ class ZeroshotCLIP(_TwoInFlight):
     `tokenized_prompts`: LongTensor [C, 77] -- clip.tokenize of CUSTOM_TEMPLATES[dataset].format(classname) (:42-45; tokenize() above with a
     BPE tokenizer produces them from names)."""
 
+    TRAINER = "ZeroshotCLIP"
+
     def __init__(self, clip_model: CLIPModel, tokenized_prompts: torch.Tensor, n_ctx: int = 2, reserve=(256, 256, 1024)):
         self.clip_model = clip_model
         self.engine = e = clip_model.engine(n_ctx)
@@ -816,7 +818,25 @@ class ZeroshotCLIP(_TwoInFlight):
             e._reserve = tuple(reserve)
             e.finalize(*reserve)
         self.tokenized_prompts = tokenized_prompts
-        self.text_features = e.encode_text_ids(tokenized_prompts, normalize=1)      # :47-50
+        self.text_features = self._text_features(e, tokenized_prompts)
+
+    def _text_features(self, e: Engine, tokenized_prompts: torch.Tensor) -> torch.Tensor:
+        return e.encode_text_ids(tokenized_prompts, normalize=1)                    # :47-50
+
+    @classmethod
+    def from_classnames(cls, clip_model: CLIPModel, classnames: Sequence[str], dataset_name: str, tokenizer=None, **kw):
+        """build_model from class names (:42-50; ZeroshotCLIP2: :85-96): every template of `dataset_name` (ovmr_amd.templates) is
+        formatted with `c.replace("_", " ")` and tokenised with `tokenizer` (default: default_tokenizer()).  Unknown dataset names are
+        refused (KeyError listing the known ones) before anything is tokenised."""
+        from . import templates
+        temps = templates.templates_for(cls.TRAINER, dataset_name)
+        if tokenizer is None:
+            tokenizer = default_tokenizer()
+        texts = [templates.prompts(t, classnames) for t in temps]
+        if cls.TRAINER == "ZeroshotCLIP":
+            print(f"Prompts: {texts[0]}")                                        # :44
+        ids = torch.stack([tokenize(p, tokenizer, clip_model.context_length) for p in texts])   # [T, C, 77], template-major
+        return cls(clip_model, ids[0] if cls.TRAINER == "ZeroshotCLIP" else ids, **kw)
 
     def _twin_state(self):
         pl = getattr(self, "_pl_state", None)
@@ -836,3 +856,18 @@ class ZeroshotCLIP(_TwoInFlight):
         """model_inference for every image batch of the test loop (Dassl.pytorch/dassl/engine/trainer.py:461-482), in order and bit-identical
         to calling it per batch, two batches in flight on two handles / streams (as CustomCLIP.forward_batches)."""
         yield from self._run_batches(batches, overlap, stable_inputs)
+
+
+class ZeroshotCLIP2(ZeroshotCLIP):
+    """trainers/zsclip.py:63-99, prompt ensembling.  `tokenized_prompts`: LongTensor [T, C, 77], template-major -- clip.tokenize of every
+    template of ovmr_amd.templates.templates_for("ZeroshotCLIP2", dataset) formatted with every class name (from_classnames builds it).
+    The text features are the ensembled classifier of ovmr_encode_text_ensemble (all templates of a chunk of classes in ONE tower pass,
+    the reference's fp16 rounding points of :88-96); model_inference / inference_batches are ZeroshotCLIP's."""
+
+    TRAINER = "ZeroshotCLIP2"
+
+    def _text_features(self, e: Engine, tokenized_prompts: torch.Tensor) -> torch.Tensor:
+        if tokenized_prompts.dim() != 3:
+            raise ValueError(f"ZeroshotCLIP2 takes token ids [templates, classes, context_length], got {tuple(tokenized_prompts.shape)}")
+        print(f"Prompt ensembling (n={tokenized_prompts.shape[0]})")                # :85-86
+        return e.encode_text_ensemble(tokenized_prompts)

@@ -55,6 +55,7 @@ SIGNATURES = {
     "ovmr_encode_text_embedded": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p]),
     "ovmr_encode_text_ids": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_p]),
     "ovmr_encode_text_groups": (c_i, [c_p, ctypes.POINTER(TextGroup), c_i, c_p]),
+    "ovmr_encode_text_ensemble": (c_i, [c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p, c_p]),
     "ovmr_embed_tokens": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "ovmr_generate_tokens": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "ovmr_assemble_prompts": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
@@ -291,6 +292,28 @@ class Engine:
             outs.append(out)
         self._ck(self.lib.ovmr_encode_text_groups(self.h, arr, len(groups), _stream()), "ovmr_encode_text_groups")
         return outs
+
+    def encode_text_ensemble(self, ids: torch.Tensor, seq_lens=None) -> torch.Tensor:
+        """The prompt-ensembled text classifier of ZeroshotCLIP2 (ovmr_encode_text_ensemble): ids [T, C, context_length], template-major
+        -> [C, embed_dim] fp16.  seq_lens: T template lengths; None = each template's exact length (max EOT position + 1) when `ids` is a
+        host tensor, the full context otherwise (no device read-back here)."""
+        T, C = int(ids.shape[0]), int(ids.shape[1])
+        host = isinstance(ids, np.ndarray) or not ids.is_cuda
+        if host and ids.numel():
+            eot = torch.as_tensor(ids).argmax(dim=-1).amax(dim=1)          # EOT has the largest id (clip/model.py:831)
+            if seq_lens is None:
+                seq_lens = (eot + 1).tolist()
+            elif any(int(e) >= int(s) for e, s in zip(eot.tolist(), seq_lens)):
+                raise ValueError(f"seq_lens {list(seq_lens)} do not reach the EOT tokens at {eot.tolist()}")
+        sl = None
+        if seq_lens is not None:
+            if len(seq_lens) != T:
+                raise ValueError(f"{len(seq_lens)} seq_lens for {T} templates")
+            sl = (ctypes.c_int32 * T)(*[int(s) for s in seq_lens])
+        ids = self._dev(ids, torch.int64)
+        out = torch.empty((C, self.spec.embed_dim), dtype=torch.float16, device=self.device)
+        self._ck(self.lib.ovmr_encode_text_ensemble(self.h, _ptr(ids), T, C, sl, _ptr(out), _stream()), "ovmr_encode_text_ensemble")
+        return out
 
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
         ids = self._dev(ids, torch.int64)

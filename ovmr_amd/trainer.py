@@ -14,6 +14,9 @@ runs unchanged with `trainer = ovmr_amd.trainer.MM_CLS_OP(cfg, dm, clip_weights=
 `dm` is anything with the four attributes the reference's DataManager (Dassl.pytorch/dassl/data/data_manager.py:116-170)
 hands the trainer: `dataset.classnames`, `test_loader`, `val_loader` (may be None) and `eval_set_loader`
 (`RandomClassSampler` batches: S consecutive rows per class).
+
+`ZeroshotCLIP` / `ZeroshotCLIP2` (trainers/zsclip.py) are registered next to it with the same Dassl-facing methods; they need only
+`dataset.classnames` and `test_loader`.
 """
 from __future__ import annotations
 
@@ -137,6 +140,98 @@ class MM_CLS_OP:
 
 
 TRAINER_REGISTRY["MM_CLS_OP"] = MM_CLS_OP
+
+
+class ZeroshotCLIP:
+    """trainers/zsclip.py:32-60 (BASELINE configuration 1) with the Dassl-facing methods MM_CLS_OP has: build_model, parse_batch_test,
+    model_inference, load_model and test().  `dm` needs `dataset.classnames` and `test_loader` (`val_loader` optional); cfg.DATASET.NAME
+    picks the template (ovmr_amd.templates).  Nothing is trained and nothing is registered, so load_model has nothing to load."""
+
+    MODULE = modules.ZeroshotCLIP
+
+    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0"):
+        from . import templates
+        templates.check_dataset(cfg.DATASET.NAME)                           # (the reference's CUSTOM_TEMPLATES lookup, :42 / :83)
+        self.cfg, self.dm, self.device = cfg, dm, torch.device(device)
+        self._clip_weights, self._tokenizer = clip_weights, tokenizer
+        self._models: "OrderedDict[str, object]" = OrderedDict()
+        self.test_loader = dm.test_loader
+        self.val_loader = getattr(dm, "val_loader", None)
+        self.num_classes = len(dm.dataset.classnames)
+        self.epoch = 0
+        self.output_dir = cfg.OUTPUT_DIR
+        self.build_model()
+        self.evaluator = Classification(self.num_classes, list(dm.dataset.classnames), device=str(self.device))
+
+    def build_model(self):
+        cfg = self.cfg
+        classnames = self.dm.dataset.classnames
+        print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")       # :38
+        w = self._clip_weights
+        if w is None:
+            raise FileNotFoundError(f"{type(self).__name__} needs clip_weights= (an OpenAI CLIP .pt file or a state dict): "
+                                    "there is no download on this path (trainers/coop.py load_clip_to_cpu fetches it in the reference)")
+        sd = checkpoint.load_clip_state_dict(w) if isinstance(w, (str, os.PathLike)) else w
+        self.clip_model = modules.build_model(sd, device=str(self.device))
+        batch = getattr(getattr(cfg.DATALOADER, "TEST", None), "BATCH_SIZE", 256)
+        self.model = self.MODULE.from_classnames(self.clip_model, classnames, cfg.DATASET.NAME, self._tokenizer,
+                                                 reserve=(batch, 256, max(1024, len(classnames))))
+        self.text_features = self.model.text_features
+
+    def get_model_names(self, names=None):
+        return list(self._models.keys()) if names is None else list(names)
+
+    def parse_batch_test(self, batch):
+        return batch["img"].to(self.device), batch["label"].to(self.device)
+
+    def load_model(self, directory, epoch=None):
+        """Dassl's load_model (trainer.py:461-493) over the registered models: there are none."""
+        if not directory:
+            print("Note that load_model() is skipped as no pretrained model is given")
+
+    def model_inference(self, image):
+        return self.model.model_inference(image)                             # :55-60
+
+    @torch.no_grad()
+    def test(self, split=None):
+        """Dassl's SimpleTrainer.test (trainer.py:460-482): two test batches in flight (ZeroshotCLIP.inference_batches), counted by the
+        on-device evaluator."""
+        self.evaluator.reset()
+        if split is None:
+            split = getattr(getattr(self.cfg, "TEST", None), "SPLIT", "test")
+        if split == "val" and self.val_loader is not None:
+            data_loader = self.val_loader
+        else:
+            split = "test"
+            data_loader = self.test_loader
+        print(f"Evaluate on the *{split}* set")
+        labels = collections.deque()
+
+        def inputs():
+            for batch in data_loader:
+                input, label = self.parse_batch_test(batch)
+                labels.append(label)
+                yield input
+
+        for output in self.model.inference_batches(inputs()):
+            self.evaluator.process(output, labels.popleft())
+        results = self.evaluator.evaluate(self.output_dir or None)
+        return list(results.values())[0]
+
+    def forward_backward(self, batch):
+        raise NotImplementedError("the zero-shot trainers have nothing to train")
+
+    train = save_model = forward_backward
+
+
+class ZeroshotCLIP2(ZeroshotCLIP):
+    """trainers/zsclip.py:63-99: prompt ensembling over IMAGENET_TEMPLATES_SELECT (+ the dataset's template off ImageNet)."""
+
+    MODULE = modules.ZeroshotCLIP2
+
+
+TRAINER_REGISTRY["ZeroshotCLIP"] = ZeroshotCLIP
+TRAINER_REGISTRY["ZeroshotCLIP2"] = ZeroshotCLIP2
 
 
 def build_trainer(cfg, dm, **kw):
