@@ -282,7 +282,8 @@ double ovmr_flops_per_prompt(const ovmr_handle* h, int seq_len);
 
 /* Unit-test hooks: launch ONE kernel (no handle).  f32 selects the fp32 (aggregator) kernels;
  * `variant` selects the kernel implementation as ovmr_set_option does; `epi` is the epilogue id of
- * ovmr_amd/csrc/common.h.  A [M,K], W [N,K], C [M,ldc]; qkv [B*L, 3*H*64] -> out [B*L, H*64].
+ * ovmr_amd/csrc/common.h.  A [M,K], W [N,K], C [M,ldc]; qkv [B*L, 3*H*64] -> out [B*L, H*64].  The *_strided / *_q
+ * forms take the operand strides and query counts of the engine's sub-matrix launches.
  * For the LayerNorm-folding epilogues (epi 6/7) ovmr_debug_gemm reads `bias` as the folded bias fp32 [N], `pos` as the
  * column sums fp32 [N] and `res` as the row statistics fp32 [M][K/256][2]; with epi 8 (fused row argmax) C receives
  * fp32 [M][ceil(N/256)][2] = (tile maximum, bits of the lowest column holding it); with epi 3 a non-NULL `pos` receives the
@@ -300,6 +301,19 @@ int ovmr_debug_layernorm(int f32, const void* x, void* y, const float* g, const 
                          long in_stride, ovmr_stream stream);
 int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B, int L, int H, int causal,
                          ovmr_stream stream);
+/* ovmr_debug_gemm (fp16 kernels) with explicit strides: A [M, lda], W [N, ldw], res [M, ldres], C [M, ldc] -- the sub-matrix
+ * launches of the last vision block (CLS-row Q with A strided by a sequence, K/V written next to Q, out_proj reading the residual
+ * of the CLS rows from the token rows).  For epi 6/7, W [N,K] and bias fp16 [N] are the RAW weight and bias: they are folded with
+ * gamma / beta fp32 [K] in scratch allocated here, the row statistics are taken over the dense buffer A strides over
+ * (lda = row_step * K, ldw = K, K % 256 == 0) and read every row_step rows, as the CLS-row Q launch does (row_step = L).
+ * OVMR_E_ARG for EPI_PATCH / EPI_SCALE_ARGMAX; otherwise the launcher's rc. */
+int ovmr_debug_gemm_strided(int variant, const void* A, int lda, const void* W, int ldw, const void* bias, const void* res,
+                            int ldres, void* C, int ldc, int M, int N, int K, int epi, float scale, const float* gamma,
+                            const float* beta, int row_step, ovmr_stream stream);
+/* fp16 attention for the first Lq <= L queries of every sequence (the last vision block runs Lq = 1, the CLS query):
+ * out [B*Lq, H*64], row b*Lq + q.  Lq > L returns OVMR_E_SHAPE. */
+int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L, int Lq, int H, int causal,
+                           ovmr_stream stream);
 
 #ifdef __cplusplus
 }

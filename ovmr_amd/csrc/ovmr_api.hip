@@ -1073,6 +1073,40 @@ int ovmr_debug_lnfold(int variant, const void* A1, const void* W1, const void* b
     return rc;
 }
 
+// ovmr_debug_gemm (fp16) with the operand strides of the engine's sub-matrix launches (the last vision block: CLS-row Q, K/V next
+// to Q, out_proj of the CLS rows).  epi 6/7: W / bias are the RAW weight and bias, folded with gamma / beta here, and the statistics
+// are those of the dense [(M-1)*row_step+1, K] buffer A strides over (lda = row_step * K), read with ln_stride = row_step * K/256.
+int ovmr_debug_gemm_strided(int variant, const void* A, int lda, const void* W, int ldw, const void* bias, const void* res,
+                            int ldres, void* C, int ldc, int M, int N, int K, int epi, float scale, const float* gamma,
+                            const float* beta, int row_step, ovmr_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (epi == EPI_PATCH || epi == EPI_SCALE_ARGMAX || epi < 0 || epi > EPI_LN_BIAS_QGELU) return OVMR_E_ARG;
+    GemmArgs a = gemm(A, lda, W, ldw, C, ldc, M, N, K, epi, bias, res, ldres);
+    a.scale = scale;
+    if (epi != EPI_LN_BIAS && epi != EPI_LN_BIAS_QGELU) return launch_gemm_f16(a, variant, s);
+    if (K % 256 || K / 256 > 64 || row_step < 1 || (long)lda != (long)row_step * K || ldw != K || !gamma || !beta || !bias)
+        return OVMR_E_ARG;
+    if (M <= 0 || N <= 0) return 0;
+    const int slots = K / 256;
+    const long rows = (long)(M - 1) * row_step + 1;
+    float *stats = nullptr, *g = nullptr, *bf = nullptr;
+    half_t* wf = nullptr;
+    int rc = 0;
+    if (hipMalloc((void**)&stats, (size_t)rows * slots * 8) != hipSuccess || hipMalloc((void**)&g, (size_t)N * 4) != hipSuccess ||
+        hipMalloc((void**)&bf, (size_t)N * 4) != hipSuccess || hipMalloc((void**)&wf, (size_t)N * K * 2) != hipSuccess)
+        rc = OVMR_E_NOMEM;
+    if (!rc) rc = launch_fold_ln((const half_t*)W, gamma, beta, (const half_t*)bias, wf, g, bf, N, K, s);
+    if (!rc) rc = rows > 0x7fffffffL ? OVMR_E_ARG : launch_row_stats((const half_t*)A, stats, (int)rows, K, slots, s);
+    if (!rc) {
+        a = gemm_ln(gemm(A, lda, wf, K, C, ldc, M, N, K, epi), stats, slots, g, bf);
+        a.ln_stride = row_step * slots;
+        rc = launch_gemm_f16(a, variant, s);
+    }
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(stats); (void)hipFree(g); (void)hipFree(bf); (void)hipFree(wf);
+    return rc;
+}
+
 int ovmr_debug_layernorm(int f32, const void* x, void* y, const float* g, const float* b, int rows, int D,
                          long in_stride, ovmr_stream stream) {
     return launch_layernorm(x, y, g, b, rows, D, in_stride, f32, (hipStream_t)stream);
@@ -1082,6 +1116,11 @@ int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B
                          ovmr_stream stream) {
     return f32 ? launch_attention_f32((const float*)qkv, (float*)out, B, L, H, (hipStream_t)stream)
                : launch_attention_f16((const half_t*)qkv, (half_t*)out, B, L, H, causal, variant, (hipStream_t)stream);
+}
+
+int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L, int Lq, int H, int causal,
+                           ovmr_stream stream) {
+    return launch_attention_f16_q((const half_t*)qkv, (half_t*)out, B, L, Lq, H, causal, variant, (hipStream_t)stream);
 }
 
 }  // extern "C"
