@@ -402,10 +402,12 @@ class Engine:
         """1: fused_logits runs the one-launch head for B rows x C classes, 0: the GEMM path (their logits may differ by one fp16 step)."""
         return int(self.lib.ovmr_head_plan(self.h, int(B), int(C)))
 
-    def zeroshot_logits(self, feats, text_feats) -> torch.Tensor:
+    def zeroshot_logits(self, feats, text_feats, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         feats = self._dev(feats, torch.float16)
         text_feats = self._dev(text_feats, torch.float16)
-        out = torch.empty((feats.shape[0], text_feats.shape[0]), dtype=torch.float16, device=self.device)
+        if out is None:
+            out = torch.empty((feats.shape[0], text_feats.shape[0]), dtype=torch.float16, device=self.device)
+        assert out.shape == (feats.shape[0], text_feats.shape[0]) and out.dtype == torch.float16 and out.is_contiguous()
         self._ck(self.lib.ovmr_zeroshot_logits(self.h, _ptr(feats), feats.shape[0], _ptr(text_feats), text_feats.shape[0],
                                                _ptr(out), _stream()), "ovmr_zeroshot_logits")
         return out
