@@ -209,7 +209,7 @@ int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq,
         const int rc = launch_attention_f16_short(qkv, out, 1, &B, &L, &row0, H, causal, s);
         if (rc != -100) return rc;
     }
-    if (variant == 4) variant = 3;
+    if (variant == 4) variant = 3;    // 4: the number of a retired kernel, an alias of 3 so that the option value keeps its meaning
     if (variant == 3) {               // single-pass kernel for the ViT-B/16 image shape; long sequences (ViT-L: L = 257 / 577) as variant 5
         int rc = launch_attention_f16_v3(qkv, out, B, L, Lq, H, causal, s);
         if (rc != -100) return rc;

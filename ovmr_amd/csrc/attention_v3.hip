@@ -14,10 +14,11 @@
 //     P^T packed to fp16 straight into the B operands of the 7 PV steps, V^T through ds_read_b64_tr_b16, the row sum from the
 //     matrix pipe, output rows exchanged between lanes so that a store instruction writes 64 contiguous bytes per row;
 //   * 14 waves per CU at <= 128 VGPRs (3.5 per SIMD).
-// What bounds it (r02m, timing-only ablations of variant 4, same tile body; tools/attn_bench.py): the memory system.  At
+// What bounds it (r02m, timing-only ablations of the retired variant 4 -- the same tile body with free-running waves instead of the
+// workgroup barrier, last present at a19fe7d): the memory system.  At
 // 512 x 12 heads x 197 the kernel moves 620 MB (Q, K, V once in, O once out) in 135-141 us = 4.4-4.6 TB/s; without the output
 // stores it takes 108-111 us, streaming K / V alone 55 us (5.6 TB/s), and the tile body hardly matters (no exponentials -4 us,
-// no LDS reads -18, one PV MFMA per step -11).  Pinned instruction order, free-running waves (variant 4), a third buffer and
+// no LDS reads -18, one PV MFMA per step -11).  Pinned instruction order, free-running waves, a third buffer and
 // head-major strides all land within +-3 % of this kernel.
 // Other shapes (text, the CLS-only last block, ViT-L) stay on variants 0 / 1.
 #include "attn_single_pass.h"

@@ -138,40 +138,36 @@ int launch_gemm_f16_small(const GemmArgs& a, hipStream_t s);            // gemm_
 // but the two within 5 %).
 bool gemm_f16_is_small(int M, int N) { return (long)((M + 63) / 64) * ((N + 63) / 64) <= 256; }
 
-// variant 0: the 128x128 register-staged kernel above for every shape; 6: 256-row tiles with the double-buffered K loop;
-// 8 (default): 6 with the ping-pong K loop, and the 64x64 split-K kernel (gemm_f16_small.hip) for latency-bound shapes
-// (gemm_f16_is_small); 7: 8 without that kernel (A/B); 9: the 64x64 split-K kernel wherever it takes the shape (tests).  6 / 8 / 9 fall back to the 128x128
-// kernel for shapes they do not take (M < 256, N < 128, K not a multiple of 128 ...).
+// Which kernel runs a GEMM, by variant (+ 100: the one-rounding QuickGELU, common.h quick_gelu_f32x2):
+//   0            the 128 x 128 register-staged kernel above for every shape;
+//   6            256-row tiles (gemm_f16_v5.hip) with the double-buffered K loop;
+//   8 (default)  256-row tiles with the ping-pong K loop, and the 64 x 64 split-K kernel (gemm_f16_small.hip) for latency-bound
+//                shapes (gemm_f16_is_small);
+//   7            8 without the split-K kernel; 9: the split-K kernel wherever it takes the shape (both: tests, and the engine's
+//                K/V + Q launches, which pin the kernel the all-token launch would take).
+// A kernel that does not take a shape (M < 256, N < 128, K not a multiple of 128 ...) hands on: split-K -> 256-row -> 128 x 128.
+// What only the 256-row kernel does -- patch rows gathered from the image, the fused row argmax, the LayerNorm fold and its
+// statistics -- runs there under every variant (0 / 7 / 9: with the loop of 8); -4: shape not supported.
 int launch_gemm_f16(const GemmArgs& a_in, int variant, hipStream_t s) {
     GemmArgs a = a_in;
-    if (variant >= 100) {                   // variant = kernel + 100 * QuickGELU form (common.h quick_gelu_fast_h4)
+    if (variant >= 100) {
         a.gelu_mode = variant / 100;
         variant %= 100;
     }
     if (a.M <= 0 || a.N <= 0) return 0;
     if (a.K <= 0 || (a.K % BK) != 0 || (a.lda & 7) || (a.ldw & 7)) return -2;  // caller pads K to 64
-    const int v5 = (variant == 0 || variant == 9 || variant == 7) ? 8 : variant;
-    if (a.im2col_R) {                                                           // only the v5 kernel gathers patch rows from the image; -4: shape not supported
-        const int rc = launch_gemm_f16_v5(a, v5, s);
+    const int loop = (variant == 0 || variant == 7 || variant == 9) ? 8 : variant;   // K loop of the 256-row kernel
+    if (a.im2col_R || a.epi == EPI_SCALE_ARGMAX || a.epi == EPI_LN_BIAS || a.epi == EPI_LN_BIAS_QGELU || a.stats_out) {
+        const int rc = launch_gemm_f16_v5(a, loop, s);
         return rc == -100 ? -4 : rc;
     }
-    if (a.epi == EPI_SCALE_ARGMAX) {                                            // only the v5 kernel; -4: shape not supported
-        const int rc = launch_gemm_f16_v5(a, v5, s);
-        return rc == -100 ? -4 : rc;
-    }
-    if (a.epi == EPI_LN_BIAS || a.epi == EPI_LN_BIAS_QGELU || a.stats_out) {   // only the v5 kernel folds LayerNorm
-        const int rc = launch_gemm_f16_v5(a, v5, s);
-        return rc == -100 ? -4 : rc;
-    }
-    if (variant == 7) variant = 8;          // A/B: variant 8 without the split-K kernel (the caller's LayerNorm-fold rule keys on 8 as well)
-    else if (variant == 9 || (variant == 8 && gemm_f16_is_small(a.M, a.N))) {
+    if (variant == 9 || (variant == 8 && gemm_f16_is_small(a.M, a.N))) {
         const int rc = launch_gemm_f16_small(a, s);
         if (rc != -100) return rc;
-        if (variant == 9) variant = 8;
     }
     if (variant >= 1) {
-        const int rc = launch_gemm_f16_v5(a, variant, s);
-        if (rc != -100) return rc;   // -100: shape not supported -> the 128x128 kernel
+        const int rc = launch_gemm_f16_v5(a, loop, s);
+        if (rc != -100) return rc;
     }
     switch (a.epi) {
         case EPI_NONE: return launch_t128<EPI_NONE>(a, s);

@@ -109,11 +109,16 @@ bool stored_as_f32(const std::string& name) {
     return false;   // conv1, proj, text_projection, attn.*, mlp.*
 }
 
-void* dev_alloc(ovmr_handle* h, size_t bytes) {
+// Device allocation registered in `list`: h->owned (until ovmr_destroy) or h->derived (until the next ovmr_finalize)
+void* dev_alloc(std::vector<void*>& list, size_t bytes) {
     void* p = nullptr;
     if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    h->owned.push_back(p);
+    list.push_back(p);
     return p;
+}
+
+int need_finalized(ovmr_handle* h) {
+    return h->finalized ? 0 : fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
 }
 
 const Buf* find(ovmr_handle* h, const std::string& name, size_t elems) {
@@ -158,32 +163,61 @@ GemmArgs gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, 
 
 inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
+// The workspace is one arena that every pass carves anew (calls on one handle are stream ordered).  Each pass states its buffers ONCE,
+// as a Carver whose constructor takes them in order: on a null base that only measures (ovmr_finalize sizes the arena with bytes()),
+// on h->ws it hands out the pointers the entry point uses -- so a buffer cannot be sized without being carved, or the reverse.
 struct Carver {
     char* base; size_t off = 0;
     explicit Carver(char* b) : base(b) {}
-    template <typename T> T* take(size_t n) { T* p = (T*)(base + off); off = align_up(off + n * sizeof(T)); return p; }
+    template <typename T> T* take(size_t n) { T* p = base ? (T*)(base + off) : nullptr; off = align_up(off + n * sizeof(T)); return p; }
+    size_t bytes() const { return off; }
 };
 
-size_t image_ws_bytes(const ovmr_handle* h, long B) {
-    const long M = B * h->L, W = h->d.vision_width;
-    size_t s = 0;
-    s += align_up((size_t)B * h->G * h->G * h->Kpad * 2);
-    s += align_up((size_t)M * W * 2) * 2;          // x, y
-    s += align_up((size_t)M * 3 * W * 2);          // qkv
-    s += align_up((size_t)M * 4 * W * 2);          // mlp hidden
-    s += align_up((size_t)B * W * 2);              // CLS rows
-    s += align_up((size_t)M * ((W + 255) / 256) * 8);   // LayerNorm partial statistics
-    return s;
-}
-size_t text_ws_bytes(const ovmr_handle* h, long N) {
-    const long M = N * h->d.context_length, W = h->d.transformer_width;
-    return align_up((size_t)M * W * 2) * 2 + align_up((size_t)M * 3 * W * 2) + align_up((size_t)M * 4 * W * 2) +
-           align_up((size_t)N * W * 2) + align_up((size_t)N * 4) + align_up((size_t)M * ((W + 255) / 256) * 8);
-}
-size_t agg_ws_bytes(const ovmr_handle* h, long rows) {
-    const long D = h->d.embed_dim;
-    return align_up((size_t)rows * D * 4) * 2 + align_up((size_t)rows * 3 * D * 4) + align_up((size_t)rows * 4 * D * 4);
-}
+// One pass of an fp16 tower over M token rows of N sequences.  Image tower (image_ws): the patch rows `col` come first and `rows` are
+// the CLS rows; text tower (text_ws): `rows` are the read-out rows and `index` their positions.  A buffer of 0 elements takes no room.
+struct TowerWs : Carver {
+    half_t *col, *x, *y, *qkv, *hid, *rows;
+    int* index;
+    float* stats;
+    TowerWs(char* base, size_t W, size_t M, size_t N, size_t col_elems, size_t n_index) : Carver(base) {
+        col = take<half_t>(col_elems);
+        x = take<half_t>(M * W);
+        y = take<half_t>(M * W);
+        qkv = take<half_t>(M * 3 * W);
+        hid = take<half_t>(M * 4 * W);                     // mlp hidden
+        rows = take<half_t>(N * W);
+        index = take<int>(n_index);
+        stats = take<float>(M * ((W + 255) / 256) * 2);    // LayerNorm partial statistics
+    }
+};
+TowerWs image_ws(const ovmr_handle* h, char* base, size_t B) { return TowerWs(base, h->d.vision_width, B * h->L, B, B * h->G * h->G * h->Kpad, 0); }
+TowerWs text_ws(const ovmr_handle* h, char* base, size_t M, size_t N) { return TowerWs(base, h->d.transformer_width, M, N, 0, N); }
+
+struct EnsembleWs : TowerWs {   // ovmr_encode_text_ensemble: a text pass, then the [T, c, E] raw rows of its N = T * c prompts behind it
+    half_t* raw;
+    EnsembleWs(const ovmr_handle* h, char* base, size_t M, size_t N) : TowerWs(text_ws(h, base, M, N)) { raw = take<half_t>(N * h->d.embed_dim); }
+};
+
+struct AggWs : Carver {         // the fp32 aggregator over `rows` token rows
+    float *x, *y, *qkv, *hid;
+    AggWs(const ovmr_handle* h, char* base, size_t rows) : Carver(base) {
+        const size_t D = h->d.embed_dim;
+        x = take<float>(rows * D);
+        y = take<float>(rows * D);
+        qkv = take<float>(rows * 3 * D);
+        hid = take<float>(rows * 4 * D);
+    }
+};
+
+// The classifier head's GEMM path: `n_logits` buffers of logit_elems_cap fp16 logits, then 65536 rows of scaled features.
+// ovmr_fused_logits takes three (ovmr_finalize sizes for that), ovmr_xval_counts one, ovmr_zeroshot_logits none.
+struct HeadWs : Carver {
+    half_t *l[3] = {nullptr, nullptr, nullptr}, *sf;
+    HeadWs(const ovmr_handle* h, char* base, int n_logits) : Carver(base) {
+        for (int m = 0; m < n_logits; ++m) l[m] = take<half_t>((size_t)h->logit_elems_cap);
+        sf = take<half_t>((size_t)65536 * h->d.embed_dim);
+    }
+};
 
 // LayerNorm folding applies when the v5 GEMM takes the shape (it then also emits the statistics): see common.h.
 // Not for latency-bound passes (gemm_f16_is_small: the N = W launches -- out_proj, c_proj -- then take the 64 x 64 split-K kernel,
@@ -201,26 +235,77 @@ GemmArgs gemm_stats(GemmArgs a, float* stats) {
     return a;
 }
 
+// Scratch of the two LayerNorm-fold hooks, allocated per call: the statistics of `rows` rows and the folded form of a raw [N, K]
+// weight (rc: allocation or fold failure).  Leaving the hook waits for the stream and frees it.
+struct LnFoldScratch {
+    float *stats = nullptr, *g = nullptr, *bf = nullptr;
+    half_t* wf = nullptr;
+    hipStream_t s;
+    int rc = 0;
+    LnFoldScratch(size_t rows, const void* W, const float* gamma, const float* beta, const void* bias, int N, int K, hipStream_t s_) : s(s_) {
+        if (hipMalloc((void**)&stats, rows * (K / 256) * 8) != hipSuccess || hipMalloc((void**)&g, (size_t)N * 4) != hipSuccess ||
+            hipMalloc((void**)&bf, (size_t)N * 4) != hipSuccess || hipMalloc((void**)&wf, (size_t)N * K * 2) != hipSuccess)
+            rc = OVMR_E_NOMEM;
+        if (!rc) rc = launch_fold_ln((const half_t*)W, gamma, beta, (const half_t*)bias, wf, g, bf, N, K, s);
+    }
+    ~LnFoldScratch() {
+        (void)hipStreamSynchronize(s);
+        (void)hipFree(stats); (void)hipFree(g); (void)hipFree(bf); (void)hipFree(wf);
+    }
+};
+
+// A LayerNorm-fed linear layer of a block: in_proj behind ln_1, or c_fc (QuickGELU epilogue) behind ln_2; wf / g / bf = its folded form
+struct LnLinear { const float *ln_g, *ln_b; const half_t *w, *b, *wf; const float *g, *bf; bool gelu; };
+LnLinear in_proj(const Block& k) { return {k.ln1_g, k.ln1_b, (const half_t*)k.in_w, (const half_t*)k.in_b, k.in_wf, k.in_g, k.in_bf, false}; }
+LnLinear c_fc(const Block& k) { return {k.ln2_g, k.ln2_b, (const half_t*)k.fc_w, (const half_t*)k.fc_b, k.fc_wf, k.fc_g, k.fc_bf, true}; }
+
+// One GEMM of such a layer: weight rows [r0, r0 + n) applied to M input rows, every `step`-th row of the buffer, into C (row stride ldc)
+struct LnPart { int r0, n, M, step; half_t* C; int ldc; };
+
+// LayerNorm of the `rows` rows of x, then the GEMMs `parts`.  stats != nullptr (the partial row statistics of x): the LayerNorm is folded
+// into the GEMMs (folded weights, EPI_LN_BIAS[_QGELU]); nullptr: launch_layernorm x -> y once, plain GEMMs on y.
+int ln_linear(ovmr_handle* h, const LnLinear& l, const half_t* x, half_t* y, int rows, int W, const float* stats, int variant,
+              std::initializer_list<LnPart> parts, hipStream_t s) {
+    if (!stats) CK(launch_layernorm(x, y, l.ln_g, l.ln_b, rows, W, W, 0, s));
+    if (l.gelu && !h->gelu_exact) variant += 100;            // the one-rounding QuickGELU (common.h quick_gelu_f32x2)
+    const int slots = W / 256, epi = l.gelu ? (stats ? EPI_LN_BIAS_QGELU : EPI_BIAS_QGELU) : (stats ? EPI_LN_BIAS : EPI_BIAS);
+    for (const LnPart& p : parts) {
+        GemmArgs a = gemm(stats ? x : y, p.step * W, (stats ? l.wf : l.w) + (size_t)p.r0 * W, W, p.C, p.ldc, p.M, p.n, W, epi, stats ? nullptr : l.b + p.r0);
+        if (stats) { a = gemm_ln(a, stats, slots, l.g + p.r0, l.bf + p.r0); a.ln_stride = p.step * slots; }
+        CK(launch_gemm_f16(a, variant, s));
+    }
+    return 0;
+}
+
 // One pre-LN residual attention block (clip/model.py:191-194) on fp16 activations.
 // stats != nullptr: ln_1 / ln_2 are folded into in_proj / c_fc.  On entry `stats` holds the partial row statistics of x
 // (launch_row_stats, or the previous block's c_proj epilogue); on exit those of the new x.
 // `groups` (text tower, ovmr_encode_text_groups): the token rows are several groups of sequences with their own length each --
 // the GEMMs run over all rows at once, attention once per group; nullptr: nseq sequences of L tokens.
+// `cls_rows` (last vision block): only the CLS row reaches ln_post (clip/model.py:423), so after the K/V projection of all tokens,
+// attention / out_proj / MLP run for the CLS query row only and the new CLS rows land in cls_rows [nseq, W] -- identical result,
+// ~6 % fewer FLOPs; x keeps the block's input.
 struct SeqGroup { int nseq, L; long row0; };
 
 int run_block_f16(ovmr_handle* h, const Block& k, half_t* x, half_t* y, half_t* qkv, half_t* hid,
                   int nseq, int L, int W, int causal, hipStream_t s, float* stats = nullptr,
-                  const std::vector<SeqGroup>* groups = nullptr) {
+                  const std::vector<SeqGroup>* groups = nullptr, half_t* cls_rows = nullptr) {
     int M = nseq * L;
     if (groups) { M = 0; for (auto& g : *groups) M += g.nseq * g.L; }
-    const int H = W / 64, slots = W / 256;
-    if (stats) {
-        CK(launch_gemm_f16(gemm_ln(gemm(x, W, k.in_wf, W, qkv, 3 * W, M, 3 * W, W, EPI_LN_BIAS), stats, slots, k.in_g, k.in_bf), h->gemm_variant, s));
-    } else {
-        CK(launch_layernorm(x, y, k.ln1_g, k.ln1_b, M, W, W, 0, s));
-        CK(launch_gemm_f16(gemm(y, W, k.in_w, W, qkv, 3 * W, M, 3 * W, W, EPI_BIAS, k.in_b), h->gemm_variant, s));
-    }
-    if (groups) {
+    const int H = W / 64;
+    if (cls_rows && nseq >= 256 && h->last_q_cls) {
+        // ... and of the in-projection itself only K and V are needed for every token: with at least 256 images (a full row tile of
+        // CLS rows) the Q third runs as its own launch over the CLS rows (A and C strided by a sequence; bit-identical values),
+        // a third of this block's largest GEMM less.  Both launches take the kernel the all-token launch of last_q_cls = 0 would
+        // take -- the split-K kernel, 9, if [M, 3W] is a latency-bound shape, else the tile kernels, 7 -- so that the K summation
+        // order, and with it every bit, is the same either way (folded launches run the 256-row kernel under either number).
+        const int v = h->gemm_variant != 8 ? h->gemm_variant : (gemm_f16_is_small(M, 3 * W) ? 9 : 7);
+        CK(ln_linear(h, in_proj(k), x, y, M, W, stats, v, {{W, 2 * W, M, 1, qkv + W, 3 * W}, {0, W, nseq, L, qkv, L * 3 * W}}, s));
+    } else
+        CK(ln_linear(h, in_proj(k), x, y, M, W, stats, h->gemm_variant, {{0, 3 * W, M, 1, qkv, 3 * W}}, s));
+    if (cls_rows)
+        CK(launch_attention_f16_q(qkv, y, nseq, L, 1, H, causal, h->attn_variant, s));
+    else if (groups) {
         // short groups (every prompt family of a classifier head: <= ~20 tokens) share ONE launch; longer ones run group by group
         int rc = -100;
         if (h->attn_variant >= 1 && groups->size() <= 4) {
@@ -235,14 +320,13 @@ int run_block_f16(ovmr_handle* h, const Block& k, half_t* x, half_t* y, half_t* 
                 CK(launch_attention_f16(qkv + g.row0 * 3 * W, y + g.row0 * W, g.nseq, g.L, H, causal, h->attn_variant, s));
     } else
         CK(launch_attention_f16(qkv, y, nseq, L, H, causal, h->attn_variant, s));
-    CK(launch_gemm_f16(gemm_stats(gemm(y, W, k.out_w, W, x, W, M, W, W, EPI_BIAS_RES, k.out_b, x, W), stats), h->gemm_variant, s));
-    if (stats) {
-        CK(launch_gemm_f16(gemm_ln(gemm(x, W, k.fc_wf, W, hid, 4 * W, M, 4 * W, W, EPI_LN_BIAS_QGELU), stats, slots, k.fc_g, k.fc_bf), h->gemm_variant + (h->gelu_exact ? 0 : 100), s));
-    } else {
-        CK(launch_layernorm(x, y, k.ln2_g, k.ln2_b, M, W, W, 0, s));
-        CK(launch_gemm_f16(gemm(y, W, k.fc_w, W, hid, 4 * W, M, 4 * W, W, EPI_BIAS_QGELU, k.fc_b), h->gemm_variant + (h->gelu_exact ? 0 : 100), s));
-    }
-    CK(launch_gemm_f16(gemm_stats(gemm(hid, 4 * W, k.pj_w, 4 * W, x, W, M, W, 4 * W, EPI_BIAS_RES, k.pj_b, x, W), stats), h->gemm_variant, s));
+    // the rest of the block on xo: x itself, or (cls_rows) the CLS rows alone, their residual read from the token rows and no statistics kept
+    half_t* xo = cls_rows ? cls_rows : x;
+    const int Mo = cls_rows ? nseq : M;
+    float* so = cls_rows ? nullptr : stats;
+    CK(launch_gemm_f16(gemm_stats(gemm(y, W, k.out_w, W, xo, W, Mo, W, W, EPI_BIAS_RES, k.out_b, x, cls_rows ? L * W : W), so), h->gemm_variant, s));
+    CK(ln_linear(h, c_fc(k), xo, y, Mo, W, so, h->gemm_variant, {{0, 4 * W, Mo, 1, hid, 4 * W}}, s));
+    CK(launch_gemm_f16(gemm_stats(gemm(hid, 4 * W, k.pj_w, 4 * W, xo, W, Mo, W, 4 * W, EPI_BIAS_RES, k.pj_b, xo, W), so), h->gemm_variant, s));
     return 0;
 }
 
@@ -274,12 +358,6 @@ struct TextGroup {
     half_t* out = nullptr;             // [N, embed_dim]
 };
 
-size_t text_groups_ws_bytes(const ovmr_handle* h, size_t M, size_t N) {
-    const size_t W = h->d.transformer_width;
-    return align_up(M * W * 2) * 2 + align_up(M * 3 * W * 2) + align_up(M * 4 * W * 2) + align_up(N * W * 2) + align_up(N * 4) +
-           align_up(M * ((W + 255) / 256) * 8);
-}
-
 // Text tower (clip/model.py:824-831) over all groups in ONE pass: embedding per group, the blocks' GEMMs over all token rows,
 // causal attention with each group's own length (truncation to the last needed row is exact under the causal mask; one launch for
 // all groups of at most 32 tokens, attention_short.hip, else group by group),
@@ -290,35 +368,28 @@ int run_text_groups(ovmr_handle* h, const std::vector<TextGroup>& gs, hipStream_
     size_t M = 0, N = 0;
     std::vector<SeqGroup> seq;
     for (auto& g : gs) { seq.push_back({g.N, g.Ls, (long)M}); M += (size_t)g.N * g.Ls; N += g.N; }
-    Carver c(h->ws);
-    half_t* x = c.take<half_t>(M * W);
-    half_t* y = c.take<half_t>(M * W);
-    half_t* qkv = c.take<half_t>(M * 3 * W);
-    half_t* hid = c.take<half_t>(M * 4 * W);
-    half_t* rows = c.take<half_t>(N * W);
-    int* index = c.take<int>(N);
-    float* stats_buf = c.take<float>(M * ((W + 255) / 256) * 2);
+    const TowerWs ws = text_ws(h, h->ws, M, N);
     size_t n0 = 0;
     for (size_t i = 0; i < gs.size(); ++i) {
         const TextGroup& g = gs[i];
-        half_t* xg = x + seq[i].row0 * W;
-        if (g.ids) CK(launch_text_embed_ids(g.ids, Lc, h->tok_emb, h->pos16_txt, xg, index + n0, g.N, Lc, g.Ls, W, s));
+        half_t* xg = ws.x + seq[i].row0 * W;
+        if (g.ids) CK(launch_text_embed_ids(g.ids, Lc, h->tok_emb, h->pos16_txt, xg, ws.index + n0, g.N, Lc, g.Ls, W, s));
         else CK(launch_text_add_pos(g.prompts, Lc, h->pos16_txt, xg, g.N, g.Ls, W, s));
         n0 += g.N;
     }
-    float* stats = !h->txt.empty() && can_fold_ln(h, h->txt[0], (int)M, W) ? stats_buf : nullptr;
-    if (stats) CK(launch_row_stats(x, stats, (int)M, W, W / 256, s));
-    for (auto& k : h->txt) CK(run_block_f16(h, k, x, y, qkv, hid, 0, 0, W, 1, s, stats, &seq));
+    float* stats = !h->txt.empty() && can_fold_ln(h, h->txt[0], (int)M, W) ? ws.stats : nullptr;
+    if (stats) CK(launch_row_stats(ws.x, stats, (int)M, W, W / 256, s));
+    for (auto& k : h->txt) CK(run_block_f16(h, k, ws.x, ws.y, ws.qkv, ws.hid, 0, 0, W, 1, s, stats, &seq));
     n0 = 0;
     for (size_t i = 0; i < gs.size(); ++i) {
         const TextGroup& g = gs[i];
-        CK(launch_gather_rows_f16(x + seq[i].row0 * W, g.ids ? index + n0 : g.index, rows + n0 * W, g.N, g.Ls, W, s));
+        CK(launch_gather_rows_f16(ws.x + seq[i].row0 * W, g.ids ? ws.index + n0 : g.index, ws.rows + n0 * W, g.N, g.Ls, W, s));
         n0 += g.N;
     }
-    CK(launch_layernorm(rows, rows, h->ln_final_g, h->ln_final_b, (int)N, W, W, 0, s));
+    CK(launch_layernorm(ws.rows, ws.rows, h->ln_final_g, h->ln_final_b, (int)N, W, W, 0, s));
     n0 = 0;
     for (auto& g : gs) {
-        CK(launch_gemm_f16(gemm(rows + n0 * W, W, h->textproj_t, W, g.out, E, g.N, E, W, EPI_NONE), h->gemm_variant, s));
+        CK(launch_gemm_f16(gemm(ws.rows + n0 * W, W, h->textproj_t, W, g.out, E, g.N, E, W, EPI_NONE), h->gemm_variant, s));
         CK(normalize_rows(h, g.out, g.N, E, g.normalize, s));
         n0 += g.N;
     }
@@ -349,7 +420,7 @@ bool head_takes_one_launch(const ovmr_handle* h, int B, int C) {
 
 int check_text_call(ovmr_handle* h, int seq_len, int normalize) {
     if (normalize < 0 || normalize > 2) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     if (seq_len < 1 || seq_len > h->d.context_length) return fail(h, OVMR_E_ARG, "seq_len %d outside [1,%d]", seq_len, h->d.context_length);
     return 0;
 }
@@ -414,6 +485,11 @@ static int pick_encode_chunk(int max_images, int L, int W, int n_cu) {
     return best;
 }
 
+static void set_enc_chunk(ovmr_handle* h) {               // needs max_images and n_cu: ovmr_finalize, and the option once finalized
+    h->enc_chunk = h->enc_chunk_forced > 0 ? std::min(h->enc_chunk_forced, h->max_images)
+                                           : pick_encode_chunk(h->max_images, h->L, (int)h->d.vision_width, h->n_cu);
+}
+
 // Launch sequences of a batch of B images: one if it fits the reserve; else chunks of enc_chunk images, a remainder of at most
 // enc_fold images (less than one round of tiles on the narrowest grid: as its own sequence it would pay a whole round on every launch
 // PLUS ~70 launches of latency, 2.1 ms for 25 ViT-B/16 images where the extra round inside the previous sequence costs 1.8) folded
@@ -439,9 +515,7 @@ int ovmr_set_option(ovmr_handle* h, const char* key, int value) {
     else if (!strcmp(key, "last_q_cls")) h->last_q_cls = value != 0;
     else if (!strcmp(key, "enc_chunk")) {
         h->enc_chunk_forced = value > 0 ? value : 0;
-        if (h->finalized)
-            h->enc_chunk = h->enc_chunk_forced > 0 ? std::min(h->enc_chunk_forced, h->max_images)
-                                                   : pick_encode_chunk(h->max_images, h->L, (int)h->d.vision_width, h->n_cu);
+        if (h->finalized) set_enc_chunk(h);
     }
     else if (!strcmp(key, "ln_fold")) h->ln_fold = value;
     else if (!strcmp(key, "xval_fused")) h->xval_fused = value;
@@ -508,7 +582,7 @@ int ovmr_set_weight(ovmr_handle* h, const char* name_c, const void* data, int dt
     Buf& b = h->w[name];
     b.f32 = stored_as_f32(name) ? 1 : 0;
     if (!b.p || b.elems != elems) {
-        b.p = dev_alloc(h, elems * (b.f32 ? 4 : 2));
+        b.p = dev_alloc(h->owned, elems * (b.f32 ? 4 : 2));
         if (!b.p) return fail(h, OVMR_E_NOMEM, "hipMalloc failed for '%s'", name_c);
     }
     b.elems = elems;
@@ -543,17 +617,11 @@ int ovmr_finalize(ovmr_handle* h, int max_images, int max_prompts, int max_class
     BINDF(cls_token, "prompt_learner.cls_token", (size_t)d.n_ctx * E)
 #undef BINDF
 
-    // derived layouts
     // derived layouts of a previous finalize are dropped first (the stream is idle: every finalize ends with a sync)
     HIP_CHECK_RET(hipStreamSynchronize(s));
     for (void* p : h->derived) (void)hipFree(p);
     h->derived.clear();
-    auto dalloc = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-        h->derived.push_back(p);
-        return p;
-    };
+    auto dalloc = [&](size_t bytes) { return dev_alloc(h->derived, bytes); };
     h->conv_w = (half_t*)dalloc(W * h->Kpad * 2);
     h->pos16_vis = (half_t*)dalloc((size_t)h->L * W * 2);
     h->cls_pos16 = (half_t*)dalloc(W * 2);
@@ -585,13 +653,13 @@ int ovmr_finalize(ovmr_handle* h, int max_images, int max_prompts, int max_class
         }
     }
 
-    // workspace: one arena, re-carved by each entry point (calls on one handle are stream ordered)
+    // workspace: one arena for the largest of the four passes (image_ws, text_ws, AggWs, HeadWs)
     h->max_images = max_images; h->max_prompts = max_prompts; h->max_classes = max_classes;
     {
         int dev = 0;
         HIP_CHECK_RET(hipGetDevice(&dev));
         HIP_CHECK_RET(hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        h->enc_chunk = h->enc_chunk_forced > 0 ? std::min(h->enc_chunk_forced, max_images) : pick_encode_chunk(max_images, h->L, (int)d.vision_width, h->n_cu);
+        set_enc_chunk(h);
     }
     {
         // fold slack: one round of the narrowest grid (N = W: W/256 column tiles of 256 rows), for reserves of two rounds or more
@@ -602,10 +670,8 @@ int ovmr_finalize(ovmr_handle* h, int max_images, int max_prompts, int max_class
     }
     h->agg_rows_cap = (long)max_classes * (d.n_ctx + 32);
     h->logit_elems_cap = 32L << 20;
-    size_t need = image_ws_bytes(h, h->img_cap);
-    need = std::max(need, text_ws_bytes(h, max_prompts));
-    need = std::max(need, agg_ws_bytes(h, h->agg_rows_cap));
-    need = std::max(need, align_up((size_t)h->logit_elems_cap * 2) * 3 + align_up((size_t)65536 * E * 2));
+    const size_t need = std::max({image_ws(h, nullptr, h->img_cap).bytes(), text_ws(h, nullptr, (size_t)max_prompts * d.context_length, max_prompts).bytes(),
+                                  AggWs(h, nullptr, h->agg_rows_cap).bytes(), HeadWs(h, nullptr, 3).bytes()});
     if (need > h->ws_bytes) {
         if (h->ws) (void)hipFree(h->ws);
         h->ws = nullptr;
@@ -621,7 +687,7 @@ int ovmr_encode_image(ovmr_handle* h, const void* image, int image_dtype, int B,
                       ovmr_stream stream) {
     if (h && B == 0) return 0;   // empty batch: torch hands out a null data_ptr
     if (!h || !image || !out_f16 || B < 0 || (image_dtype != OVMR_F16 && image_dtype != OVMR_F32)) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const ovmr_model_desc& d = h->d;
     const int W = d.vision_width, R = d.image_resolution, L = h->L, G2 = h->G * h->G, E = d.embed_dim;
@@ -631,14 +697,8 @@ int ovmr_encode_image(ovmr_handle* h, const void* image, int image_dtype, int B,
     int b0 = 0;
     for (const int Bc : encode_plan(h, B)) {
         const int M = Bc * L;
-        Carver c(h->ws);
-        half_t* col = c.take<half_t>((size_t)Bc * G2 * h->Kpad);
-        half_t* x = c.take<half_t>((size_t)M * W);
-        half_t* y = c.take<half_t>((size_t)M * W);
-        half_t* qkv = c.take<half_t>((size_t)M * 3 * W);
-        half_t* hid = c.take<half_t>((size_t)M * 4 * W);
-        half_t* rows = c.take<half_t>((size_t)Bc * W);
-        float* stats_buf = c.take<float>((size_t)M * ((W + 255) / 256) * 2);
+        const TowerWs ws = image_ws(h, h->ws, Bc);
+        half_t *col = ws.col, *x = ws.x, *rows = ws.rows;
         half_t* out = (half_t*)out_f16 + (size_t)b0 * E;
         // K1/K2: conv1 as GEMM over patches, positional add in the epilogue, CLS row, ln_pre
         // fp16 images with 16 x 16 patches: the GEMM's K loop gathers the patch rows from the image itself (gemm_f16_v5.hip, a.im2col_R);
@@ -655,47 +715,10 @@ int ovmr_encode_image(ovmr_handle* h, const void* image, int image_dtype, int B,
         CK(launch_gemm_f16(pe, h->gemm_variant, s));
         CK(launch_fill_cls(x, h->cls_pos16, Bc, L, W, s));
         CK(launch_layernorm(x, x, h->ln_pre_g, h->ln_pre_b, M, W, W, 0, s));
-        float* stats = can_fold_ln(h, h->vis[0], M, W) ? stats_buf : nullptr;
+        float* stats = can_fold_ln(h, h->vis[0], M, W) ? ws.stats : nullptr;
         if (stats) CK(launch_row_stats(x, stats, M, W, W / 256, s));
-        for (size_t li = 0; li + 1 < h->vis.size(); ++li) CK(run_block_f16(h, h->vis[li], x, y, qkv, hid, Bc, L, W, 0, s, stats));
-        // Last block: only the CLS row reaches ln_post (clip/model.py:423), so after the K/V projection of all
-        // tokens, attention / out-proj / MLP run for the CLS query row only -- identical result, ~6 % fewer FLOPs.
-        {
-            const Block& k = h->vis.back();
-            const int H = W / 64;
-            half_t* hid_c = hid;                       // [Bc, 4W]
-            half_t* yc = y;                            // [Bc, W]
-            // ... and of the in-projection itself only K and V are needed for every token: with at least 256 images (a full row tile of
-            // CLS rows) the Q third runs as its own launch over the CLS rows (A and C strided by a sequence; bit-identical values),
-            // a third of this block's largest GEMM less
-            const bool q_cls_only = Bc >= 256 && h->last_q_cls;
-            const size_t WW = (size_t)W * W;
-            if (stats) {
-                if (q_cls_only) {
-                    CK(launch_gemm_f16(gemm_ln(gemm(x, W, k.in_wf + WW, W, qkv + W, 3 * W, M, 2 * W, W, EPI_LN_BIAS), stats, W / 256, k.in_g + W, k.in_bf + W), h->gemm_variant, s));
-                    GemmArgs q = gemm_ln(gemm(x, L * W, k.in_wf, W, qkv, L * 3 * W, Bc, W, W, EPI_LN_BIAS), stats, W / 256, k.in_g, k.in_bf);
-                    q.ln_stride = L * (W / 256);
-                    CK(launch_gemm_f16(q, h->gemm_variant, s));
-                } else
-                    CK(launch_gemm_f16(gemm_ln(gemm(x, W, k.in_wf, W, qkv, 3 * W, M, 3 * W, W, EPI_LN_BIAS), stats, W / 256, k.in_g, k.in_bf), h->gemm_variant, s));
-            } else {
-                CK(launch_layernorm(x, y, k.ln1_g, k.ln1_b, M, W, W, 0, s));
-                if (q_cls_only) {
-                    // (both launches take the kernel the all-token launch of last_q_cls = 0 would take -- the split-K kernel, 9, if
-                    //  [M, 3W] is a latency-bound shape, else the tile kernels, 7 -- so that the K summation order, and with it every
-                    //  bit, is the same either way)
-                    const int v = h->gemm_variant != 8 ? h->gemm_variant : (gemm_f16_is_small(M, 3 * W) ? 9 : 7);
-                    CK(launch_gemm_f16(gemm(y, W, (const half_t*)k.in_w + WW, W, qkv + W, 3 * W, M, 2 * W, W, EPI_BIAS, (const half_t*)k.in_b + W), v, s));
-                    CK(launch_gemm_f16(gemm(y, L * W, k.in_w, W, qkv, L * 3 * W, Bc, W, W, EPI_BIAS, k.in_b), v, s));
-                } else
-                    CK(launch_gemm_f16(gemm(y, W, k.in_w, W, qkv, 3 * W, M, 3 * W, W, EPI_BIAS, k.in_b), h->gemm_variant, s));
-            }
-            CK(launch_attention_f16_q(qkv, yc, Bc, L, 1, H, 0, h->attn_variant, s));
-            CK(launch_gemm_f16(gemm(yc, W, k.out_w, W, rows, W, Bc, W, W, EPI_BIAS_RES, k.out_b, x, L * W), h->gemm_variant, s));
-            CK(launch_layernorm(rows, yc, k.ln2_g, k.ln2_b, Bc, W, W, 0, s));
-            CK(launch_gemm_f16(gemm(yc, W, k.fc_w, W, hid_c, 4 * W, Bc, 4 * W, W, EPI_BIAS_QGELU, k.fc_b), h->gemm_variant + (h->gelu_exact ? 0 : 100), s));
-            CK(launch_gemm_f16(gemm(hid_c, 4 * W, k.pj_w, 4 * W, rows, W, Bc, W, 4 * W, EPI_BIAS_RES, k.pj_b, rows, W), h->gemm_variant, s));
-        }
+        for (size_t li = 0; li < h->vis.size(); ++li)           // the last block leaves its CLS rows in `rows` (run_block_f16, cls_rows)
+            CK(run_block_f16(h, h->vis[li], x, ws.y, ws.qkv, ws.hid, Bc, L, W, 0, s, stats, nullptr, li + 1 == h->vis.size() ? rows : nullptr));
         // K9: ln_post on the CLS rows, projection; K10: normalise
         CK(launch_layernorm(rows, rows, h->ln_post_g, h->ln_post_b, Bc, W, W, 0, s));
         CK(launch_gemm_f16(gemm(rows, W, h->proj_t, W, out, E, Bc, E, W, EPI_NONE), h->gemm_variant, s));
@@ -749,7 +772,7 @@ int ovmr_encode_text_groups(ovmr_handle* h, const ovmr_text_group* groups, int n
     }
     if (gs.empty()) return 0;
     hipStream_t s = (hipStream_t)stream;
-    if (text_groups_ws_bytes(h, M, N) <= h->ws_bytes) return run_text_groups(h, gs, s);      // one pass over all groups
+    if (text_ws(h, nullptr, M, N).bytes() <= h->ws_bytes) return run_text_groups(h, gs, s);      // one pass over all groups
     for (auto& g : gs) CK(run_text_group_chunked(h, g, s));                                    // too many rows for the workspace
     return 0;
 }
@@ -766,7 +789,7 @@ int ovmr_encode_text_ensemble(ovmr_handle* h, const int64_t* ids, int T, int C, 
         sumL += seq_lens ? seq_lens[t] : Lc;
     }
     // chunk of classes: the tower's rows for all T templates of c classes, then the [T, c, E] scratch of raw rows behind them
-    auto need = [&](size_t c) { return text_groups_ws_bytes(h, c * sumL, c * T) + align_up(c * T * E * 2); };
+    auto need = [&](size_t c) { return EnsembleWs(h, nullptr, c * sumL, c * T).bytes(); };
     if (need(1) > h->ws_bytes)
         return fail(h, OVMR_E_SHAPE, "the %d prompts of one class (%zu token rows) do not fit the workspace of %zu bytes: finalize with a "
                     "larger reserve", T, sumL, h->ws_bytes);
@@ -780,7 +803,7 @@ int ovmr_encode_text_ensemble(ovmr_handle* h, const int64_t* ids, int T, int C, 
     std::vector<TextGroup> gs(T);
     for (int i = 0, c0 = 0; i < n_chunks; ++i) {
         const int cc = C / n_chunks + (i < C % n_chunks ? 1 : 0);
-        half_t* raw = (half_t*)(h->ws + text_groups_ws_bytes(h, (size_t)cc * sumL, (size_t)cc * T));
+        half_t* raw = EnsembleWs(h, h->ws, (size_t)cc * sumL, (size_t)cc * T).raw;
         for (int t = 0; t < T; ++t) {                    // ids are template-major: [T, C, context_length]
             TextGroup& g = gs[t];
             g.ids = ids + ((size_t)t * C + c0) * Lc; g.N = cc; g.Ls = seq_lens ? seq_lens[t] : Lc; g.normalize = 0;
@@ -796,14 +819,14 @@ int ovmr_encode_text_ensemble(ovmr_handle* h, const int64_t* ids, int T, int C, 
 int ovmr_embed_tokens(ovmr_handle* h, const int64_t* ids, int N, int L, void* out_f16, ovmr_stream stream) {
     if (h && N == 0) return 0;
     if (!h || !ids || !out_f16 || N < 0 || L < 1) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     return launch_embed_gather(ids, h->tok_emb, (half_t*)out_f16, (long)N * L, h->d.transformer_width, (hipStream_t)stream);
 }
 
 int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S, float* tokens_f32, ovmr_stream stream) {
     if (h && Cb == 0) return 0;
     if (!h || !feats_f16 || !tokens_f32 || Cb < 0 || S < 1) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     const ovmr_model_desc& d = h->d;
     const int D = d.embed_dim, La = d.n_ctx + S;
     if (La > 128) return fail(h, OVMR_E_SHAPE, "n_ctx + shots = %d exceeds 128", La);
@@ -811,15 +834,10 @@ int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S, f
     const int chunk = (int)std::max(1L, h->agg_rows_cap / La);
     for (int c0 = 0; c0 < Cb; c0 += chunk) {
         const int Cc = std::min(chunk, Cb - c0);
-        const size_t M = (size_t)Cc * La;
-        Carver c(h->ws);
-        float* x = c.take<float>(M * D);
-        float* y = c.take<float>(M * D);
-        float* qkv = c.take<float>(M * 3 * D);
-        float* hid = c.take<float>(M * 4 * D);
-        CK(launch_agg_input(h->cls_token, (const half_t*)feats_f16 + (size_t)c0 * S * D, x, Cc, S, d.n_ctx, D, s));
-        for (auto& k : h->agg) CK(run_block_f32(h, k, x, y, qkv, hid, Cc, La, D, s));
-        CK(launch_agg_output(x, tokens_f32 + (size_t)c0 * d.n_ctx * D, Cc, La, d.n_ctx, D, s));
+        const AggWs ws(h, h->ws, (size_t)Cc * La);
+        CK(launch_agg_input(h->cls_token, (const half_t*)feats_f16 + (size_t)c0 * S * D, ws.x, Cc, S, d.n_ctx, D, s));
+        for (auto& k : h->agg) CK(run_block_f32(h, k, ws.x, ws.y, ws.qkv, ws.hid, Cc, La, D, s));
+        CK(launch_agg_output(ws.x, tokens_f32 + (size_t)c0 * d.n_ctx * D, Cc, La, d.n_ctx, D, s));
     }
     return 0;
 }
@@ -828,7 +846,7 @@ int ovmr_assemble_prompts(ovmr_handle* h, const void* base_f16, const int64_t* l
                           void* out_f16, ovmr_stream stream) {
     if (h && Cb == 0) return 0;
     if (!h || !base_f16 || !tokens_f32 || !out_f16 || Cb < 0) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     if (h->d.embed_dim != h->d.transformer_width)
         return fail(h, OVMR_E_SHAPE, "visual tokens (embed_dim %d) do not fit the text width %d", h->d.embed_dim, h->d.transformer_width);
     CK(launch_assemble_prompts((const half_t*)base_f16, labels, tokens_f32, (half_t*)out_f16, Cb, h->d.context_length,
@@ -840,11 +858,10 @@ int ovmr_xval_counts(ovmr_handle* h, const void* feats_f16, const int32_t* label
                      int32_t* tp, int32_t* n_pred, ovmr_stream stream) {
     if (h && R == 0) return 0;
     if (!h || !feats_f16 || !labels || !clf_f16 || !tp || !n_pred || R < 0 || C < 1) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int D = h->d.embed_dim;
-    Carver c(h->ws);
-    half_t* logits = c.take<half_t>((size_t)h->logit_elems_cap);
+    half_t* logits = HeadWs(h, h->ws, 1).l[0];
     if (h->xval_fused && R >= 256 && C >= 128) {
         // K18 + K19 fused: the [R, C] logits never reach HBM.  The GEMM epilogue leaves one
         // (maximum, lowest column) pair per row and 256-column tile; a row kernel finishes the argmax and counts.
@@ -914,7 +931,7 @@ int ovmr_fused_logits(ovmr_handle* h, const void* feats_f16, int B, const void* 
                       const float* w, int C, int mode, float* out_f32, ovmr_stream stream) {
     if (h && B == 0) return 0;
     if (!h || !feats_f16 || !out_f32 || B < 0 || C < 1) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int D = h->d.embed_dim;
     const void* clf[3];
@@ -937,15 +954,12 @@ int ovmr_fused_logits(ovmr_handle* h, const void* feats_f16, int B, const void* 
     const int chunk = (int)std::min<long>(std::max<long>(1, h->logit_elems_cap / C), 65536);
     for (int b0 = 0; b0 < B; b0 += chunk) {
         const int Bc = std::min(chunk, B - b0);
-        Carver c(h->ws);
-        half_t* l[3] = {nullptr, nullptr, nullptr};
-        for (int m = 0; m < 3; ++m) l[m] = c.take<half_t>((size_t)h->logit_elems_cap);
-        half_t* sf = c.take<half_t>((size_t)65536 * D);
+        const HeadWs ws(h, h->ws, 3);
         // (logit_scale * image_features) is rounded to fp16 before the matmul (:358-360)
-        CK(launch_scale_f16((const half_t*)feats_f16 + (size_t)b0 * D, sf, h->logit_scale_exp, (long)Bc * D, s));
+        CK(launch_scale_f16((const half_t*)feats_f16 + (size_t)b0 * D, ws.sf, h->logit_scale_exp, (long)Bc * D, s));
         for (int m = 0; m < n_mod; ++m)
-            CK(launch_gemm_f16(gemm(sf, D, clf[m], D, l[m], C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
-        CK(launch_fused_softmax(l[0], n_mod > 1 ? l[1] : nullptr, n_mod > 2 ? l[2] : nullptr,
+            CK(launch_gemm_f16(gemm(ws.sf, D, clf[m], D, ws.l[m], C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
+        CK(launch_fused_softmax(ws.l[0], n_mod > 1 ? ws.l[1] : nullptr, n_mod > 2 ? ws.l[2] : nullptr,
                                 mode == OVMR_MODE_FUSION ? w : nullptr, n_mod, out_f32 + (size_t)b0 * C, Bc, C, s));
     }
     return 0;
@@ -955,7 +969,7 @@ int ovmr_zeroshot_logits(ovmr_handle* h, const void* feats_f16, int B, const voi
                          ovmr_stream stream) {
     if (h && B == 0) return 0;
     if (!h || !feats_f16 || !text_f16 || !out_f16 || B < 0 || C < 1) return OVMR_E_ARG;
-    if (!h->finalized) return fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
+    if (int rc = need_finalized(h)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int D = h->d.embed_dim;
     if (h->fused_head) {                           // scale, product and the fp16 rounding of the logits in one launch
@@ -966,8 +980,7 @@ int ovmr_zeroshot_logits(ovmr_handle* h, const void* feats_f16, int B, const voi
     }
     for (int b0 = 0; b0 < B; b0 += 65536) {
         const int Bc = std::min(65536, B - b0);
-        Carver c(h->ws);
-        half_t* sf = c.take<half_t>((size_t)65536 * D);
+        half_t* sf = HeadWs(h, h->ws, 0).sf;
         CK(launch_scale_f16((const half_t*)feats_f16 + (size_t)b0 * D, sf, h->logit_scale_exp, (long)Bc * D, s));
         CK(launch_gemm_f16(gemm(sf, D, text_f16, D, (half_t*)out_f16 + (size_t)b0 * C, C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
     }
@@ -985,29 +998,25 @@ double ovmr_flops_per_image(const ovmr_handle* h) {
     const double G2 = (double)h->G * h->G, W = d.vision_width, K = 3.0 * d.vision_patch_size * d.vision_patch_size;
     return 2.0 * G2 * K * W + tower_flops(h->L, W, d.vision_layers) + 2.0 * W * d.embed_dim;
 }
-double ovmr_flops_per_image_executed(const ovmr_handle* h) {
-    if (!h) return 0;
-    const ovmr_model_desc& d = h->d;
-    const double L = h->L, W = d.vision_width;
-    // last block as launched: K/V projection of all tokens (4 L W^2), then one query row: scores + PV (4 L W), out_proj (2 W^2),
-    // MLP (16 W^2).  Q: for the CLS row alone (2 W^2) where the launch sequences hold >= 256 images and last_q_cls is set (what
-    // ovmr_encode_image does for a reserve of that size), else for every token (2 L W^2)
-    const bool q_cls = h->last_q_cls && (!h->finalized || std::min(h->max_images, h->enc_chunk > 0 ? h->enc_chunk : h->max_images) >= 256);
+// FLOPs of one image with the last block as launched: K/V projection of all tokens (4 L W^2), then one query row: scores + PV (4 L W),
+// out_proj (2 W^2), MLP (16 W^2).  Q: for the CLS row alone (2 W^2) where the launch sequence holds >= 256 images and last_q_cls is
+// set (q_cls), else for every token (2 L W^2)
+static double image_flops_executed(const ovmr_handle* h, bool q_cls) {
+    const double L = h->L, W = h->d.vision_width;
     const double last_full = 24.0 * L * W * W + 4.0 * L * L * W;
     const double last_run = 4.0 * L * W * W + 4.0 * L * W + 18.0 * W * W + (q_cls ? 2.0 * W * W : 2.0 * L * W * W);
     return ovmr_flops_per_image(h) - last_full + last_run;
 }
+double ovmr_flops_per_image_executed(const ovmr_handle* h) {
+    if (!h) return 0;
+    // (what ovmr_encode_image does for a reserve of that size)
+    return image_flops_executed(h, h->last_q_cls && (!h->finalized || std::min(h->max_images, h->enc_chunk > 0 ? h->enc_chunk : h->max_images) >= 256));
+}
 double ovmr_flops_executed(const ovmr_handle* h, int B) {
     if (!h || !h->finalized || B <= 0) return 0;
-    const ovmr_model_desc& d = h->d;
-    const double L = h->L, W = d.vision_width;
-    const double last_full = 24.0 * L * W * W + 4.0 * L * L * W;
     double total = 0;
-    for (const int Bc : encode_plan(h, B)) {               // the launch sequences ovmr_encode_image runs for this batch
-        const bool q_cls = h->last_q_cls && Bc >= 256;
-        const double last_run = 4.0 * L * W * W + 4.0 * L * W + 18.0 * W * W + (q_cls ? 2.0 * W * W : 2.0 * L * W * W);
-        total += Bc * (ovmr_flops_per_image(h) - last_full + last_run);
-    }
+    for (const int Bc : encode_plan(h, B))                 // the launch sequences ovmr_encode_image runs for this batch
+        total += Bc * image_flops_executed(h, h->last_q_cls && Bc >= 256);
     return total;
 }
 double ovmr_flops_per_prompt(const ovmr_handle* h, int seq_len) {
@@ -1049,27 +1058,13 @@ int ovmr_debug_lnfold(int variant, const void* A1, const void* W1, const void* b
     hipStream_t s = (hipStream_t)stream;
     if (D % 256 || N2 % 64) return OVMR_E_ARG;
     const int slots = D / 256;
-    float *stats = nullptr, *g = nullptr, *bf = nullptr;
-    half_t* wf = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&stats, (size_t)M * slots * 8) != hipSuccess || hipMalloc((void**)&g, (size_t)N2 * 4) != hipSuccess ||
-        hipMalloc((void**)&bf, (size_t)N2 * 4) != hipSuccess || hipMalloc((void**)&wf, (size_t)N2 * D * 2) != hipSuccess)
-        rc = OVMR_E_NOMEM;
-    if (!rc) rc = launch_fold_ln((const half_t*)W2, gamma, beta, (const half_t*)b2, wf, g, bf, N2, D, s);
-    if (!rc && A1) {
-        GemmArgs a = gemm(A1, K1, W1, K1, x1, D, M, D, K1, EPI_BIAS_RES, b1, res, D);
-        a.stats_out = stats;
-        rc = launch_gemm_f16(a, variant, s);
-    } else if (!rc) {
-        rc = launch_row_stats((const half_t*)x1, stats, M, D, slots, s);     // A1 == NULL: x1 is an input
-    }
-    if (!rc) {
-        GemmArgs a = gemm(x1, D, wf, D, C2, N2, M, N2, D, qgelu ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS);
-        a.ln_stats = stats; a.ln_slots = slots; a.ln_g = g; a.ln_b = bf;
-        rc = launch_gemm_f16(a, variant, s);
-    }
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(stats); (void)hipFree(g); (void)hipFree(bf); (void)hipFree(wf);
+    const LnFoldScratch f((size_t)M, W2, gamma, beta, b2, N2, D, s);
+    int rc = f.rc;
+    if (!rc && A1)
+        rc = launch_gemm_f16(gemm_stats(gemm(A1, K1, W1, K1, x1, D, M, D, K1, EPI_BIAS_RES, b1, res, D), f.stats), variant, s);
+    else if (!rc)
+        rc = launch_row_stats((const half_t*)x1, f.stats, M, D, slots, s);     // A1 == NULL: x1 is an input
+    if (!rc) rc = launch_gemm_f16(gemm_ln(gemm(x1, D, f.wf, D, C2, N2, M, N2, D, qgelu ? EPI_LN_BIAS_QGELU : EPI_LN_BIAS), f.stats, slots, f.g, f.bf), variant, s);
     return rc;
 }
 
@@ -1089,21 +1084,14 @@ int ovmr_debug_gemm_strided(int variant, const void* A, int lda, const void* W, 
     if (M <= 0 || N <= 0) return 0;
     const int slots = K / 256;
     const long rows = (long)(M - 1) * row_step + 1;
-    float *stats = nullptr, *g = nullptr, *bf = nullptr;
-    half_t* wf = nullptr;
-    int rc = 0;
-    if (hipMalloc((void**)&stats, (size_t)rows * slots * 8) != hipSuccess || hipMalloc((void**)&g, (size_t)N * 4) != hipSuccess ||
-        hipMalloc((void**)&bf, (size_t)N * 4) != hipSuccess || hipMalloc((void**)&wf, (size_t)N * K * 2) != hipSuccess)
-        rc = OVMR_E_NOMEM;
-    if (!rc) rc = launch_fold_ln((const half_t*)W, gamma, beta, (const half_t*)bias, wf, g, bf, N, K, s);
-    if (!rc) rc = rows > 0x7fffffffL ? OVMR_E_ARG : launch_row_stats((const half_t*)A, stats, (int)rows, K, slots, s);
+    const LnFoldScratch f((size_t)rows, W, gamma, beta, bias, N, K, s);
+    int rc = f.rc;
+    if (!rc) rc = rows > 0x7fffffffL ? OVMR_E_ARG : launch_row_stats((const half_t*)A, f.stats, (int)rows, K, slots, s);
     if (!rc) {
-        a = gemm_ln(gemm(A, lda, wf, K, C, ldc, M, N, K, epi), stats, slots, g, bf);
+        a = gemm_ln(gemm(A, lda, f.wf, K, C, ldc, M, N, K, epi), f.stats, slots, f.g, f.bf);
         a.ln_stride = row_step * slots;
         rc = launch_gemm_f16(a, variant, s);
     }
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(stats); (void)hipFree(g); (void)hipFree(bf); (void)hipFree(wf);
     return rc;
 }
 

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RES, EPI_PATCH, EPI_SCALE = range(6)
 GEMM_VARIANTS = [0, 6, 8, 9]    # 0: 128x128 register-staged; 6 / 8: 256-row LDS-DMA tiles (double-buffered / ping-pong K loop; 8 also picks
                                 # the 64x64 split-K kernel for latency-bound shapes); 9: the 64x64 split-K kernel wherever it takes the shape
-ATTN_VARIANTS = [0, 1, 3, 5]     # 5: 32x32x16 flash kernel for L >= 256 (variant 3 routes ViT-L there); variant 4 lives in the experiment build only
+ATTN_VARIANTS = [0, 1, 3, 5]     # 5: 32x32x16 flash kernel for L >= 256 (variant 3 routes ViT-L there); 4 is a retired kernel's number, an alias of 3
 
 
 @pytest.fixture(scope="module")

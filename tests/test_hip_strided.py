@@ -4,13 +4,13 @@ tolerances.  Every case also fills its output with a sentinel bit pattern and as
 rows and columns changed.  Needs an MI355X: run with `pytest -m gpu`.
 
 a. CLS-row Q projection: A strided by a sequence (lda = L*W), C by L*3W, and the folded form reading the LayerNorm statistics every
-   L rows (ln_stride) -- ovmr_amd/csrc/ovmr_api.hip:676-678 (folded) and :689 (plain).
-b. K/V projection written next to Q: W and bias offset by W rows, C = qkv + W with N = 2W, ldc = 3W -- ovmr_api.hip:675 and :688.
-c. out_proj of the CLS rows: residual read from the token rows (ldres = L*W), C a separate [Bc, W] -- ovmr_api.hip:694.
-d. logits with odd and padded ldc (N = classes, rows not 16-byte aligned) -- the head GEMMs of ovmr_api.hip:947 and :972.
+   L rows (ln_stride) -- ovmr_amd/csrc/ovmr_api.hip, the second part of the last block's in_proj in run_block_f16 (ln_linear: folded and plain).
+b. K/V projection written next to Q: W and bias offset by W rows, C = qkv + W with N = 2W, ldc = 3W -- its first part.
+c. out_proj of the CLS rows: residual read from the token rows (ldres = L*W), C a separate [Bc, W] -- run_block_f16 with cls_rows.
+d. logits with odd and padded ldc (N = classes, rows not 16-byte aligned) -- the head GEMMs of ovmr_fused_logits and ovmr_zeroshot_logits.
 e. A strided near the v5 kernel's 32-bit offset guard (gemm_f16_v5.hip:817-820): the last rows of both sides of M * lda * 2 = 2^31.
-f. attention for the first Lq < L queries (Lq = 1: the CLS query) -- launch_attention_f16_q at ovmr_api.hip:693.
-g. fp32 aggregator attention up to its L <= 128 limit (64 KiB of dynamic LDS) -- ovmr_api.hip:255, run by ovmr_generate_tokens (:821).
+f. attention for the first Lq < L queries (Lq = 1: the CLS query) -- launch_attention_f16_q in run_block_f16 with cls_rows.
+g. fp32 aggregator attention up to its L <= 128 limit (64 KiB of dynamic LDS) -- run_block_f32, run by ovmr_generate_tokens.
 """
 import pytest
 import torch
