@@ -8,8 +8,8 @@
     python -m ovmr_amd.cli --eval-only --trainer ZeroshotCLIP2 --root DATA --clip-weights ViT-B-16.pt \\
         --bpe-path bpe_simple_vocab_16e6.txt.gz --output-dir output/zsclip2 DATASET.NAME Caltech101
 
-runs the zero-shot trainers of trainers/zsclip.py on the same folder data set (main_zeroshot), and
-
+runs the zero-shot trainers of trainers/zsclip.py on the same folder data set.  Either way `main` is train.py's evaluation path,
+`trainer.build_trainer(cfg, dm, ...)` and `.test()` (ovmr_amd/trainer.py), on loaders of this runner's own.  It
 takes the command line of `scripts/mm_cls/generate_classifier.sh:30-44` / `train.py:183-255` as it is: `--dataset-config-file` and
 `--config-file` (YAML, read with PyYAML), the flags `reset_cfg` copies (`--root --output-dir --seed --trainer --backbone --init_weight
 --n_ctx --eval_mode --eval_tau`) and the trailing `KEY VALUE` opts, merged in train.py's order by `ovmr_amd.config.setup_cfg` with the
@@ -35,7 +35,6 @@ runner prints end-to-end images/s and the share of the time the host waited for 
 from __future__ import annotations
 
 import argparse
-import collections
 import os
 import os.path as osp
 import sys
@@ -263,35 +262,24 @@ def build_splits(cfg, eval_split: str = "train", test_split: str = "val", exempl
 BACKBONES = {"ViT-B/16": (768, 16, 12), "ViT-B/32": (768, 32, 12), "ViT-L/14": (1024, 14, 24), "ViT-L/14@336px": (1024, 14, 24)}   # clip/clip.py:32-40 (ViT entries)
 
 
-def main(argv=None) -> Dict[str, float]:
-    from . import config
-    from .templates import ZEROSHOT_TRAINERS
-    args = parse(argv)
-    cfg = config.setup_cfg(args)                              # train.py:134-155
-    if cfg.TRAINER.NAME not in ("MM_CLS_OP",) + ZEROSHOT_TRAINERS or not args.eval_only:
-        raise SystemExit("only `--eval-only --trainer MM_CLS_OP` (classifier generation / evaluation) and `--eval-only --trainer "
-                         "ZeroshotCLIP | ZeroshotCLIP2` (zero-shot evaluation) are on the hot path")
-    if cfg.TRAINER.NAME in ZEROSHOT_TRAINERS:
-        return main_zeroshot(args, cfg)
-    out_dir = cfg.OUTPUT_DIR
-    if osp.isdir(out_dir) and osp.exists(osp.join(out_dir, "mm_classifiers.pt")):
-        print(f"Oops! The results exist at {out_dir} (so skip this job)")       # generate_classifier.sh:27-28
-        return {}
-    shots, batch, seed = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE, cfg.SEED
-    if shots < 1:
-        raise SystemExit("DATASET.NUM_SHOTS must be >= 1: the eval-set loader draws NUM_SHOTS rows per class (data_manager.py:157-170)")
-    if batch < shots:
-        raise SystemExit(f"DATALOADER.TEST.BATCH_SIZE {batch} is smaller than DATASET.NUM_SHOTS {shots}: RandomClassSampler needs one class per batch")
-    if cfg.DATALOADER.K_TRANSFORMS != 1:
-        raise SystemExit("DATALOADER.K_TRANSFORMS > 1 only applies to training transforms; the test transform has one view")
+def _check_model_matches_cfg(spec, cfg) -> None:
+    name, size = cfg.MODEL.BACKBONE.NAME, spec.image_resolution
+    if name:
+        if name not in BACKBONES:
+            raise SystemExit(f"MODEL.BACKBONE.NAME {name!r}: only the ViT CLIP models are on the hot path ({sorted(BACKBONES)})")
+        if (spec.vision_width, spec.vision_patch_size, spec.vision_layers) != BACKBONES[name]:
+            raise SystemExit(f"--clip-weights holds a ViT of width {spec.vision_width}, patch {spec.vision_patch_size}, {spec.vision_layers} layers: "
+                             f"not MODEL.BACKBONE.NAME {name!r}")
+    if tuple(cfg.INPUT.SIZE) != (size, size):
+        raise SystemExit(f"INPUT.SIZE {tuple(cfg.INPUT.SIZE)} does not match the model's input resolution {size} "
+                         "(the positional embedding has one row per patch of that resolution, clip/model.py:416)")
 
+
+def _init_process_group(args) -> bool:
+    """Launched by torch.distributed.run (scripts/generate_classifier.sh with several GPUs): one rank per GPU, process group nccl = RCCL;
+    forward_prompt then shards the classes over the ranks (two collectives) and rank 0 evaluates and writes.
+    True when the group was opened here (and is this runner's to close); `args.device` becomes the rank's own GPU."""
     import torch
-    from . import checkpoint, modules
-    from .evaluator import Classification
-    from .tokenizer import BPETokenizer
-
-    # launched by torch.distributed.run (scripts/generate_classifier.sh with several GPUs): one rank per GPU, process group nccl = RCCL;
-    # forward_prompt then shards the classes over the ranks (two collectives) and rank 0 evaluates and writes
     import torch.distributed as dist
     own_group = False
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
@@ -310,156 +298,123 @@ def main(argv=None) -> Dict[str, float]:
         else:
             dist.init_process_group(backend, timeout=to)
         own_group = True
+    return own_group
+
+
+def _loader_factory(args, cfg, size: int, tfm: dict):
+    """loader(items, batch, rank, world, n_classes): the pipelined loader, or with no decode workers the in-thread FolderLoader."""
+    workers = cfg.DATALOADER.NUM_WORKERS if args.workers is None else args.workers
+    if workers <= 0:
+        return lambda items, batch, rank=0, world=1, n_classes=0: FolderLoader(items, batch, size, rank, world, n_classes, **tfm)
+    from .loader import PipelinedFolderLoader
+    kw = dict(workers=workers, prefetch=args.prefetch, device=args.device, fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
+    return lambda items, batch, rank=0, world=1, n_classes=0: PipelinedFolderLoader(items, batch, size, rank, world, n_classes, **kw)
+
+
+def _report_pipeline(results: dict, name: str, loader) -> None:
+    st = getattr(loader, "stats", None)      # (a FolderLoader keeps none)
+    if st:
+        print(f"input pipeline, {name}: {st['images']} images in {st['wall_s']:.2f} s = {st['images_per_s']:.0f} img/s end to end "
+              f"({st['workers']} decode workers, {st.get('device_resized', 0)} images resized on the GPU / {st.get('host_resized', 0)} by the workers), "
+              f"host blocked on decode {st['decode_wait_s']:.2f} s = {100 * st['decode_bound_fraction']:.0f} % of the time")
+        results[f"pipeline_{name.split()[0]}"] = st
+
+
+def main(argv=None) -> Dict[str, float]:
+    """train.py:183-255 on the evaluation path: build_trainer(cfg) and test().  MM_CLS_OP generates the classifiers from the exemplar set,
+    writes mm_classifiers.pt / visual_tokens.pt and evaluates the test set; the zero-shot trainers take the classes and test items of the
+    same job (build_splits; no exemplar is decoded) and the text classifier from DATASET.NAME's template(s), and write no model file.
+    The result block and acc_per_class.csv / f1_per_class.csv land in OUTPUT_DIR."""
+    from . import config, templates
+    args = parse(argv)
+    cfg = config.setup_cfg(args)                              # train.py:134-155
+    zeroshot = cfg.TRAINER.NAME in templates.ZEROSHOT_TRAINERS
+    if not (zeroshot or cfg.TRAINER.NAME == "MM_CLS_OP") or not args.eval_only:
+        raise SystemExit("only `--eval-only --trainer MM_CLS_OP` (classifier generation / evaluation) and `--eval-only --trainer "
+                         "ZeroshotCLIP | ZeroshotCLIP2` (zero-shot evaluation) are on the hot path")
+    shots, batch, seed = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE, cfg.SEED
+    split_cfg = cfg
+    if zeroshot:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit(f"--trainer {cfg.TRAINER.NAME} runs in one process: sharding the zero-shot test pass over ranks is not implemented")
+        try:
+            templates.check_dataset(cfg.DATASET.NAME)
+        except KeyError as e:
+            raise SystemExit(e.args[0]) from None
+        # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set); nothing of the draw is decoded
+        import copy
+        split_cfg = copy.deepcopy(cfg)
+        split_cfg.DATASET.NUM_SHOTS = max(1, shots)
+    else:
+        if osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
+            print(f"Oops! The results exist at {cfg.OUTPUT_DIR} (so skip this job)")       # generate_classifier.sh:27-28
+            return {}
+        if shots < 1:
+            raise SystemExit("DATASET.NUM_SHOTS must be >= 1: the eval-set loader draws NUM_SHOTS rows per class (data_manager.py:157-170)")
+        if batch < shots:
+            raise SystemExit(f"DATALOADER.TEST.BATCH_SIZE {batch} is smaller than DATASET.NUM_SHOTS {shots}: RandomClassSampler needs one class per batch")
+        if cfg.DATALOADER.K_TRANSFORMS != 1:
+            raise SystemExit("DATALOADER.K_TRANSFORMS > 1 only applies to training transforms; the test transform has one view")
+
+    import torch
+    import torch.distributed as dist
+    from types import SimpleNamespace
+    from . import checkpoint, modules, trainer
+    from .tokenizer import BPETokenizer
+    own_group = not zeroshot and _init_process_group(args)
     if seed >= 0:
         print(f"Setting fixed seed: {seed}")                  # train.py:157-159
         torch.manual_seed(seed)
-    classnames, exemplars, test_items = build_splits(cfg, args.eval_split, args.test_split, args.exemplar_list)
+    classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, args.test_split, args.exemplar_list)
 
-    clip_model = modules.build_model(checkpoint.load_clip_state_dict(args.clip_weights), device=args.device)
-    spec = clip_model.spec
-    size = spec.image_resolution
-    name = cfg.MODEL.BACKBONE.NAME
-    if name:
-        if name not in BACKBONES:
-            raise SystemExit(f"MODEL.BACKBONE.NAME {name!r}: only the ViT CLIP models are on the hot path ({sorted(BACKBONES)})")
-        if (spec.vision_width, spec.vision_patch_size, spec.vision_layers) != BACKBONES[name]:
-            raise SystemExit(f"--clip-weights holds a ViT of width {spec.vision_width}, patch {spec.vision_patch_size}, {spec.vision_layers} layers: "
-                             f"not MODEL.BACKBONE.NAME {name!r}")
-    if tuple(cfg.INPUT.SIZE) != (size, size):
-        raise SystemExit(f"INPUT.SIZE {tuple(cfg.INPUT.SIZE)} does not match the model's input resolution {size} "
-                         "(the positional embedding has one row per patch of that resolution, clip/model.py:416)")
+    # what the loaders need to know of the model is in the weights' shapes: the decode workers start before the engine exists
+    clip_sd = checkpoint.load_clip_state_dict(args.clip_weights)
+    spec = modules.infer_spec(clip_sd)
+    _check_model_matches_cfg(spec, cfg)
     normalize = "normalize" in tuple(cfg.INPUT.TRANSFORMS)    # transforms.py:514-518
     tfm = dict(interpolation=cfg.INPUT.INTERPOLATION, mean=tuple(cfg.INPUT.PIXEL_MEAN) if normalize else None,
                std=tuple(cfg.INPUT.PIXEL_STD) if normalize else None)
-    pl_state = None
-    if cfg.MODEL.INIT_WEIGHTS:                                # load_pretrained_weights (trainers/mm_classifier_one_prompt.py:403-404)
-        ck = checkpoint._torch_load(cfg.MODEL.INIT_WEIGHTS)
-        pl_state = ck["state_dict"] if "state_dict" in ck else ck
-    if args.model_dir:
-        pl_state = checkpoint.load_prompt_learner_state(args.model_dir, args.load_epoch)
-    else:
-        print("Note that load_model() is skipped as no pretrained model is given")       # :464-466
-    import torch.distributed as dist
-    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
-    workers = cfg.DATALOADER.NUM_WORKERS if args.workers is None else args.workers
-    if workers > 0:
-        from .loader import PipelinedFolderLoader
-        kw = dict(workers=workers, prefetch=args.prefetch, device=args.device, fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
-        eval_loader = PipelinedFolderLoader(exemplars, batch // shots * shots, size, rank, world, len(classnames), **kw)
-        test_loader = PipelinedFolderLoader(test_items, batch, size, **kw)
-        # the decode workers start while the engine takes the weights; on rank 0 one ring (sized for the larger batch) serves both loaders,
-        # ranks > 0 never touch the test set: theirs is sized for the exemplar batches alone
-        (eval_loader if rank > 0 or eval_loader.bs > test_loader.bs else test_loader).warm()
-    else:
-        eval_loader = FolderLoader(exemplars, batch // shots * shots, size, rank, world, len(classnames), **tfm)
-        test_loader = FolderLoader(test_items, batch, size, **tfm)
-    model = modules.CustomCLIP(cfg, classnames, clip_model, tokenizer=BPETokenizer(args.bpe_path),
-                               prompt_learner_state=pl_state, reserve=(batch, 256, max(1024, len(classnames))))
-    evaluator = Classification(len(classnames), classnames, device=args.device)
-    # the reference does this inside the first forward (:341-342); up front it keeps the two loaders' statistics apart.  Rank 0's two
-    # files are written by a worker thread while the test set runs (CustomCLIP._write_files), joined below
-    model.forward_prompt(eval_loader, wait_files=False)
-    if rank > 0:                             # the classifiers are complete on every rank; rank 0 evaluates the test set and reports
-        if own_group:
-            dist.barrier()
-            dist.destroy_process_group()
-        return {}
-    labels = collections.deque()
-
-    def test_images():
-        for b in test_loader:
-            labels.append(b["label"])
-            yield b["img"]
-
-    for out in model.forward_batches(test_images(), eval_set_loader=eval_loader):      # two test batches in flight (modules.py)
-        evaluator.process(out, labels.popleft())
-    model.wait_files()
-    results = dict(evaluator.evaluate(out_dir))
-    for name, ld in (("exemplar set", eval_loader), ("test set", test_loader)):
-        st = getattr(ld, "stats", None)
-        if st:
-            print(f"input pipeline, {name}: {st['images']} images in {st['wall_s']:.2f} s = {st['images_per_s']:.0f} img/s end to end "
-                  f"({st['workers']} decode workers, {st.get('device_resized', 0)} images resized on the GPU / {st.get('host_resized', 0)} by the workers), "
-                  f"host blocked on decode {st['decode_wait_s']:.2f} s = {100 * st['decode_bound_fraction']:.0f} % of the time")
-            results[f"pipeline_{name.split()[0]}"] = st
+    kw = {}
+    if not zeroshot:
+        pl_state = None
+        if cfg.MODEL.INIT_WEIGHTS:                            # load_pretrained_weights (trainers/mm_classifier_one_prompt.py:403-404)
+            ck = checkpoint._torch_load(cfg.MODEL.INIT_WEIGHTS)
+            pl_state = ck["state_dict"] if "state_dict" in ck else ck
+        if args.model_dir:
+            pl_state = checkpoint.load_prompt_learner_state(args.model_dir, args.load_epoch)
+        else:
+            print("Note that load_model() is skipped as no pretrained model is given")       # :464-466
+        kw["prompt_learner_state"] = pl_state
+    rank, world = (dist.get_rank(), dist.get_world_size()) if not zeroshot and dist.is_available() and dist.is_initialized() else (0, 1)
+    loader = _loader_factory(args, cfg, spec.image_resolution, tfm)
+    eval_loader = None if zeroshot else loader(exemplars, batch // shots * shots, rank, world, len(classnames))
+    test_loader = loader(test_items, batch)
+    # the decode workers start while the engine takes the weights; on rank 0 one ring (sized for the larger batch) serves both loaders,
+    # ranks > 0 never touch the test set: theirs is sized for the exemplar batches alone
+    first = eval_loader if eval_loader is not None and (rank > 0 or eval_loader.bs > test_loader.bs) else test_loader
+    if hasattr(first, "warm"):
+        first.warm()
+    dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
+    tr = trainer.build_trainer(cfg, dm, clip_weights=clip_sd, tokenizer=BPETokenizer(args.bpe_path), device=args.device,
+                               reserve=(batch, 256, max(1024, len(classnames))), **kw)
+    if not zeroshot:
+        # the reference does this inside the first forward (:341-342); up front it keeps the two loaders' statistics apart.  Rank 0's two
+        # files are written by a worker thread while the test set runs (CustomCLIP._write_files), joined at the end of test()
+        tr.model.forward_prompt(eval_loader, wait_files=False)
+        if rank > 0:                         # the classifiers are complete on every rank; rank 0 evaluates the test set and reports
+            if own_group:
+                dist.barrier()
+                dist.destroy_process_group()
+            return {}
+    tr.test()
+    results = dict(tr.results)
+    if not zeroshot:
+        _report_pipeline(results, "exemplar set", eval_loader)
+    _report_pipeline(results, "test set", test_loader)
     results["classnames"] = classnames
     if own_group:
         dist.barrier()
         dist.destroy_process_group()
-    return results
-
-
-def main_zeroshot(args, cfg) -> Dict[str, float]:
-    """`--eval-only --trainer ZeroshotCLIP | ZeroshotCLIP2` (trainers/zsclip.py): the classes and test items of the MM_CLS_OP job on the
-    same folder data set and command line (build_splits; no exemplar is decoded), the text classifier from DATASET.NAME's template(s),
-    the test set through inference_batches into the on-device evaluator; the result block and acc_per_class.csv / f1_per_class.csv
-    land in OUTPUT_DIR, no model file is written."""
-    import copy
-    from . import templates
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise SystemExit(f"--trainer {cfg.TRAINER.NAME} runs in one process: sharding the zero-shot test pass over ranks is not implemented")
-    try:
-        templates.check_dataset(cfg.DATASET.NAME)
-    except KeyError as e:
-        raise SystemExit(e.args[0]) from None
-    batch = cfg.DATALOADER.TEST.BATCH_SIZE
-    # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set); nothing of the draw is decoded
-    split_cfg = copy.deepcopy(cfg)
-    split_cfg.DATASET.NUM_SHOTS = max(1, cfg.DATASET.NUM_SHOTS)
-    classnames, _, test_items = build_splits(split_cfg, args.eval_split, args.test_split, args.exemplar_list)
-
-    import torch
-    from . import checkpoint, modules
-    from .evaluator import Classification
-    from .tokenizer import BPETokenizer
-    if cfg.SEED >= 0:
-        print(f"Setting fixed seed: {cfg.SEED}")              # train.py:157-159
-        torch.manual_seed(cfg.SEED)
-    name = cfg.MODEL.BACKBONE.NAME
-    print(f"Loading CLIP (backbone: {name})")                # trainers/zsclip.py:38
-    clip_model = modules.build_model(checkpoint.load_clip_state_dict(args.clip_weights), device=args.device)
-    spec = clip_model.spec
-    size = spec.image_resolution
-    if name:
-        if name not in BACKBONES:
-            raise SystemExit(f"MODEL.BACKBONE.NAME {name!r}: only the ViT CLIP models are on the hot path ({sorted(BACKBONES)})")
-        if (spec.vision_width, spec.vision_patch_size, spec.vision_layers) != BACKBONES[name]:
-            raise SystemExit(f"--clip-weights holds a ViT of width {spec.vision_width}, patch {spec.vision_patch_size}, {spec.vision_layers} layers: "
-                             f"not MODEL.BACKBONE.NAME {name!r}")
-    if tuple(cfg.INPUT.SIZE) != (size, size):
-        raise SystemExit(f"INPUT.SIZE {tuple(cfg.INPUT.SIZE)} does not match the model's input resolution {size}")
-    normalize = "normalize" in tuple(cfg.INPUT.TRANSFORMS)
-    tfm = dict(interpolation=cfg.INPUT.INTERPOLATION, mean=tuple(cfg.INPUT.PIXEL_MEAN) if normalize else None,
-               std=tuple(cfg.INPUT.PIXEL_STD) if normalize else None)
-    workers = cfg.DATALOADER.NUM_WORKERS if args.workers is None else args.workers
-    if workers > 0:
-        from .loader import PipelinedFolderLoader
-        test_loader = PipelinedFolderLoader(test_items, batch, size, workers=workers, prefetch=args.prefetch, device=args.device,
-                                            fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
-        test_loader.warm()                                    # the decode workers start while the text classifier is built
-    else:
-        test_loader = FolderLoader(test_items, batch, size, **tfm)
-    module = modules.ZeroshotCLIP2 if cfg.TRAINER.NAME == "ZeroshotCLIP2" else modules.ZeroshotCLIP
-    model = module.from_classnames(clip_model, classnames, cfg.DATASET.NAME, BPETokenizer(args.bpe_path),
-                                   reserve=(batch, 256, max(1024, len(classnames))))
-    evaluator = Classification(len(classnames), classnames, device=args.device)
-    print("Evaluate on the *test* set")
-    labels = collections.deque()
-
-    def test_images():
-        for b in test_loader:
-            labels.append(b["label"])
-            yield b["img"]
-
-    for out in model.inference_batches(test_images()):       # two test batches in flight (modules.py)
-        evaluator.process(out, labels.popleft())
-    results = dict(evaluator.evaluate(cfg.OUTPUT_DIR or None))
-    st = getattr(test_loader, "stats", None)
-    if st:
-        print(f"input pipeline, test set: {st['images']} images in {st['wall_s']:.2f} s = {st['images_per_s']:.0f} img/s end to end "
-              f"({st['workers']} decode workers), host blocked on decode {st['decode_wait_s']:.2f} s")
-        results["pipeline_test"] = st
-    results["classnames"] = classnames
     return results
 
 

@@ -8,24 +8,25 @@ against the reference
     trainer.load_model(args.model_dir, epoch=args.load_epoch)
     trainer.test()
 
-runs unchanged with `trainer = ovmr_amd.trainer.MM_CLS_OP(cfg, dm, clip_weights=...)`.  Everything that needs autograd
-(forward_backward, the optimiser, save_model) is out of scope and raises.
+runs unchanged with `trainer = ovmr_amd.trainer.MM_CLS_OP(cfg, dm, clip_weights=...)`; the runner (ovmr_amd/cli.py) is such a
+script.  Everything that needs autograd (forward_backward, the optimiser, save_model) is out of scope and
+raises.
 
 `dm` is anything with the four attributes the reference's DataManager (Dassl.pytorch/dassl/data/data_manager.py:116-170)
 hands the trainer: `dataset.classnames`, `test_loader`, `val_loader` (may be None) and `eval_set_loader`
 (`RandomClassSampler` batches: S consecutive rows per class).
 
 `ZeroshotCLIP` / `ZeroshotCLIP2` (trainers/zsclip.py) are registered next to it with the same Dassl-facing methods; they need only
-`dataset.classnames` and `test_loader`.
+`dataset.classnames` and `test_loader`.  What Dassl's SimpleTrainer gives all three lives in `_EvalTrainer`; a trainer class states
+`check_cfg`, `build_model`, `model_inference` and how its model turns the test batches into outputs.
 """
 from __future__ import annotations
 
 import collections
 import os
-import os.path as osp
 import random
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 
@@ -35,11 +36,17 @@ from .evaluator import Classification
 TRAINER_REGISTRY: Dict[str, type] = {}
 
 
-class MM_CLS_OP:
-    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0"):
+class _EvalTrainer:
+    """The evaluation side of Dassl's SimpleTrainer (trainer.py:321-521).  `reserve`: the engine's workspace reserve (images per
+    batch, exemplar rows, classes); None = the trainer class's own default."""
+
+    CLIP_FETCHED_BY = ""          # where the reference downloads the CLIP weights (the FileNotFoundError names it)
+    NOT_TRAINED = ""              # the NotImplementedError of forward_backward / train / save_model
+
+    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None):
         self.check_cfg(cfg)
         self.cfg, self.dm, self.device = cfg, dm, torch.device(device)
-        self._clip_weights, self._tokenizer = clip_weights, tokenizer
+        self._clip_weights, self._tokenizer, self._reserve = clip_weights, tokenizer, reserve
         self._models: "OrderedDict[str, object]" = OrderedDict()
         self.test_loader = dm.test_loader
         self.val_loader = getattr(dm, "val_loader", None)
@@ -50,33 +57,21 @@ class MM_CLS_OP:
         self.build_model()
         self.evaluator = Classification(self.num_classes, list(dm.dataset.classnames), device=str(self.device))
 
-    # :369-370
     def check_cfg(self, cfg):
-        assert cfg.TRAINER.COCOOP.PREC in ["fp16", "fp32", "amp"]
+        pass
 
-    # :372-419 (inference-relevant part: CLIP weights -> CustomCLIP -> optional INIT_WEIGHTS -> register "prompt_learner")
     def build_model(self):
-        cfg = self.cfg
-        random.seed(cfg.SEED)
-        classnames = self.dm.dataset.classnames
-        print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")
+        raise NotImplementedError
+
+    def load_clip(self) -> "modules.CLIPModel":
+        """load_clip_to_cpu + clip_model.to(device) of the reference's build_model, from `clip_weights` (a path or a state dict)."""
+        print(f"Loading CLIP (backbone: {self.cfg.MODEL.BACKBONE.NAME})")
         w = self._clip_weights
         if w is None:
-            raise FileNotFoundError("MM_CLS_OP needs clip_weights= (an OpenAI CLIP .pt file or a state dict): "
-                                    "there is no download on this path (clip/clip.py:29-70 fetches it in the reference)")
+            raise FileNotFoundError(f"{type(self).__name__} needs clip_weights= (an OpenAI CLIP .pt file or a state dict): "
+                                    f"there is no download on this path ({self.CLIP_FETCHED_BY} fetches it in the reference)")
         sd = checkpoint.load_clip_state_dict(w) if isinstance(w, (str, os.PathLike)) else w
-        clip_model = modules.build_model(sd, device=str(self.device))
-        if cfg.TRAINER.COCOOP.PREC != "fp16":
-            # the reference calls clip_model.float() here (:380-382) and then fails inside forward_prompt, whose buffers are
-            # fp16 (:216-225): only fp16 evaluation exists
-            raise RuntimeError("the OVMR evaluation path is fp16-only (trainers/mm_classifier_one_prompt.py:216-225)")
-        print("Building custom CLIP")
-        self.model = modules.CustomCLIP(cfg, classnames, clip_model, tokenizer=self._tokenizer)
-        init = getattr(cfg.MODEL, "INIT_WEIGHTS", "")
-        if init:                                                              # load_pretrained_weights (:403-404)
-            ckpt = checkpoint._torch_load(init)
-            self.model.prompt_learner.load_state_dict(ckpt["state_dict"] if "state_dict" in ckpt else ckpt, strict=False)
-        self.register_model("prompt_learner", self.model.prompt_learner)     # :410
+        return modules.build_model(sd, device=str(self.device))
 
     def register_model(self, name, model, optim=None, sched=None):
         self._models[name] = model
@@ -84,14 +79,12 @@ class MM_CLS_OP:
     def get_model_names(self, names=None):
         return list(self._models.keys()) if names is None else list(names)
 
-    # :454-459 / trainer.py:510-518
-    def parse_batch_train(self, batch):
-        return batch["img"].to(self.device), batch["label"].to(self.device)
-
+    # trainer.py:515-521.  The copies are enqueued like the engine's and the evaluator's own (Engine._dev, Classification.process): a
+    # batch that is already where it belongs costs nothing, and no batch makes the host wait for the stream
     def parse_batch_test(self, batch):
-        return batch["img"].to(self.device), batch["label"].to(self.device)
+        return batch["img"].to(self.device, non_blocking=True), batch["label"].to(self.device, non_blocking=True)
 
-    # :461-493 -- the file handling lives in ovmr_amd.checkpoint (Dassl layout, "module." prefixes, dropped token buffers)
+    # trainer.py:461-493 -- the file handling lives in ovmr_amd.checkpoint (Dassl layout, "module." prefixes, dropped token buffers)
     def load_model(self, directory, epoch=None):
         if not directory:
             print("Note that load_model() is skipped as no pretrained model is given")
@@ -101,11 +94,12 @@ class MM_CLS_OP:
             print(f'Loading weights to {name} from "{path}" (epoch = {saved_epoch})')
             self._models[name].load_state_dict(state, strict=False)
 
-    # trainer.py:504-508
-    def model_inference(self, input, scale_no=0, label=None):
-        if self.eval_set_loader is not None:
-            return self.model(input, eval_set_loader=self.eval_set_loader, scale_no=scale_no, label=label)
-        return self.model(input, label=label)
+    def outputs(self, inputs):
+        """model_inference for every input batch of the test pass, in order (a model may keep further batches in flight)."""
+        raise NotImplementedError
+
+    def after_test(self):
+        """What a trainer still owes once the last output has been counted."""
 
     # trainer.py:460-482 (DATASET.REGION_AUG False)
     @torch.no_grad()
@@ -119,7 +113,7 @@ class MM_CLS_OP:
             split = "test"
             data_loader = self.test_loader
         print(f"Evaluate on the *{split}* set")
-        labels = collections.deque()                 # model_inference's forwards (:504-508), two batches in flight (CustomCLIP.forward_batches)
+        labels = collections.deque()                 # an output is handed over after later batches have been fetched (two in flight)
 
         def inputs():
             for batch in data_loader:
@@ -127,101 +121,101 @@ class MM_CLS_OP:
                 labels.append(label)
                 yield input
 
-        for output in self.model.forward_batches(inputs(), eval_set_loader=self.eval_set_loader):
+        for output in self.outputs(inputs()):
             self.evaluator.process(output, labels.popleft())
-        self.model.wait_files()                      # mm_classifiers.pt / visual_tokens.pt were written while the test set ran
-        results = self.evaluator.evaluate(self.output_dir or None)
-        return list(results.values())[0]
+        self.after_test()
+        self.results = self.evaluator.evaluate(self.output_dir or None)
+        return list(self.results.values())[0]
 
     def forward_backward(self, batch):
-        raise NotImplementedError("training (autograd through CustomCLIP.forward, :310-338) is out of scope of the HIP hot path")
+        raise NotImplementedError(self.NOT_TRAINED)
 
     train = save_model = forward_backward
+
+
+class MM_CLS_OP(_EvalTrainer):
+    """`prompt_learner_state`: the prompt learner's weights, already resolved by the caller; CustomCLIP then refuses an incomplete
+    set (a later load_model can not: PromptLearner.load_state_dict counts the keys it holds as present) and MODEL.INIT_WEIGHTS is
+    not read here."""
+
+    CLIP_FETCHED_BY = "clip/clip.py:29-70"
+    NOT_TRAINED = "training (autograd through CustomCLIP.forward, :310-338) is out of scope of the HIP hot path"
+
+    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, prompt_learner_state=None):
+        self._prompt_learner_state = prompt_learner_state
+        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve)
+
+    # :369-370
+    def check_cfg(self, cfg):
+        assert cfg.TRAINER.COCOOP.PREC in ["fp16", "fp32", "amp"]
+
+    # :372-419 (inference-relevant part: CLIP weights -> CustomCLIP -> optional INIT_WEIGHTS -> register "prompt_learner")
+    def build_model(self):
+        cfg = self.cfg
+        random.seed(cfg.SEED)
+        clip_model = self.load_clip()
+        if cfg.TRAINER.COCOOP.PREC != "fp16":
+            # the reference calls clip_model.float() here (:380-382) and then fails inside forward_prompt, whose buffers are
+            # fp16 (:216-225, SURVEY.md 8a-8): only fp16 evaluation exists
+            raise RuntimeError("the OVMR evaluation path is fp16-only (trainers/mm_classifier_one_prompt.py:216-225)")
+        print("Building custom CLIP")
+        self.model = modules.CustomCLIP(cfg, self.dm.dataset.classnames, clip_model, tokenizer=self._tokenizer,
+                                        prompt_learner_state=self._prompt_learner_state, reserve=self._reserve)
+        init = getattr(cfg.MODEL, "INIT_WEIGHTS", "")
+        if init and self._prompt_learner_state is None:                       # load_pretrained_weights (:403-404)
+            ckpt = checkpoint._torch_load(init)
+            self.model.prompt_learner.load_state_dict(ckpt["state_dict"] if "state_dict" in ckpt else ckpt, strict=False)
+        self.register_model("prompt_learner", self.model.prompt_learner)     # :410
+
+    # :454-459
+    def parse_batch_train(self, batch):
+        return self.parse_batch_test(batch)
+
+    # trainer.py:504-508
+    def model_inference(self, input, scale_no=0, label=None):
+        if self.eval_set_loader is not None:
+            return self.model(input, eval_set_loader=self.eval_set_loader, scale_no=scale_no, label=label)
+        return self.model(input, label=label)
+
+    def outputs(self, inputs):
+        return self.model.forward_batches(inputs, eval_set_loader=self.eval_set_loader)
+
+    def after_test(self):
+        self.model.wait_files()                      # mm_classifiers.pt / visual_tokens.pt were written while the test set ran
 
 
 TRAINER_REGISTRY["MM_CLS_OP"] = MM_CLS_OP
 
 
-class ZeroshotCLIP:
-    """trainers/zsclip.py:32-60 (BASELINE configuration 1) with the Dassl-facing methods MM_CLS_OP has: build_model, parse_batch_test,
-    model_inference, load_model and test().  `dm` needs `dataset.classnames` and `test_loader` (`val_loader` optional); cfg.DATASET.NAME
-    picks the template (ovmr_amd.templates).  Nothing is trained and nothing is registered, so load_model has nothing to load."""
+class ZeroshotCLIP(_EvalTrainer):
+    """trainers/zsclip.py:32-60 (BASELINE configuration 1).  `dm` needs `dataset.classnames` and `test_loader` (`val_loader` optional);
+    cfg.DATASET.NAME picks the template (ovmr_amd.templates).  Nothing is trained and nothing is registered, so load_model has nothing
+    to load."""
 
     MODULE = modules.ZeroshotCLIP
+    CLIP_FETCHED_BY = "trainers/coop.py load_clip_to_cpu"
+    NOT_TRAINED = "the zero-shot trainers have nothing to train"
 
-    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0"):
+    def check_cfg(self, cfg):
         from . import templates
         templates.check_dataset(cfg.DATASET.NAME)                           # (the reference's CUSTOM_TEMPLATES lookup, :42 / :83)
-        self.cfg, self.dm, self.device = cfg, dm, torch.device(device)
-        self._clip_weights, self._tokenizer = clip_weights, tokenizer
-        self._models: "OrderedDict[str, object]" = OrderedDict()
-        self.test_loader = dm.test_loader
-        self.val_loader = getattr(dm, "val_loader", None)
-        self.num_classes = len(dm.dataset.classnames)
-        self.epoch = 0
-        self.output_dir = cfg.OUTPUT_DIR
-        self.build_model()
-        self.evaluator = Classification(self.num_classes, list(dm.dataset.classnames), device=str(self.device))
 
     def build_model(self):
         cfg = self.cfg
         classnames = self.dm.dataset.classnames
-        print(f"Loading CLIP (backbone: {cfg.MODEL.BACKBONE.NAME})")       # :38
-        w = self._clip_weights
-        if w is None:
-            raise FileNotFoundError(f"{type(self).__name__} needs clip_weights= (an OpenAI CLIP .pt file or a state dict): "
-                                    "there is no download on this path (trainers/coop.py load_clip_to_cpu fetches it in the reference)")
-        sd = checkpoint.load_clip_state_dict(w) if isinstance(w, (str, os.PathLike)) else w
-        self.clip_model = modules.build_model(sd, device=str(self.device))
-        batch = getattr(getattr(cfg.DATALOADER, "TEST", None), "BATCH_SIZE", 256)
-        self.model = self.MODULE.from_classnames(self.clip_model, classnames, cfg.DATASET.NAME, self._tokenizer,
-                                                 reserve=(batch, 256, max(1024, len(classnames))))
+        self.clip_model = self.load_clip()                                   # :38
+        reserve = self._reserve
+        if reserve is None:
+            batch = getattr(getattr(cfg.DATALOADER, "TEST", None), "BATCH_SIZE", 256)
+            reserve = (batch, 256, max(1024, len(classnames)))
+        self.model = self.MODULE.from_classnames(self.clip_model, classnames, cfg.DATASET.NAME, self._tokenizer, reserve=reserve)
         self.text_features = self.model.text_features
-
-    def get_model_names(self, names=None):
-        return list(self._models.keys()) if names is None else list(names)
-
-    def parse_batch_test(self, batch):
-        return batch["img"].to(self.device), batch["label"].to(self.device)
-
-    def load_model(self, directory, epoch=None):
-        """Dassl's load_model (trainer.py:461-493) over the registered models: there are none."""
-        if not directory:
-            print("Note that load_model() is skipped as no pretrained model is given")
 
     def model_inference(self, image):
         return self.model.model_inference(image)                             # :55-60
 
-    @torch.no_grad()
-    def test(self, split=None):
-        """Dassl's SimpleTrainer.test (trainer.py:460-482): two test batches in flight (ZeroshotCLIP.inference_batches), counted by the
-        on-device evaluator."""
-        self.evaluator.reset()
-        if split is None:
-            split = getattr(getattr(self.cfg, "TEST", None), "SPLIT", "test")
-        if split == "val" and self.val_loader is not None:
-            data_loader = self.val_loader
-        else:
-            split = "test"
-            data_loader = self.test_loader
-        print(f"Evaluate on the *{split}* set")
-        labels = collections.deque()
-
-        def inputs():
-            for batch in data_loader:
-                input, label = self.parse_batch_test(batch)
-                labels.append(label)
-                yield input
-
-        for output in self.model.inference_batches(inputs()):
-            self.evaluator.process(output, labels.popleft())
-        results = self.evaluator.evaluate(self.output_dir or None)
-        return list(results.values())[0]
-
-    def forward_backward(self, batch):
-        raise NotImplementedError("the zero-shot trainers have nothing to train")
-
-    train = save_model = forward_backward
+    def outputs(self, inputs):
+        return self.model.inference_batches(inputs)
 
 
 class ZeroshotCLIP2(ZeroshotCLIP):

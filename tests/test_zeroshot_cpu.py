@@ -115,3 +115,56 @@ def test_zero_shot_trainers_are_registered():
             assert callable(getattr(cls, m)), (name, m)
         with pytest.raises(NotImplementedError):
             cls.train(object.__new__(cls), None)
+
+
+def test_one_test_loop_pairs_late_outputs_with_their_own_labels(capsys):
+    """trainer._EvalTrainer.test() on the host, without an engine: a model that hands batch i's outputs over after batch i + 1 has been
+    fetched (two in flight) still has every output counted against its own batch's labels; the split rule; the after-loop hook."""
+    from types import SimpleNamespace
+    import torch
+    from ovmr_amd import modules, trainer
+    C = 3
+    log = []
+
+    class Late(trainer._EvalTrainer):
+        def build_model(self):
+            pass
+
+        def outputs(self, inputs):                       # an "image" batch is its rows' predicted classes
+            held = None
+            for n, x in enumerate(inputs):
+                if held is not None:
+                    log.append(("output", n - 1))
+                    yield held
+                held = torch.nn.functional.one_hot(x, C).float()
+                last = n
+            log.append(("output", last))
+            yield held
+            log.append("exhausted")
+
+        def after_test(self):
+            log.append("after")
+
+    def batches(pred, label, sizes):
+        pred, label = torch.tensor(pred).split(sizes), torch.tensor(label).split(sizes)
+        return [{"img": p, "label": l} for p, l in zip(pred, label)]
+
+    # 3 + 2 rows; rows 1 and 4 are wrong: 3 of 5.  Batch 1's outputs against batch 0's labels would not even have batch 0's length
+    test_loader = batches([0, 2, 2, 1, 1], [0, 1, 2, 1, 0], [3, 2])
+    val_loader = batches([2, 1, 0, 0], [2, 1, 0, 1], [2, 2])             # 3 of 4
+    cfg = modules.make_cfg(output_dir="")
+    cfg.TEST = SimpleNamespace(SPLIT="val")
+    for split, val, want, used in (("val", None, 60.0, "test"), ("test", val_loader, 60.0, "test"), ("val", val_loader, 75.0, "val")):
+        cfg.TEST.SPLIT = split
+        dm = SimpleNamespace(dataset=SimpleNamespace(classnames=["a", "b", "c"]), test_loader=test_loader, val_loader=val)
+        t = Late(cfg, dm, device="cpu")
+        del log[:]
+        capsys.readouterr()
+        acc = t.test()
+        assert f"Evaluate on the *{used}* set" in capsys.readouterr().out
+        assert acc == pytest.approx(want) and acc == list(t.results.values())[0] == t.results["accuracy"]
+        assert t.results["error_rate"] == pytest.approx(100.0 - want)
+        assert log == [("output", 0), ("output", 1), "exhausted", "after"]
+    assert t.test(split="test") == pytest.approx(60.0)                     # an explicit split overrides TEST.SPLIT
+    for k in (trainer.MM_CLS_OP, trainer.ZeroshotCLIP, trainer.ZeroshotCLIP2):
+        assert k.test is trainer._EvalTrainer.test and k.load_model is trainer._EvalTrainer.load_model

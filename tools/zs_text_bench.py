@@ -31,7 +31,7 @@ def main():
     e = Engine(spec, 2)
     e.load_state_dict({k: torch.from_numpy(v) for k, v in synth.clip_state_dict(spec, 11, jitter=True).items()},
                       {k: torch.from_numpy(v) for k, v in synth.prompt_learner_state_dict(spec, 2, 11, True).items()})
-    e.finalize(256, 256, 1024)                                   # the runner's reserve (cli.main_zeroshot, test batch 256)
+    e.finalize(256, 256, 1024)                                   # the runner's reserve (cli.main, test batch 256)
     rng = np.random.default_rng(0)
     for C in a.classes:
         T = a.templates
