@@ -228,6 +228,17 @@ int ovmr_unpack_rows(const void* gathered_f16, int rows, int C, int D, int n_ctx
  * accuracy, error rate, macro-F1 and the per-class tables of evaluate() (:69-138) are functions of these 3C integers.  Needs no handle. */
 int ovmr_eval_counts(const void* outputs, int dtype, long ld, const int64_t* labels, int B, int C, int32_t* counts, ovmr_stream stream);
 
+/* Classification.process(topk > 1) (Dassl.pytorch/dassl/evaluation/evaluator.py:56-58) and ranked prediction: per row of outputs [B, C] (fp16 or
+ * fp32, row stride ld >= C elements) the k best columns, best first.  The order is total: larger value first, equal values in increasing
+ * column order, every NaN above +inf (NaNs among themselves in increasing column order), -0.0 == +0.0 (ordered by column) -- what
+ * torch.sort(descending=True, stable=True) gives on the host, so column 0 is the prediction ovmr_eval_counts counts for the same row.
+ * values (may be NULL): the selected elements as fp32 (fp16 converts exactly, a NaN stays a NaN); indices: int32 [B, k].  labels int64 [B]
+ * and hits int32 [1] come together or not at all: hits[0] += the number of rows whose label is among the row's k columns (:56-58; a label
+ * outside [0, C) never hits; the caller zeroes hits once and accumulates over the batches of a test pass).  1 <= k <= min(C, 32),
+ * otherwise OVMR_E_ARG; B == 0 returns 0.  One launch; needs no handle. */
+int ovmr_topk_rows(const void* outputs, int dtype, long ld, int B, int C, int k, float* values, int32_t* indices,
+                   const int64_t* labels, int32_t* hits, ovmr_stream stream);
+
 /* exp(logit_scale) as held by the handle (set through ovmr_set_weight("logit_scale")). */
 float ovmr_logit_scale(const ovmr_handle* h);
 

@@ -8,7 +8,12 @@
     python -m ovmr_amd.cli --eval-only --trainer ZeroshotCLIP2 --root DATA --clip-weights ViT-B-16.pt \\
         --bpe-path bpe_simple_vocab_16e6.txt.gz --output-dir output/zsclip2 DATASET.NAME Caltech101
 
-runs the zero-shot trainers of trainers/zsclip.py on the same folder data set.  Either way `main` is train.py's evaluation path,
+runs the zero-shot trainers of trainers/zsclip.py on the same folder data set, and
+
+    python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --predict IMAGES --topk 5 [--classifiers OUTPUT_DIR/mm_classifiers.pt]
+
+ranks the job's classes for UNLABELLED images (a directory, or a text file of paths) instead of the test pass: OUTPUT_DIR/predictions.csv holds
+`image,rank,label,classname,score` (any of the three trainers; `--classifiers` loads a generated file instead of generating again).  Either way `main` is train.py's evaluation path,
 `trainer.build_trainer(cfg, dm, ...)` and `.test()` (ovmr_amd/trainer.py), on loaders of this runner's own.  It
 takes the command line of `scripts/mm_cls/generate_classifier.sh:30-44` / `train.py:183-255` as it is: `--dataset-config-file` and
 `--config-file` (YAML, read with PyYAML), the flags `reset_cfg` copies (`--root --output-dir --seed --trainer --backbone --init_weight
@@ -17,7 +22,7 @@ reference's defaults (EVAL_MODE multimodal, N_CTX 16, DATALOADER.TEST.BATCH_SIZE
 config file says otherwise -- exactly what train.py does without its YAML files).  Keys this path honours: `DATASET.NUM_SHOTS`,
 `DATASET.SUBSAMPLE_CLASSES` (all | base | new, datasets/oxford_pets.py:141-202), `DATALOADER.TEST.BATCH_SIZE`, `DATALOADER.NUM_WORKERS`,
 `INPUT.SIZE / INTERPOLATION / PIXEL_MEAN / PIXEL_STD / TRANSFORMS`, `TRAINER.COCOOP.N_CTX`, `MODEL.BACKBONE.NAME`, `MODEL.INIT_WEIGHTS`,
-`EVAL_MODE`, `EVAL_TAU`, `SEED`, `OUTPUT_DIR`; training / optimiser keys are accepted and ignored; any other key raises.  yacs / Dassl
+`EVAL_MODE`, `EVAL_TAU`, `SEED`, `OUTPUT_DIR`, `TEST.TOPK`; training / optimiser keys are accepted and ignored; any other key raises.  yacs / Dassl
 are not needed; `--transforms` sets INPUT.TRANSFORMS as in train.py:69-70, train.py's remaining flags (`--source-domains --target-domains
 --fs_classifier --head --stage_num --visual_token_path`) are accepted and ignored.  Extra flags of this runner: `--clip-weights` (no download here), `--bpe-path`, `--eval-split / --test-split`, the
 input-pipeline knobs, `--exemplar-list`.  Data layout (datasets/imagenet.py:146-159):
@@ -187,6 +192,58 @@ def read_exemplar_list(path: str, num_classes: int, shots: int) -> List[Tuple[st
     return few
 
 
+IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".gif", ".ppm", ".pgm", ".tif", ".tiff", ".webp")
+MAX_TOPK = 32                 # ovmr_topk_rows (include/ovmr_hip.h)
+
+
+def list_predict_images(path: str) -> List[str]:
+    """`--predict PATH`: a directory -- every image file below it (IMAGE_EXTENSIONS, hidden names skipped), sorted by path -- or a text
+    file with one image path per line, in file order.  Checked before anything is loaded: an empty PATH or a missing file is a SystemExit
+    that names it."""
+    if not path:
+        raise SystemExit("--predict: PATH is empty (a directory of images, or a text file with one image path per line)")
+    if osp.isdir(path):
+        images = []
+        for d, dirs, files in os.walk(path):
+            dirs[:] = [x for x in dirs if not x.startswith(".")]
+            images += [osp.join(d, n) for n in files if not n.startswith(".") and n.lower().endswith(IMAGE_EXTENSIONS)]
+        if not images:
+            raise SystemExit(f"--predict {path!r}: no image file below this directory ({', '.join(IMAGE_EXTENSIONS)})")
+        return sorted(images)
+    if not osp.isfile(path):
+        raise SystemExit(f"--predict {path!r}: no such directory or list file")
+    images = []
+    with open(path) as f:
+        for no, raw in enumerate(f, 1):
+            img = raw.strip()
+            if not img:
+                continue
+            if not osp.isfile(img):
+                raise SystemExit(f"{path}:{no}: image {img!r} does not exist")
+            images.append(img)
+    if not images:
+        raise SystemExit(f"--predict {path!r}: the list names no image")
+    return images
+
+
+def ranked_predictions(paths: Sequence[str], values, indices, classnames: Sequence[str]):
+    """[(path, [(label, classname, score), ...k])] from the [N, k] values / indices of a prediction pass."""
+    return [(p, [(int(c), classnames[int(c)], float(v)) for v, c in zip(vs, cs)]) for p, vs, cs in zip(paths, values.tolist(), indices.tolist())]
+
+
+def write_predictions(path: str, predictions) -> None:
+    """predictions.csv: `image,rank,label,classname,score`, one line per (image, rank) in input order, ranks 0..k-1; the score is
+    repr(float), so it parses back to the same value."""
+    import csv
+    os.makedirs(osp.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, delimiter=",", lineterminator="\n")
+        w.writerow(["image", "rank", "label", "classname", "score"])
+        for image, ranks in predictions:
+            for rank, (label, name, score) in enumerate(ranks):
+                w.writerow([image, rank, label, name, repr(float(score))])
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     # the reference's flags, with the reference's defaults (train.py:183-255)
@@ -224,6 +281,11 @@ def parse(argv=None):
     ap.add_argument("--test-split", default="val")
     ap.add_argument("--exemplar-list", default="", help="text file, one `<image path> <label>` per line: use exactly these exemplars (e.g. a "
                     "reference run's few-shot set) instead of drawing NUM_SHOTS per class under --seed; labels are those BEFORE class subsampling")
+    ap.add_argument("--predict", metavar="PATH", default=None, help="ranked prediction on UNLABELLED images instead of the test pass: a directory "
+                    "(every image file below it, sorted by path) or a text file with one image path per line; writes OUTPUT_DIR/predictions.csv")
+    ap.add_argument("--topk", type=int, default=None, metavar="K", help="classes per image of --predict, best first (default 5; 1 <= K <= min(32, classes))")
+    ap.add_argument("--classifiers", metavar="FILE", default="", help="with --predict --trainer MM_CLS_OP: load this mm_classifiers.pt instead of "
+                    "generating the classifiers (no exemplar is decoded, no model file is written)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode worker processes of the pipelined loader (default: DATALOADER.NUM_WORKERS); 0 = decode in this thread")
@@ -244,7 +306,7 @@ def build_splits(cfg, eval_split: str = "train", test_split: str = "val", exempl
     root = cfg.DATASET.ROOT
     folders, eval_all = list_split(root, eval_split)
     all_names = read_classnames(root, folders)
-    _, test_items = list_split(root, test_split)
+    test_items = list_split(root, test_split)[1] if test_split else []       # (a prediction run has no labelled test split)
     if exemplar_list:
         few = read_exemplar_list(exemplar_list, len(folders), shots)
     else:
@@ -334,6 +396,25 @@ def main(argv=None) -> Dict[str, float]:
                          "ZeroshotCLIP | ZeroshotCLIP2` (zero-shot evaluation) are on the hot path")
     shots, batch, seed = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE, cfg.SEED
     split_cfg = cfg
+    predict, images, k = args.predict is not None, [], None
+    if predict:
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--predict runs in one process: sharding the prediction pass over ranks is not implemented")
+        k = 5 if args.topk is None else args.topk
+        if not 1 <= k <= MAX_TOPK:
+            raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, number of classes)]")
+        if args.classifiers and zeroshot:
+            raise SystemExit(f"--classifiers {args.classifiers!r}: --trainer {cfg.TRAINER.NAME} has no generated classifiers to load (MM_CLS_OP only)")
+        if args.classifiers and not osp.isfile(args.classifiers):
+            raise SystemExit(f"--classifiers {args.classifiers!r}: no such file")
+        images = list_predict_images(args.predict)
+    elif args.topk is not None or args.classifiers:
+        raise SystemExit("--topk / --classifiers belong to --predict PATH (the test pass takes TEST.TOPK)")
+    load_classifiers = predict and bool(args.classifiers)
+    if zeroshot or load_classifiers:
+        import copy
+        split_cfg = copy.deepcopy(cfg)
+        split_cfg.DATASET.NUM_SHOTS = max(1, shots)       # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set)
     if zeroshot:
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit(f"--trainer {cfg.TRAINER.NAME} runs in one process: sharding the zero-shot test pass over ranks is not implemented")
@@ -341,11 +422,8 @@ def main(argv=None) -> Dict[str, float]:
             templates.check_dataset(cfg.DATASET.NAME)
         except KeyError as e:
             raise SystemExit(e.args[0]) from None
-        # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set); nothing of the draw is decoded
-        import copy
-        split_cfg = copy.deepcopy(cfg)
-        split_cfg.DATASET.NUM_SHOTS = max(1, shots)
-    else:
+        # (nothing of the few-shot draw is decoded)
+    elif not load_classifiers:
         if osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
             print(f"Oops! The results exist at {cfg.OUTPUT_DIR} (so skip this job)")       # generate_classifier.sh:27-28
             return {}
@@ -365,7 +443,11 @@ def main(argv=None) -> Dict[str, float]:
     if seed >= 0:
         print(f"Setting fixed seed: {seed}")                  # train.py:157-159
         torch.manual_seed(seed)
-    classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, args.test_split, args.exemplar_list)
+    classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if predict else args.test_split, args.exemplar_list)
+    if predict:
+        if k > len(classnames):
+            raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
+        test_items = [(p, 0) for p in images]             # the loader protocol carries a label: a dummy one, never read
 
     # what the loaders need to know of the model is in the weights' shapes: the decode workers start before the engine exists
     clip_sd = checkpoint.load_clip_state_dict(args.clip_weights)
@@ -387,7 +469,7 @@ def main(argv=None) -> Dict[str, float]:
         kw["prompt_learner_state"] = pl_state
     rank, world = (dist.get_rank(), dist.get_world_size()) if not zeroshot and dist.is_available() and dist.is_initialized() else (0, 1)
     loader = _loader_factory(args, cfg, spec.image_resolution, tfm)
-    eval_loader = None if zeroshot else loader(exemplars, batch // shots * shots, rank, world, len(classnames))
+    eval_loader = None if zeroshot or load_classifiers else loader(exemplars, batch // shots * shots, rank, world, len(classnames))
     test_loader = loader(test_items, batch)
     # the decode workers start while the engine takes the weights; on rank 0 one ring (sized for the larger batch) serves both loaders,
     # ranks > 0 never touch the test set: theirs is sized for the exemplar batches alone
@@ -397,7 +479,9 @@ def main(argv=None) -> Dict[str, float]:
     dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
     tr = trainer.build_trainer(cfg, dm, clip_weights=clip_sd, tokenizer=BPETokenizer(args.bpe_path), device=args.device,
                                reserve=(batch, 256, max(1024, len(classnames))), **kw)
-    if not zeroshot:
+    if load_classifiers:
+        tr.model.load_classifiers(args.classifiers)
+    elif not zeroshot:
         # the reference does this inside the first forward (:341-342); up front it keeps the two loaders' statistics apart.  Rank 0's two
         # files are written by a worker thread while the test set runs (CustomCLIP._write_files), joined at the end of test()
         tr.model.forward_prompt(eval_loader, wait_files=False)
@@ -406,11 +490,18 @@ def main(argv=None) -> Dict[str, float]:
                 dist.barrier()
                 dist.destroy_process_group()
             return {}
-    tr.test()
-    results = dict(tr.results)
-    if not zeroshot:
+    if predict:
+        values, indices = tr.predict(test_loader, k)
+        results = {"predictions": ranked_predictions(images, values, indices, classnames)}
+        out_csv = osp.join(cfg.OUTPUT_DIR, "predictions.csv")
+        write_predictions(out_csv, results["predictions"])
+        print(f"=> top-{k} predictions of {len(images):,} images: {out_csv}")
+    else:
+        tr.test()
+        results = dict(tr.results)
+    if eval_loader is not None:
         _report_pipeline(results, "exemplar set", eval_loader)
-    _report_pipeline(results, "test set", test_loader)
+    _report_pipeline(results, "predict set" if predict else "test set", test_loader)
     results["classnames"] = classnames
     if own_group:
         dist.barrier()

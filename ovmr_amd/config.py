@@ -45,6 +45,7 @@ DEFAULTS: Dict[str, Any] = {
     "TRAINER.COCOOP.CTX_INIT": "",
     "TRAINER.COCOOP.PREC": "fp16",
     "TEST.SPLIT": "test",
+    "TEST.TOPK": 1,                                  # Classification.process(mo, gt, topk) (evaluator.py:50): a row is correct when its label is among its k best
 }
 
 # accepted and never read on this path (prefix match on the dotted key)

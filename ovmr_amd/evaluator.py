@@ -29,16 +29,33 @@ class Classification:
     def reset(self):
         # int32 [3][C] = tp, n_pred, n_label, + one slot counting rows whose label is outside [0, C) (include/ovmr_hip.h: ovmr_eval_counts)
         self._counts = torch.zeros(3 * self.num_classes + 1, dtype=torch.int32, device=self.device)
+        self._topk = None                            # the `topk` of this pass, set by its first process()
+        self._hits = None                            # int32 [1], topk > 1: rows whose label is among their k best columns
 
     @torch.no_grad()
-    def process(self, mo: torch.Tensor, gt: torch.Tensor):
+    def process(self, mo: torch.Tensor, gt: torch.Tensor, topk: int = 1):
         """mo: [B, C] model output (fp32 probabilities of CustomCLIP.forward, or fp16 zero-shot logits), gt: [B] labels
-        (evaluator.py:50-67).  One kernel launch on the current stream, no host synchronisation."""
+        (evaluator.py:50-67).  One kernel launch on the current stream, no host synchronisation.  topk > 1 (:56-58): a row counts as
+        correct when its label is among its k best columns (ovmr_topk_rows: one more launch, hits accumulate on the device); the
+        histograms -- macro-F1, the per-class tables -- keep coming from the top-1 prediction, the reference's pred[:, 0] (:64-65).
+        One pass uses one topk."""
         C = self.num_classes
         if mo.dim() != 2 or mo.shape[1] != C or gt.shape[0] != mo.shape[0]:
             raise ValueError(f"outputs {tuple(mo.shape)} / labels {tuple(gt.shape)} do not fit {C} classes")
+        topk = int(topk)
+        if not 1 <= topk <= min(32, C):
+            raise ValueError(f"topk {topk} outside [1, min(32, {C} classes)]")
+        if self._topk is None:
+            self._topk = topk
+            if topk > 1:
+                self._hits = torch.zeros(1, dtype=torch.int32, device=self.device)
+        elif topk != self._topk:
+            raise ValueError(f"process(topk={topk}) in a pass that began with topk={self._topk}: one pass uses one topk (reset() starts the next)")
         if self.device.type == "cpu":
             self._process_host(mo, gt)
+            if topk > 1:
+                order = torch.sort(mo.float(), dim=1, descending=True, stable=True)[1][:, :topk]     # the library's total order
+                self._hits += int((order == gt.long().unsqueeze(1)).any(dim=1).sum())
             return
         from . import runtime
         lib = runtime.load_library()                                      # raises without the HIP library: no fallback for device tensors
@@ -54,6 +71,8 @@ class Classification:
                                   runtime._ptr(gt), mo.shape[0], C, runtime._ptr(self._counts), runtime._stream())
         if rc != 0:
             raise runtime.OvmrError(f"ovmr_eval_counts failed with {rc}")
+        if topk > 1 and mo.shape[0]:
+            runtime.topk_rows(mo, topk, gt, self._hits)
 
     def _process_host(self, mo, gt):
         """The same three histograms for host tensors (mo.max(1)[1]: lowest column on ties)."""
@@ -79,7 +98,8 @@ class Classification:
     def evaluate(self, output_dir: Optional[str] = None) -> "OrderedDict[str, float]":
         tp, n_pred, n_label = (t.double() for t in self.counts())
         total = float(n_label.sum())
-        acc = 100.0 * float(tp.sum()) / max(total, 1.0)
+        correct = int(tp.sum()) if self._hits is None else int(self._hits.cpu()[0])        # evaluator.py:56-60
+        acc = 100.0 * correct / max(total, 1.0)
         precision = torch.where(n_pred > 0, tp / n_pred.clamp(min=1), torch.zeros_like(tp))
         recall = torch.where(n_label > 0, tp / n_label.clamp(min=1), torch.zeros_like(tp))
         f1 = torch.where(precision + recall > 0, 2 * precision * recall / (precision + recall).clamp(min=1e-300),
@@ -90,7 +110,7 @@ class Classification:
         self.per_class_accuracy = (100.0 * recall).tolist()
         self.per_class_f1 = (100.0 * f1).tolist()
         print("=> result\n"
-              f"* total: {int(total):,}\n* correct: {int(tp.sum()):,}\n* accuracy: {acc:.1f}%\n"
+              f"* total: {int(total):,}\n* correct: {correct:,}\n* accuracy: {acc:.1f}%\n"
               f"* error: {100.0 - acc:.1f}%\n* macro_f1: {macro_f1:.1f}%")       # the format parse_test_res.py greps for
         if output_dir:                                                    # evaluator.py:84-113 (csv module formats)
             import csv

@@ -332,6 +332,14 @@ class _TwoInFlight:
                 t.set_option(k, v)
         return _ensure_final(t)
 
+    @staticmethod
+    def _topk(out, k: int):
+        """(values fp32 [B, k], indices int64 [B, k]) of a [B, C] output: ovmr_topk_rows on the current stream, the library's total
+        order (include/ovmr_hip.h: larger first, ties to the lower column, NaN largest)."""
+        from . import runtime
+        values, indices = runtime.topk_rows(out, k)
+        return values, indices.long()
+
     def _run_batches(self, batches, overlap, stable_inputs):
         cur = torch.cuda.current_stream(self.device)
 
@@ -778,6 +786,44 @@ class CustomCLIP(_TwoInFlight):
         out.record_stream(st)
         return out
 
+    # ------------------------------------------------------------------ ranked prediction (no counterpart in the reference's API)
+    @torch.no_grad()
+    def predict_topk(self, image, k: int, eval_set_loader=None):
+        """forward(image) followed by ovmr_topk_rows on its output, on the same stream: (values fp32 [B, k], indices int64 [B, k]), the k
+        most probable classes of every image, best first."""
+        return self._topk(self.forward(image, eval_set_loader=eval_set_loader), k)
+
+    @torch.no_grad()
+    def predict_topk_batches(self, batches: Iterable, k: int, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
+        """predict_topk for every image batch, in order, over forward_batches (two batches in flight): one (values, indices) pair per batch."""
+        for out in self.forward_batches(batches, eval_set_loader=eval_set_loader, overlap=overlap, stable_inputs=stable_inputs):
+            yield self._topk(out, k)
+
+    @torch.no_grad()
+    def load_classifiers(self, path: str):
+        """Installs the classifiers of a mm_classifiers.pt written by forward_prompt (:276-285: text / vision / multimodal classifier
+        [C, embed_dim] and fusion_weight [C, 3], all fp32; the three classifiers hold fp16 values, so .half() is exact) as forward_prompt
+        leaves them: a later forward generates nothing.  Both handles of forward_batches read them from here.  visual_tokens.pt is not
+        needed for inference and is not read.  Returns (mm_classifier, visual_classifer, fusion_weight)."""
+        from . import checkpoint
+        obj = checkpoint._torch_load(path)
+        keys = ("text_classifier", "vision_classifier", "mm_classifier", "fusion_weight")
+        if not isinstance(obj, dict) or any(not isinstance(obj.get(k), torch.Tensor) for k in keys):
+            raise ValueError(f'"{path}" is not a mm_classifiers.pt: it must hold the tensors {keys}')
+        C, D = len(self.tokenized_prompts), self.engine.spec.embed_dim
+        for k in keys:
+            want = (C, 3) if k == "fusion_weight" else (C, D)
+            if tuple(obj[k].shape) != want:
+                raise ValueError(f'"{path}": {k} is {tuple(obj[k].shape)}, this model has {C} classes of width {D} (expected {want})')
+        self.wait_files()
+        dev = self.device
+        t, v, mm = (obj[k].to(dev).half().contiguous() for k in keys[:3])
+        self.zero_shot_classifier = self.prompt_learner.zero_shot_classifier = t
+        self.visual_classifer, self.mm_classifier = v, mm
+        self.fusion_weight = obj["fusion_weight"].to(dev).float().contiguous()
+        self.inference_text_initialized = torch.ones(C, dtype=torch.int32, device=dev)
+        return self.mm_classifier, self.visual_classifer, self.fusion_weight
+
     @torch.no_grad()
     def forward_batches(self, batches: Iterable, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
         """The model calls of the evaluation loop (dassl's test(): one forward per test batch, trainers' model_inference),
@@ -850,6 +896,18 @@ class ZeroshotCLIP(_TwoInFlight):
 
     def model_inference(self, image):
         return self._forward_on(self.engine, image)
+
+    # ranked prediction (no counterpart in the reference's API); eval_set_loader is accepted for CustomCLIP's signature and not read
+    @torch.no_grad()
+    def predict_topk(self, image, k: int, eval_set_loader=None):
+        """model_inference(image) followed by ovmr_topk_rows on its logits, on the same stream: (values fp32 [B, k], indices int64 [B, k])."""
+        return self._topk(self.model_inference(image), k)
+
+    @torch.no_grad()
+    def predict_topk_batches(self, batches: Iterable, k: int, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
+        """predict_topk for every image batch, in order, over inference_batches (two batches in flight)."""
+        for out in self.inference_batches(batches, overlap=overlap, stable_inputs=stable_inputs):
+            yield self._topk(out, k)
 
     @torch.no_grad()
     def inference_batches(self, batches: Iterable, overlap: Optional[bool] = None, stable_inputs: bool = False):

@@ -65,6 +65,7 @@ SIGNATURES = {
     "ovmr_pack_rows": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "ovmr_unpack_rows": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "ovmr_eval_counts": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, c_p, c_p]),
+    "ovmr_topk_rows": (c_i, [c_p, c_i, ctypes.c_long, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "ovmr_head_plan": (c_i, [c_p, c_i, c_i]),
     "ovmr_zeroshot_logits": (c_i, [c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
     "ovmr_logit_scale": (ctypes.c_float, [c_p]),
@@ -117,6 +118,36 @@ def _stream():
 
 class OvmrError(RuntimeError):
     pass
+
+
+def topk_rows(mo: torch.Tensor, k: int, labels: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None):
+    """ovmr_topk_rows on the current stream: mo [B, C] fp16 / fp32 on the GPU (rows may be strided: stride(1) == 1, stride(0) >= C, no
+    copy) -> (values fp32 [B, k], indices int32 [B, k]), best first in the library's total order (include/ovmr_hip.h).  labels int64 [B]
+    and hits int32 [1] (both on the GPU, together or not at all): hits[0] += rows whose label is among their k columns."""
+    lib = load_library()
+    if mo.dim() != 2 or not mo.is_cuda or mo.dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"topk_rows takes a [B, C] fp16 / fp32 device tensor, got {tuple(mo.shape)} {mo.dtype} on {mo.device}")
+    B, C = mo.shape
+    if B > 1 and mo.stride(1) == 1 and mo.stride(0) < C:
+        mo = mo.contiguous()                         # (an expanded row: not a row view of a matrix)
+    elif C > 1 and mo.stride(1) != 1:
+        mo = mo.contiguous()
+    if (labels is None) != (hits is None):
+        raise ValueError("topk_rows takes labels and hits together or not at all")
+    if labels is not None:
+        if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (B,)):
+            raise ValueError("labels must be a contiguous int64 [B] device tensor")
+        if not (hits.is_cuda and hits.dtype == torch.int32 and hits.numel() >= 1):
+            raise ValueError("hits must be an int32 device tensor")
+    with torch.cuda.device(mo.device):
+        values = torch.empty((B, int(k)), dtype=torch.float32, device=mo.device)
+        indices = torch.empty((B, int(k)), dtype=torch.int32, device=mo.device)
+        ld = mo.stride(0) if B > 1 else max(C, mo.stride(0))
+        rc = lib.ovmr_topk_rows(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, B, C, int(k), _ptr(values), _ptr(indices),
+                                _ptr(labels), _ptr(hits), ctypes.c_void_p(torch.cuda.current_stream(mo.device).cuda_stream))
+    if rc != 0:
+        raise OvmrError(f"ovmr_topk_rows failed with {rc} (B = {B}, C = {C}, k = {k})")
+    return values, indices
 
 
 class Engine:

@@ -121,11 +121,29 @@ class _EvalTrainer:
                 labels.append(label)
                 yield input
 
+        topk = int(getattr(getattr(self.cfg, "TEST", None), "TOPK", 1))          # evaluator.process(mo, gt, topk), evaluator.py:50
+        kw = {"topk": topk} if topk != 1 else {}
         for output in self.outputs(inputs()):
-            self.evaluator.process(output, labels.popleft())
+            self.evaluator.process(output, labels.popleft(), **kw)
         self.after_test()
         self.results = self.evaluator.evaluate(self.output_dir or None)
         return list(self.results.values())[0]
+
+    def ranked(self, inputs, k):
+        """predict_topk for every input batch, in order: (values fp32 [B, k], indices int64 [B, k]) pairs."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def predict(self, data_loader, k: int = 5):
+        """Ranked prediction on unlabelled images (no counterpart in the reference): the k best classes of every image of `data_loader`
+        (the loader protocol's batches; their labels are not read), best first, through the model's predict_topk_batches -- two batches
+        in flight, ovmr_topk_rows on each output, ONE device-to-host copy at the end.  Returns (values fp32 [N, k], indices int64 [N, k])
+        on the host, rows in loader order."""
+        pairs = list(self.ranked((self.parse_batch_test(batch)[0] for batch in data_loader), k))
+        self.after_test()
+        if not pairs:
+            return torch.zeros((0, k), dtype=torch.float32), torch.zeros((0, k), dtype=torch.int64)
+        return torch.cat([v for v, _ in pairs]).cpu(), torch.cat([i for _, i in pairs]).cpu()
 
     def forward_backward(self, batch):
         raise NotImplementedError(self.NOT_TRAINED)
@@ -180,6 +198,9 @@ class MM_CLS_OP(_EvalTrainer):
     def outputs(self, inputs):
         return self.model.forward_batches(inputs, eval_set_loader=self.eval_set_loader)
 
+    def ranked(self, inputs, k):
+        return self.model.predict_topk_batches(inputs, k, eval_set_loader=self.eval_set_loader)
+
     def after_test(self):
         self.model.wait_files()                      # mm_classifiers.pt / visual_tokens.pt were written while the test set ran
 
@@ -216,6 +237,9 @@ class ZeroshotCLIP(_EvalTrainer):
 
     def outputs(self, inputs):
         return self.model.inference_batches(inputs)
+
+    def ranked(self, inputs, k):
+        return self.model.predict_topk_batches(inputs, k)
 
 
 class ZeroshotCLIP2(ZeroshotCLIP):
