@@ -69,10 +69,14 @@ const char* ovmr_version(void);
  *   (at most one round -- 256 -- of 64 x 64 tiles: the text tower on a few dozen prompts, CLS-row chains), the 64 x 64 kernel that splits K
  *   over its waves; 7 = 8 without that kernel (A/B); 6 = the 256-row tiles with the double-buffered K loop; 9 = the 64 x 64 split-K kernel wherever it takes the shape (tests);
  *   0 = the 128x128 register-staged kernel everywhere (LayerNorm-folding and fused-argmax launches still take the tile kernel).
- * "attn" (default 3): 3 = single-pass persistent kernel where the shape is its own (non-causal, 192 < L <= 208), the 32x32x16 flash
- *   kernel (= 5) for non-causal L >= 256 (ViT-L), else as 1; 5 = that kernel where it applies, else as 1;
- *   1 = flash-style LDS-DMA kernel for L >= 128, else as 0; 0 = the plain flash-style kernel.  Every variant but 0 runs sequences of at
- *   most 32 tokens (truncated text prompts) on the one-wave-per-(sequence, head) kernel, bit-equal to 0.
+ * "attn" (default 3): which fp16 attention kernel a launch of L tokens and Lq <= L query rows runs (route() in csrc/attention.hip, exported
+ *   as ovmr_debug_attention_route; the first line that applies):
+ *     every value >= 1, Lq == L <= 32 (truncated text prompts)      the one-wave-per-(sequence, head) kernel, bit-equal to variant 0;
+ *     3, no mask, Lq == L, 192 < L <= 208 (ViT-B/16)                the single-pass persistent kernel;
+ *     3 or 5, no mask, L >= 256, Lq >= 32 (ViT-L)                   the 32x32x16 flash kernel;
+ *     1, 3 or 5, L >= 128                                           the flash-style LDS-DMA kernel;
+ *     otherwise, and 0 everywhere                                   the plain flash-style kernel.
+ *   4, the number of a retired kernel, is an alias of 3.
  * "ln_fold" (default 1): ln_1 / ln_2 of the fp16 towers are folded into the consuming GEMM where the shape allows
  *   (width % 256 == 0 and >= 256 token rows); 0 runs the separate LayerNorm kernel everywhere.
  * "xval_fused" (default 1): ovmr_xval_counts takes the row argmax inside the logits GEMM's epilogue (the [R, C] logits are never
@@ -325,6 +329,9 @@ int ovmr_debug_gemm_strided(int variant, const void* A, int lda, const void* W, 
  * out [B*Lq, H*64], row b*Lq + q.  Lq > L returns OVMR_E_SHAPE. */
 int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L, int Lq, int H, int causal,
                            ovmr_stream stream);
+/* The kernel an fp16 attention launch under option "attn" = variant runs (no launch, no GPU): 0 plain flash-style, 1 flash-style
+ * LDS-DMA, 2 short sequences, 3 single-pass, 5 32x32x16 flash. */
+int ovmr_debug_attention_route(int variant, int L, int Lq, int causal);
 
 #ifdef __cplusplus
 }

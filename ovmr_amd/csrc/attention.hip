@@ -12,7 +12,8 @@
 //   * V is transposed while it is staged ([d][key] rows of 136 B, conflict-free ds_read_b64);
 //     K rows are XOR-swizzled 128-byte rows (conflict-free ds_read_b128).
 // fp32 kernel (aggregator, L = n_ctx + shots <= 128): one thread per query row, K/V in LDS.
-#include "common.h"
+#include "attn_common.h"
+#include "../../include/ovmr_hip.h"
 
 namespace {
 
@@ -101,17 +102,7 @@ __global__ __launch_bounds__(256) void attn_f16_v0(const half_t* __restrict__ qk
             mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
             const float m_new = fmaxf(m_run, mx);
             const float alpha = exp2f(m_run - m_new);
-            float psum = 0.f;
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float p = exp2f(s[nt][r] - m_new);
-                    s[nt][r] = p;
-                    psum += p;
-                }
-            psum += __shfl_xor(psum, 16, 64);
-            psum += __shfl_xor(psum, 32, 64);
+            const float psum = attn::exp_sum<4>(s, m_new);
             l_run = l_run * alpha + psum;
             m_run = m_new;
 #pragma unroll
@@ -137,12 +128,7 @@ __global__ __launch_bounds__(256) void attn_f16_v0(const half_t* __restrict__ qk
     }
     if (active && q < Lq) {
         const float inv = 1.0f / l_run;
-        half_t* op = out + ((long)b * Lq + q) * D + h * 64 + fg * 4;
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            half4_t w = {(half_t)(o[dt][0] * inv), (half_t)(o[dt][1] * inv), (half_t)(o[dt][2] * inv), (half_t)(o[dt][3] * inv)};
-            *(half4_t*)(op + dt * 16) = w;
-        }
+        attn::store_row4(out + ((long)b * Lq + q) * D + h * 64 + fg * 4, o, inv);
     }
 }
 
@@ -191,11 +177,23 @@ __global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ 
         *(float4_t*)(op + c * 4) = (float4_t){o[c * 4] * inv, o[c * 4 + 1] * inv, o[c * 4 + 2] * inv, o[c * 4 + 3] * inv};
 }
 
+// Which kernel a launch of `variant` runs: 0 attn_f16_v0, 1 attn_f16_v1, 2 attn_f16_short, 3 attn_f16_v3, 5 attn_f16_v5
+// (include/ovmr_hip.h, "attn").  Every kernel computes the same values: a mistake here costs time, not correctness, and only
+// tests/test_attn_route_cpu.py would see it.
+enum Kernel { K_V0 = 0, K_V1 = 1, K_SHORT = 2, K_V3 = 3, K_V5 = 5 };
+
+Kernel route(int variant, int L, int Lq, int causal) {
+    if (variant >= 1 && attn::short_takes(L, Lq)) return K_SHORT;
+    if (variant == 4) variant = 3;    // 4: the number of a retired kernel, an alias of 3 so that the option value keeps its meaning
+    if (variant == 3 && attn::v3_takes(L, Lq, causal)) return K_V3;
+    if ((variant == 3 || variant == 5) && attn::v5_takes(L, Lq, causal)) return K_V5;
+    if ((variant == 1 || variant == 3 || variant == 5) && attn::v1_wanted(L)) return K_V1;
+    return K_V0;
+}
+
 }  // namespace
 
-int launch_attention_f16_v1(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s);  // attention_v1.hip
-int launch_attention_f16_v3(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s);  // attention_v3.hip
-int launch_attention_f16_v5(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s);  // attention_v5.hip
+extern "C" int ovmr_debug_attention_route(int variant, int L, int Lq, int causal) { return route(variant, L, Lq, causal); }
 
 int launch_attention_f16(const half_t* qkv, half_t* out, int B, int L, int H, int causal, int variant, hipStream_t s) {
     return launch_attention_f16_q(qkv, out, B, L, L, H, causal, variant, s);
@@ -204,33 +202,22 @@ int launch_attention_f16(const half_t* qkv, half_t* out, int B, int L, int H, in
 int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, int variant, hipStream_t s) {
     if (B <= 0 || L <= 0 || Lq <= 0) return 0;
     if (Lq > L) return -2;
-    if (variant >= 1 && Lq == L && L <= 32) {   // short sequences (text prompts truncated to their last needed row): one wave per (sequence, head)
+    switch (route(variant, L, Lq, causal)) {
+    case K_SHORT: {
         const long row0 = 0;
-        const int rc = launch_attention_f16_short(qkv, out, 1, &B, &L, &row0, H, causal, s);
-        if (rc != -100) return rc;
+        return launch_attention_f16_short(qkv, out, 1, &B, &L, &row0, H, causal, s);
     }
-    if (variant == 4) variant = 3;    // 4: the number of a retired kernel, an alias of 3 so that the option value keeps its meaning
-    if (variant == 3) {               // single-pass kernel for the ViT-B/16 image shape; long sequences (ViT-L: L = 257 / 577) as variant 5
-        int rc = launch_attention_f16_v3(qkv, out, B, L, Lq, H, causal, s);
-        if (rc != -100) return rc;
-        rc = launch_attention_f16_v5(qkv, out, B, L, Lq, H, causal, s);
-        if (rc != -100) return rc;
-        variant = 1;
-    }
-    if (variant == 5) {               // 32x32x16 flash kernel (non-causal, L >= 256); other shapes as variant 1
-        const int rc = launch_attention_f16_v5(qkv, out, B, L, Lq, H, causal, s);
-        if (rc != -100) return rc;
-        variant = 1;
-    }
-    if (variant == 1 && L >= 128) {   // short (text) sequences: one key block, the plain kernel is faster (tools/attn_bench.py)
-        int rc = launch_attention_f16_v1(qkv, out, B, L, Lq, H, causal, s);
-        if (rc != -100) return rc;
+    case K_V3:
+        if (const int rc = attn::launch_attention_f16_v3(qkv, out, B, L, H, s); rc != -100) return rc;
+        [[fallthrough]];              // -100: no slot for this device in the launcher's table; the launch runs as variant 1
+    case K_V1: return attn::launch_attention_f16_v1(qkv, out, B, L, Lq, H, causal, s);
+    case K_V5: return attn::launch_attention_f16_v5(qkv, out, B, L, Lq, H, s);
+    case K_V0: break;
     }
     const int nT = (Lq + 15) / 16, nWG = (nT + 3) / 4;
-    const float sl2e = 0.125f * 1.4426950408889634f;   // hd^-0.5 * log2(e), hd = 64
     const dim3 grid((unsigned)((long)B * H * nWG));
-    if (causal) hipLaunchKernelGGL(attn_f16_v0<true>, grid, dim3(256), 0, s, qkv, out, L, Lq, H, nT, nWG, sl2e);
-    else hipLaunchKernelGGL(attn_f16_v0<false>, grid, dim3(256), 0, s, qkv, out, L, Lq, H, nT, nWG, sl2e);
+    if (causal) hipLaunchKernelGGL(attn_f16_v0<true>, grid, dim3(256), 0, s, qkv, out, L, Lq, H, nT, nWG, attn::SCALE_LOG2E);
+    else hipLaunchKernelGGL(attn_f16_v0<false>, grid, dim3(256), 0, s, qkv, out, L, Lq, H, nT, nWG, attn::SCALE_LOG2E);
     return (int)hipGetLastError();
 }
 

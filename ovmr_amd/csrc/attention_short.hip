@@ -7,9 +7,10 @@
 //   * ONE WAVE per (sequence, head), four per workgroup, all groups of the pass in one grid (group table by value);
 //   * same arithmetic as attn_f16_v0 with one key block: S^T = K Q^T as 16x16x32 MFMAs (K and Q fragments straight from global memory:
 //     16 bytes per lane, the operands of these passes are cache resident), masked, exact row maximum, p = exp2(s - m) in fp32, row sum
-//     in fp32, P rounded to fp16 as the B operand of O^T = V^T P^T, V transposed through a per-wave LDS tile ([d][key] rows of 72 B);
+//     in fp32 (that softmax step is attn_f16_v0's own code, attn_common.h: the two are bit-equal by construction), P rounded to fp16 as
+//     the B operand of O^T = V^T P^T, V transposed through a per-wave LDS tile ([d][key] rows of 72 B);
 //   * L <= 16: one query tile; 16 < L <= 32: two, sharing the K fragments and the V^T tile.
-#include "common.h"
+#include "attn_common.h"
 
 struct AttnShortGroups {       // up to 4 groups of sequences in one [rows, 3 H 64] qkv buffer
     int n;                     // groups
@@ -97,17 +98,7 @@ __global__ __launch_bounds__(256) void attn_f16_short(const half_t* __restrict__
             }
         mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float psum = 0.f;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float p = exp2f(s[nt][r] - mx);
-                s[nt][r] = p;
-                psum += p;
-            }
-        psum += __shfl_xor(psum, 16, 64);
-        psum += __shfl_xor(psum, 32, 64);
+        const float psum = attn::exp_sum<2>(s, mx);
         half8_t pf;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -124,39 +115,32 @@ __global__ __launch_bounds__(256) void attn_f16_short(const half_t* __restrict__
             const half8_t vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
             o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf, (float4_t){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         }
-        if (q < L) {
-            const float inv = 1.0f / psum;
-            half_t* op = out + (row_base + q) * D + h * 64 + fg * 4;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const half4_t w = {(half_t)(o[dt][0] * inv), (half_t)(o[dt][1] * inv), (half_t)(o[dt][2] * inv), (half_t)(o[dt][3] * inv)};
-                *(half4_t*)(op + dt * 16) = w;
-            }
-        }
+        if (q < L) attn::store_row4(out + (row_base + q) * D + h * 64 + fg * 4, o, 1.0f / psum);
     }
 }
 
 }  // namespace
 
-// Every group: sequences of L[i] <= 32 tokens, rows row0[i] .. of qkv [rows, 3 H 64]; out [rows, H 64].  -100: a group is too long.
+// Every group: sequences of L[i] <= 32 tokens, rows row0[i] .. of qkv [rows, 3 H 64]; out [rows, H 64].  -100: a group table this kernel
+// cannot take (more than 4 groups, a group longer than 32 tokens, a first row past 2^31): the multi-group caller launches group by group.
 int launch_attention_f16_short(const half_t* qkv, half_t* out, int n_groups, const int* nseq, const int* L, const long* row0, int H,
                                int causal, hipStream_t s) {
-    if (n_groups < 1 || n_groups > 4) return -100;
+    bool fits = n_groups >= 1 && n_groups <= 4;
+    for (int i = 0; fits && i < n_groups; ++i) fits = L[i] >= 1 && L[i] <= 32 && row0[i] <= 0x7fffffffL;
+    if (!fits) return -100;
     AttnShortGroups g;
     g.n = n_groups;
     g.pair0[0] = 0;
     for (int i = 0; i < 4; ++i) {
         const bool live = i < n_groups;
-        if (live && (L[i] < 1 || L[i] > 32 || row0[i] > 0x7fffffffL)) return -100;
         g.L[i] = live ? L[i] : 1;
         g.nseq[i] = live ? nseq[i] : 0;
         g.row0[i] = live ? (int)row0[i] : 0;
         g.pair0[i + 1] = g.pair0[i] + g.nseq[i] * H;
     }
     if (g.pair0[n_groups] == 0) return 0;
-    const float sl2e = 0.125f * 1.4426950408889634f;       // hd^-0.5 * log2(e), hd = 64
     const dim3 grid((unsigned)((g.pair0[n_groups] + 3) / 4));
-    if (causal) hipLaunchKernelGGL(attn_f16_short<true>, grid, dim3(256), 0, s, qkv, out, g, H, sl2e);
-    else hipLaunchKernelGGL(attn_f16_short<false>, grid, dim3(256), 0, s, qkv, out, g, H, sl2e);
+    if (causal) hipLaunchKernelGGL(attn_f16_short<true>, grid, dim3(256), 0, s, qkv, out, g, H, attn::SCALE_LOG2E);
+    else hipLaunchKernelGGL(attn_f16_short<false>, grid, dim3(256), 0, s, qkv, out, g, H, attn::SCALE_LOG2E);
     return (int)hipGetLastError();
 }

@@ -16,33 +16,15 @@
 //   * two 16-row query tiles per wave, 4 waves (8 tiles) per workgroup, both tiles of a wave sharing every K / V fragment
 //     read from LDS; <= 128 VGPRs, i.e. 4 waves per SIMD (3 waves/SIMD: 233 us instead of 193 at B = 512); the workgroups
 //     of a head run on one XCD; 16 tiles / 7 waves per workgroup (K/V read once) measured 198 us, 4 tiles 321 us.
-#include "common.h"
+#include "attn_common.h"
 
 #include <algorithm>
 
 namespace {
 
 constexpr int KB1 = 64;
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef short short4v __attribute__((__vector_size__(8)));
-
-__device__ __forceinline__ half4_t tr_read(const half_t* p) {
-    short4v r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)p);
-    return __builtin_bit_cast(half4_t, r);
-}
-
-// max over the four lanes {l, l^16, l^32, l^48} that hold one query row's scores, without the LDS crossbar: v_permlane16_swap /
-// v_permlane32_swap exchange 16- / 32-lane halves between two registers, so with both operands = x the two results hold
-// x of this lane and x of the partner lane (ds_bpermute: two ~100-cycle LDS round trips in the max -> exp dependency chain).
-__device__ __forceinline__ float row_max4(float x) {
-    const unsigned u = __builtin_bit_cast(unsigned, x);
-    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    x = fmaxf(__builtin_bit_cast(float, (unsigned)a[0]), __builtin_bit_cast(float, (unsigned)a[1]));
-    const unsigned w = __builtin_bit_cast(unsigned, x);
-    auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-    return fmaxf(__builtin_bit_cast(float, (unsigned)b[0]), __builtin_bit_cast(float, (unsigned)b[1]));
-}
+using attn::row_max4;
+using attn::tr_read;
 
 template <bool CAUSAL>
 __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__ qkv, half_t* __restrict__ out,
@@ -53,9 +35,7 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fg = lane >> 4;
     const int D = H * 64, ld = 3 * D;
-    // the workgroups of one (sequence, head) get block ids congruent mod 8: same XCD, so the second one finds K / V in that L2
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int wg = slot % nWG, bh = (slot / nWG) * 8 + xcd;
+    const auto [wg, bh] = attn::xcd_decode(blockIdx.x, nWG);   // the workgroups of one (sequence, head) on one XCD
     if (bh >= nBH) return;
     const int h = bh % H, b = bh / H;
     // query tiles of this workgroup: full groups of 2 * nW first, the remainder in the last one, and wave w takes tiles 2w
@@ -78,12 +58,9 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) qf[u][ks] = *(const half8_t*)(base + (long)qc * ld + ks * 32 + fg * 8);
     }
-    // m_run: the reference maximum the exponentials are taken against (scaled domain).  It only moves when a block's
-    // maximum exceeds it by more than 8 (a factor 256 in p, harmless for fp16 P and fp32 accumulators): then o and the row
-    // sums are rescaled.  After the first key block that is rare, so the 16 packed multiplies and the exp of the usual
-    // every-block rescale disappear.  The row sums are accumulated by the matrix pipe (ones . P^T, accumulator ol), not by
-    // 32 VALU adds and two cross-lane shuffles per tile: the VALU issue port is what bounds this kernel (75 % busy,
-    // profiles/r01g_pmc_attn.json), the MFMA pipe is not.
+    // m_run: the lazily moved reference maximum of the exponentials (attn::lazy_reference).  The row sums are accumulated by the
+    // matrix pipe (ones . P^T, accumulator ol), not by 32 VALU adds and two cross-lane shuffles per tile: the VALU issue port is
+    // what bounds this kernel (75 % busy, profiles/r01g_pmc_attn.json), the MFMA pipe is not.
     float m_run[2] = {-INFINITY, -INFINITY};
     float4_t ol[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
     half8_t ones;
@@ -94,7 +71,6 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
     for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[u][i] = (float4_t){0.f, 0.f, 0.f, 0.f};
-
     // staging: 16 LDS-DMA instructions per block (8 K + 8 V) dealt round-robin to the waves; one instruction = 8 rows x 128 B
     const int srow = lane >> 3, schunk = ((lane & 7) ^ srow) * 8;
     auto stage = [&](int buf, int k0) {
@@ -102,8 +78,8 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
         for (int ins = wave; ins < 16; ins += nW) {       // 0..7: K rows, 8..15: V rows
             const int isv = ins >> 3, r0 = (ins & 7) * 8;
             const int kc = min(k0 + r0 + srow, L - 1);
-            __builtin_amdgcn_global_load_lds((gptr_t)(base + (1 + isv) * D + (long)kc * ld + schunk),
-                                             (lptr_t)(dst + isv * (KB1 * 64) + r0 * 64), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((attn::gptr_t)(base + (1 + isv) * D + (long)kc * ld + schunk),
+                                             (attn::lptr_t)(dst + isv * (KB1 * 64) + r0 * 64), 16, 0, 0);
         }
     };
 
@@ -180,15 +156,11 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[u][nt][r]);
             mx = row_max4(mx);
-            const float mxs = mx * scale_log2e;
-            if (__builtin_amdgcn_ballot_w64(mxs > m_run[u] + 8.0f) != 0) {     // wave-uniform: some row needs a new reference
-                const float m_new = fmaxf(m_run[u], mxs);
-                const float alpha = __builtin_amdgcn_exp2f(m_run[u] - m_new);   // raw v_exp_f32: arguments are <= 0 (first block: -inf)
-                m_run[u] = m_new;
+            attn::lazy_reference(mx * scale_log2e, m_run[u], [&](float alpha) {
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) o[u][dt] *= alpha;
                 ol[u] *= alpha;
-            }
+            });
             const float m_ref = m_run[u];
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
@@ -206,12 +178,10 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
             if (s2 >= nsv) continue;
-            // V^T fragment through the transposing read: lane (fr, fg) addresses key row kr, 4 d-columns
-            const int kr = s2 * 32 + fg * 4 + (fr >> 2);
+            const int kr = attn::vt_row(s2 * 32, fr, fg);      // V^T fragment through the transposing read
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                const int c = dt * 2 + ((fr & 3) >> 1);
-                const int off = (((c ^ (kr & 7)) << 3) + (fr & 1) * 4);      // halves; (kr+16)&7 == kr&7
+                const int off = attn::vt_col(kr, dt, fr);
                 half4_t v0 = tr_read(sV + kr * 64 + off);
                 half4_t v1 = tr_read(sV + (kr + 16) * 64 + off);
                 half8_t vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
@@ -248,26 +218,20 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
 #pragma unroll
             for (int r = 0; r < 4; ++r) s1[r] = (r < thr) ? s1[r] : -INFINITY;
             const float mx = row_max4(fmaxf(fmaxf(s1[0], s1[1]), fmaxf(s1[2], s1[3])));
-            const float mxs = mx * scale_log2e;
-            if (__builtin_amdgcn_ballot_w64(mxs > m_run[u] + 8.0f) != 0) {
-                const float m_new = fmaxf(m_run[u], mxs);
-                const float alpha = __builtin_amdgcn_exp2f(m_run[u] - m_new);
-                m_run[u] = m_new;
+            attn::lazy_reference(mx * scale_log2e, m_run[u], [&](float alpha) {
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) o[u][dt] *= alpha;
                 ol[u] *= alpha;
-            }
+            });
             const float m_ref = m_run[u];
 #pragma unroll
             for (int r = 0; r < 4; ++r) s1[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[r], scale_log2e, -m_ref));
             pt[u] = (half8_t){(half_t)s1[0], (half_t)s1[1], (half_t)s1[2], (half_t)s1[3], (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
         }
-        const int kr = fg * 4 + (fr >> 2);
+        const int kr = attn::vt_row(0, fr, fg);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            const int c = dt * 2 + ((fr & 3) >> 1);
-            const int off = (((c ^ (kr & 7)) << 3) + (fr & 1) * 4);
-            const half4_t v0 = tr_read(sV + kr * 64 + off);
+            const half4_t v0 = tr_read(sV + kr * 64 + attn::vt_col(kr, dt, fr));
             const half8_t vf = {v0[0], v0[1], v0[2], v0[3], (half_t)0.f, (half_t)0.f, (half_t)0.f, (half_t)0.f};
 #pragma unroll
             for (int u = 0; u < 2; ++u) o[u][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pt[u], o[u][dt], 0, 0, 0);
@@ -279,28 +243,21 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
     for (int u = 0; u < 2; ++u) {
         if (act[u] && qrow[u] < Lq) {
             const float inv = 1.0f / ol[u][0];            // every d-row of ones . P^T holds the row sum of this lane's query
-            half_t* op = out + ((long)b * Lq + qrow[u]) * D + h * 64 + fg * 4;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                half4_t w = {(half_t)(o[u][dt][0] * inv), (half_t)(o[u][dt][1] * inv), (half_t)(o[u][dt][2] * inv),
-                             (half_t)(o[u][dt][3] * inv)};
-                *(half4_t*)(op + dt * 16) = w;
-            }
+            attn::store_row4(out + ((long)b * Lq + qrow[u]) * D + h * 64 + fg * 4, o[u], inv);
         }
     }
 }
 
 }  // namespace
 
-int launch_attention_f16_v1(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s) {
+int attn::launch_attention_f16_v1(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s) {
     const int tpw = 8;                                     // query tiles per workgroup: 8 (4 waves x 2 tiles) measured best: 16 -> 198 us, 8 -> 193 us, 4 -> 321 us at B = 512
     const int nT = (Lq + 15) / 16, nWG = (nT + tpw - 1) / tpw;
     const int per = (nT + nWG - 1) / nWG;                  // most tiles any workgroup gets
     const dim3 block(64 * std::max(4, (per + 1) / 2));      // at least 4 waves: the spare ones only help staging K / V
-    const float sl2e = 0.125f * 1.4426950408889634f;
     const int nBH = B * H;
-    const dim3 grid((unsigned)((long)((nBH + 7) / 8) * 8 * nWG));
-    if (causal) hipLaunchKernelGGL(attn_f16_v1<true>, grid, block, 0, s, qkv, out, L, Lq, H, nT, nWG, nBH, sl2e);
-    else hipLaunchKernelGGL(attn_f16_v1<false>, grid, block, 0, s, qkv, out, L, Lq, H, nT, nWG, nBH, sl2e);
+    const dim3 grid(attn::xcd_grid(nBH, nWG));
+    if (causal) hipLaunchKernelGGL(attn_f16_v1<true>, grid, block, 0, s, qkv, out, L, Lq, H, nT, nWG, nBH, attn::SCALE_LOG2E);
+    else hipLaunchKernelGGL(attn_f16_v1<false>, grid, block, 0, s, qkv, out, L, Lq, H, nT, nWG, nBH, attn::SCALE_LOG2E);
     return (int)hipGetLastError();
 }

@@ -23,7 +23,7 @@
 // 64 %, 28 % of the wave cycles in s_waitcnt / barriers); shader-clock stamps showed where a block goes, and a kernel with two tiles per
 // wave at two waves per SIMD that fewer, fatter waves lose (HISTORY.md, round 3): with 124 VGPRs and one tile per wave the kernel lives on
 // occupancy -- a fourth wave per SIMD (32 KiB ring) beat a second block in flight (48 KiB ring, 3 waves).
-#include "common.h"
+#include "attn_common.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -31,29 +31,12 @@
 namespace {
 
 typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-typedef short short4v __attribute__((__vector_size__(8)));
 
 constexpr int KB5 = 64;
 constexpr int STAGES5 = 2;                              // LDS ring depth
 constexpr int STAGE5 = 2 * KB5 * 64;                    // halves per stage: 64 K rows, then 64 V rows
 
-// LDS-DMA from inline asm (M0 = LDS byte address of the wave's 1 KiB piece, saved / restored inside the statement), as in
-// attention_v3.hip: with the builtin hipcc puts an s_waitcnt vmcnt(0) in front of the first transposing V read of every key block
-// (seen in the ISA of this kernel too), which drains the two blocks in flight.  Ordering is by hand: counted wait + barrier at the
-// top of the block loop.  (Waits hipcc computes for its own loads ignore these DMAs and can therefore only be too strict.)
-// (scalar base + 32-bit per-lane byte offset: the block walk is one scalar add, the per-lane offsets never change)
-__device__ __forceinline__ void glds16_asm5(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-__device__ __forceinline__ half4_t tr_read5(const half_t* p) {
-    short4v r = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4v*)p);
-    return __builtin_bit_cast(half4_t, r);
-}
+using attn::tr_read;
 
 // Ring depth and row sums: two LDS stages, row sums as 32 v_add_f32 per block.  Measured against a three-stage ring and row sums from the
 // matrix pipe (ones . P^T, 16 more registers) (r03p; 64 x 16 x 577 / 128 x 16 x 577 / 256 x 16 x 257, us): <3, MFMA> 142 / 276 / 168,
@@ -70,9 +53,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, h = lane >> 5;
     const int D = H * 64, ld = 3 * D;
-    // the workgroups of one (sequence, head) get block ids congruent mod 8: one XCD, its L2 serves their K / V re-reads
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int wg = slot % nWG, bh = (slot / nWG) * 8 + xcd;
+    const auto [wg, bh] = attn::xcd_decode(blockIdx.x, nWG);   // the workgroups of one (sequence, head) on one XCD
     if (bh >= nBH) return;
     const int hh = bh % H, b = bh / H;
     const half_t* base = qkv + (long)b * L * ld + hh * 64;
@@ -91,7 +72,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
     // per-lane byte offsets are set up once; the block walk is a scalar base; only a block that reaches past the last key clamps its rows.
     constexpr int NI = (16 + NW - 1) / NW;
     const int srow = lane >> 3, sslot = lane & 7;
-    const unsigned lds_base = (unsigned)(uintptr_t)(lptr_t)smem;
+    const unsigned lds_base = (unsigned)(uintptr_t)(attn::lptr_t)smem;
     unsigned soff[NI], sdst[NI];
     int srow_t[NI];
 #pragma unroll
@@ -109,21 +90,27 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
         if (k0 + KB5 <= L) {
 #pragma unroll
             for (int t = 0; t < NI; ++t)
-                if (NW * (t + 1) <= 16 || wave + NW * t < 16) glds16_asm5(kbase, soff[t], __builtin_amdgcn_readfirstlane(sdst[t] + 2u * (unsigned)(st * STAGE5)));
+                if (NW * (t + 1) <= 16 || wave + NW * t < 16)
+                    attn::glds16_asm(kbase, soff[t], __builtin_amdgcn_readfirstlane(sdst[t] + 2u * (unsigned)(st * STAGE5)));
         } else {                                           // the last block: rows past the last key repeat it (finite values, masked below)
 #pragma unroll
             for (int t = 0; t < NI; ++t)
                 if (NW * (t + 1) <= 16 || wave + NW * t < 16)
-                    glds16_asm5(kbase, soff[t] - (unsigned)max(k0 + srow_t[t] - (L - 1), 0) * row_bytes,
-                                __builtin_amdgcn_readfirstlane(sdst[t] + 2u * (unsigned)(st * STAGE5)));
+                    attn::glds16_asm(kbase, soff[t] - (unsigned)max(k0 + srow_t[t] - (L - 1), 0) * row_bytes,
+                                     __builtin_amdgcn_readfirstlane(sdst[t] + 2u * (unsigned)(st * STAGE5)));
         }
     };
 
-    float m_run = -INFINITY;                               // reference maximum of the exponentials (scaled domain), variant 1's lazy form
+    float m_run = -INFINITY;                               // the lazily moved reference maximum of the exponentials (attn::lazy_reference)
     float16_t o[2];
 #pragma unroll
     for (int k = 0; k < 16; ++k) { o[0][k] = 0.f; o[1][k] = 0.f; }
     float lsum = 0.f;                                      // this lane's share of the row sum (lanes l and l + 32 are added at the end)
+    auto rescale = [&](float alpha) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { o[0][k] *= alpha; o[1][k] *= alpha; }
+        lsum *= alpha;
+    };
 
     // per-lane LDS offsets (halves).  K fragment of k-step ks: row r, logical chunk 2 ks + h.  V^T fragment of d block blk,
     // k-step t: the 16-lane group g = lane >> 4 serves d columns blk*32 + (g & 1)*16 + [0,16) and the keys 16 t + 4 (g >> 1) + [0,4)
@@ -189,20 +176,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
         for (int sb = 0; sb < 2; ++sb)
 #pragma unroll
             for (int k = 0; k < 16; ++k) mx = fmaxf(mx, s[sb][k]);
-        {
-            const unsigned u = __builtin_bit_cast(unsigned, mx);
-            auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-            mx = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-        }
-        const float mxs = mx * scale_log2e;
-        if (__builtin_amdgcn_ballot_w64(mxs > m_run + 8.0f) != 0) {      // wave-uniform: some row needs a new reference
-            const float m_new = fmaxf(m_run, mxs);
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // <= 0 (first block: -inf -> 0)
-            m_run = m_new;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) { o[0][k] *= alpha; o[1][k] *= alpha; }
-            lsum *= alpha;
-        }
+        const float2_t m2 = attn::pair32(mx);
+        attn::lazy_reference(fmaxf(m2[0], m2[1]) * scale_log2e, m_run, rescale);
         const float m_ref = m_run;
 #pragma unroll
         for (int st = 0; st < 4; ++st) {                   // 16-key PV steps: registers 8 t .. 8 t + 7 of half sb = st >> 1, t = st & 1
@@ -218,8 +193,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
             }
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
-                const half4_t v0 = tr_read5(smem + voff[blk] + (st_off + st * 16 * 64));
-                const half4_t v1 = tr_read5(smem + voff[blk] + (st_off + (st * 16 + 8) * 64));
+                const half4_t v0 = tr_read(smem + voff[blk] + (st_off + st * 16 * 64));
+                const half4_t v1 = tr_read(smem + voff[blk] + (st_off + (st * 16 + 8) * 64));
                 const half8_t vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 o[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[blk], 0, 0, 0);
             }
@@ -257,20 +232,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
                 s0[k] = ((k & 3) + 8 * (k >> 2) < thr_k) ? s0[k] : -INFINITY;
                 mx = fmaxf(mx, s0[k]);
             }
-            {
-                const unsigned u = __builtin_bit_cast(unsigned, mx);
-                auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-                mx = fmaxf(__builtin_bit_cast(float, (unsigned)sw[0]), __builtin_bit_cast(float, (unsigned)sw[1]));
-            }
-            const float mxs = mx * scale_log2e;
-            if (__builtin_amdgcn_ballot_w64(mxs > m_run + 8.0f) != 0) {
-                const float m_new = fmaxf(m_run, mxs);
-                const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-                m_run = m_new;
-#pragma unroll
-                for (int k = 0; k < 16; ++k) { o[0][k] *= alpha; o[1][k] *= alpha; }
-                lsum *= alpha;
-            }
+            const float2_t m2 = attn::pair32(mx);
+            attn::lazy_reference(fmaxf(m2[0], m2[1]) * scale_log2e, m_run, rescale);
             const float m_ref = m_run;
             half8_t pf;
 #pragma unroll
@@ -284,8 +247,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
             }
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
-                const half4_t v0 = tr_read5(smem + voff[blk] + st_off);
-                const half4_t v1 = tr_read5(smem + voff[blk] + (st_off + 8 * 64));
+                const half4_t v0 = tr_read(smem + voff[blk] + st_off);
+                const half4_t v1 = tr_read(smem + voff[blk] + (st_off + 8 * 64));
                 const half8_t vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
                 o[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, o[blk], 0, 0, 0);
             }
@@ -297,12 +260,8 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
     __builtin_amdgcn_s_barrier();                          // every wave is done with the K / V stages: they become staging tiles
     if (!act) return;
     char* et = (char*)smem + wave * 4096;                  // this wave's 32 rows x 128 B
-    float inv;
-    {
-        const unsigned u = __builtin_bit_cast(unsigned, lsum);
-        auto sw = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-        inv = 1.0f / (__builtin_bit_cast(float, (unsigned)sw[0]) + __builtin_bit_cast(float, (unsigned)sw[1]));
-    }
+    const float2_t l2 = attn::pair32(lsum);
+    const float inv = 1.0f / (l2[0] + l2[1]);
     // register k of o[blk] holds d = blk*32 + (k & 3) + 8 (k >> 2) + 4 h: 8-byte unit u = blk*8 + 2 (k >> 2) + h of row r, stored at
     // u ^ f(r & 15), f(x) = ((x & 7) << 1) | (x >> 3) (gemm_f16_v5.hip epilogue: conflict-free 8-byte writes and 16-byte reads)
     const int fsw = ((r & 7) << 1) | ((r >> 3) & 1);
@@ -326,20 +285,18 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
 }
 
 template <int NW>
-int launch_v5(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, hipStream_t s) {
+int launch_nw(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, hipStream_t s) {
     const int nT = (Lq + 31) / 32, nWG = (nT + NW - 1) / NW, nBH = B * H;
-    const float sl2e = 0.125f * 1.4426950408889634f;
-    const dim3 grid((unsigned)((long)((nBH + 7) / 8) * 8 * nWG));
-    hipLaunchKernelGGL((attn_f16_v5<NW>), grid, dim3(NW * 64), 0, s, qkv, out, L, Lq, H, nT, nWG, nBH, sl2e);
+    hipLaunchKernelGGL((attn_f16_v5<NW>), dim3(attn::xcd_grid(nBH, nWG)), dim3(NW * 64), 0, s, qkv, out, L, Lq, H, nT, nWG, nBH,
+                       attn::SCALE_LOG2E);
     return (int)hipGetLastError();
 }
 
 }  // namespace
 
-// -100: shape not taken (causal, short sequences, a handful of query rows): the caller falls back to variant 1.
-int launch_attention_f16_v5(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, int causal, hipStream_t s) {
-    if (causal || L < 256 || Lq < 32) return -100;
+int attn::launch_attention_f16_v5(const half_t* qkv, half_t* out, int B, int L, int Lq, int H, hipStream_t s) {
+    if (!attn::v5_takes(L, Lq, 0)) return -2;
     const int nT = (Lq + 31) / 32;
     const bool three = ((nT + 2) / 3) * 3 < ((nT + 3) / 4) * 4;      // fewer idle wave slots with 3-wave workgroups
-    return three ? launch_v5<3>(qkv, out, B, L, Lq, H, s) : launch_v5<4>(qkv, out, B, L, Lq, H, s);
+    return three ? launch_nw<3>(qkv, out, B, L, Lq, H, s) : launch_nw<4>(qkv, out, B, L, Lq, H, s);
 }

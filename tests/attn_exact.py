@@ -1,7 +1,8 @@
-"""Exact-operand cases for the attention kernels: attention.hip (variant 0 and attn_f32_small), attention_v1.hip,
-attention_v3.hip with attn_single_pass.h, attention_v5.hip and attention_short.hip, behind ovmr_debug_attention and
-ovmr_debug_attention_q.  numpy and torch on the CPU, no library: shared by test_hip_attn_exact.py (GPU) and
-test_attn_exact_cpu.py (which checks this builder).
+"""Exact-operand cases for the attention kernels: attention.hip (attn_f16_v0 and attn_f32_small), attention_v1.hip,
+attention_v3.hip, attention_v5.hip and attention_short.hip, with the steps they share in attn_common.h, behind
+ovmr_debug_attention and ovmr_debug_attention_q.  numpy and torch on the CPU, no library: shared by
+test_hip_attn_exact.py (GPU), test_attn_exact_cpu.py (which checks this builder) and test_attn_route_cpu.py (which
+holds the library's routing function to route() below and checks that the case table reaches every kernel).
 
 THE METHOD (gemm_exact.py carried over to softmax)
 
@@ -82,10 +83,11 @@ TIE_MARGIN = Fraction(1, 1 << 20)       # no expected value within this relative
 # quotients are held to.  All others keep 2^-20.
 NEAR_TIES = {Fraction(17, 273): Fraction(1, 1 << 22), Fraction(136, 273): Fraction(1, 1 << 22)}
 
-SHORT_L = (1, 5, 16, 17, 32, 33)                        # <= 32: attention_short.hip under variants 1 / 3; 33: fall-back
-MID_L = (63, 64, 65, 77, 127, 128, 129, 144, 145)       # 144 / 145: variant 1's tail of 16 / 17 keys (peeled or not)
-SINGLE_L = (192, 193, 197, 208, 209)                    # 193 .. 208: the single-pass kernel, and both sides of it
-LONG_L = (256, 257, 272, 273, 320, 321, 336, 337, 577)  # 272 / 273: variant 5's peel boundary; 320 .. 337: variant 1's
+# Which kernel a length runs under a variant: route() below, held to the library's routing function by test_attn_route_cpu.py.
+SHORT_L = (1, 5, 16, 17, 32, 33)                        # <= 32: the short kernel under every variant but 0; 33: just past it
+MID_L = (63, 64, 65, 77, 127, 128, 129, 144, 145)       # 128: where variant 1 starts; 144 / 145: its tail of 16 / 17 keys (peeled or not)
+SINGLE_L = (192, 193, 197, 208, 209)                    # 193 .. 208: the single-pass kernel under variant 3, and both sides of it
+LONG_L = (256, 257, 272, 273, 320, 321, 336, 337, 577)  # >= 256: variant 5's kernel; 272 / 273: its peel boundary; 320 .. 337: variant 1's
 Q_L, Q_LQ = (197, 257, 577), (1, 16, 17, 33)
 F32_L, F32_UNIFORM_L = (6, 18, 66, 127, 128), (16, 64, 128)
 THREE_L = (197, 257, 577)
@@ -121,6 +123,43 @@ def _cases():
 
 
 CASES = _cases()
+
+
+# ---- which kernel runs ---------------------------------------------------------------------------------------
+
+V0, V1, SHORT, V3, V5 = 0, 1, 2, 3, 5       # attn_f16_v0, attn_f16_v1, attn_f16_short, attn_f16_v3, attn_f16_v5
+
+
+def route(variant, L, Lq, causal):
+    """The kernel launch_attention_f16_q ran for (variant, L, Lq <= L, causal) when each launcher still tested its own
+    shape and declined with -100: restated from that chain, step for step, not from the library's routing function."""
+    def short_declines():       # one group, first row 0: the launcher declined a group longer than 32 tokens
+        return L < 1 or L > 32
+
+    def v3_declines():
+        return bool(causal) or Lq != L or L <= 192 or L > 208
+
+    def v5_declines():
+        return bool(causal) or L < 256 or Lq < 32
+
+    if variant >= 1 and Lq == L and L <= 32:
+        if not short_declines():
+            return SHORT
+    if variant == 4:
+        variant = 3
+    if variant == 3:
+        if not v3_declines():
+            return V3
+        if not v5_declines():
+            return V5
+        variant = 1
+    if variant == 5:
+        if not v5_declines():
+            return V5
+        variant = 1
+    if variant == 1 and L >= 128:
+        return V1               # variant 1's launcher declined no shape
+    return V0
 
 
 # ---- codes ---------------------------------------------------------------------------------------------------
