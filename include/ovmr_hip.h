@@ -243,6 +243,22 @@ int ovmr_eval_counts(const void* outputs, int dtype, long ld, const int64_t* lab
 int ovmr_topk_rows(const void* outputs, int dtype, long ld, int B, int C, int k, float* values, int32_t* indices,
                    const int64_t* labels, int32_t* hits, ovmr_stream stream);
 
+/* The evaluator's detail mode: ALL the counting of Classification.process for one batch in one launch -- the per-class results
+ * (Dassl.pytorch/dassl/evaluation/evaluator.py:38-40, 69-73, printed by :140-163) and the confusion matrix (:165-171) next to what
+ * ovmr_eval_counts and ovmr_topk_rows count; it replaces both launches.  outputs [B, C] fp16 / fp32 with row stride ld >= C elements
+ * (rows need no alignment), labels int64 [B], 1 <= k <= min(C, 32).  Per row the k best columns in the total order of ovmr_topk_rows;
+ * pred = the best one = the argmax of ovmr_eval_counts.  counts: int32 [3][C] + [1], updated exactly as ovmr_eval_counts does; a row
+ * whose label lies outside [0, C) touches nothing but its last slot.  For the other rows, each of the following may be NULL:
+ *   hits       int32 [1]      += 1 when the label is among the row's k columns (the hits of ovmr_topk_rows)
+ *   class_hits int32 [C]      class_hits[label] += 1 for the same rows: the `matches` of _per_class_res[label] (:69-73); at k == 1 it
+ *                             equals counts[0]
+ *   cmat       int32 [C][C]   cmat[label][pred] += 1, row-major, 64-bit index arithmetic: _y_true against _y_pred (:62-67)
+ * The caller zeroes the buffers once and accumulates over a test pass; integer atomics only, so the result does not depend on the
+ * order of execution.  OVMR_E_ARG (nothing is written) for a NULL outputs / labels / counts, ld < C, an unknown dtype or k out of
+ * range; B == 0 returns 0.  One launch, no allocation, no host synchronisation; needs no handle. */
+int ovmr_eval_detail(const void* outputs, int dtype, long ld, const int64_t* labels, int B, int C, int k, int32_t* counts, int32_t* hits,
+                     int32_t* class_hits, int32_t* cmat, ovmr_stream stream);
+
 /* exp(logit_scale) as held by the handle (set through ovmr_set_weight("logit_scale")). */
 float ovmr_logit_scale(const ovmr_handle* h);
 

@@ -13,7 +13,13 @@ runs the zero-shot trainers of trainers/zsclip.py on the same folder data set, a
     python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --predict IMAGES --topk 5 [--classifiers OUTPUT_DIR/mm_classifiers.pt]
 
 ranks the job's classes for UNLABELLED images (a directory, or a text file of paths) instead of the test pass: OUTPUT_DIR/predictions.csv holds
-`image,rank,label,classname,score` (any of the three trainers; `--classifiers` loads a generated file instead of generating again).  Either way `main` is train.py's evaluation path,
+`image,rank,label,classname,score` (any of the three trainers; `--classifiers` loads a generated file instead of generating again).
+
+    python -m ovmr_amd.cli --eval-only --trainer ZeroshotCLIP ... --per-class-result --confusion-matrix
+
+adds the reference's `=> per-class result` block (and `perclass_accuracy` in the results) and OUTPUT_DIR/cmat.pt, the row-normalised
+confusion matrix, to the test pass of any of the three trainers.  These two FLAGS are the switch: the reference's keys
+`TEST.PER_CLASS_RESULT` / `TEST.COMPUTE_CMAT` stay accepted and ignored.  They do not go with `--predict`.  Either way `main` is train.py's evaluation path,
 `trainer.build_trainer(cfg, dm, ...)` and `.test()` (ovmr_amd/trainer.py), on loaders of this runner's own.  It
 takes the command line of `scripts/mm_cls/generate_classifier.sh:30-44` / `train.py:183-255` as it is: `--dataset-config-file` and
 `--config-file` (YAML, read with PyYAML), the flags `reset_cfg` copies (`--root --output-dir --seed --trainer --backbone --init_weight
@@ -286,6 +292,10 @@ def parse(argv=None):
     ap.add_argument("--topk", type=int, default=None, metavar="K", help="classes per image of --predict, best first (default 5; 1 <= K <= min(32, classes))")
     ap.add_argument("--classifiers", metavar="FILE", default="", help="with --predict --trainer MM_CLS_OP: load this mm_classifiers.pt instead of "
                     "generating the classifiers (no exemplar is decoded, no model file is written)")
+    ap.add_argument("--per-class-result", action="store_true", help="the test pass also prints the reference's `=> per-class result` block and "
+                    "reports perclass_accuracy (the reference's TEST.PER_CLASS_RESULT; counted on the GPU by ovmr_eval_detail)")
+    ap.add_argument("--confusion-matrix", action="store_true", help="the test pass also writes OUTPUT_DIR/cmat.pt, the row-normalised confusion "
+                    "matrix (the reference's TEST.COMPUTE_CMAT; counted on the GPU by ovmr_eval_detail)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode worker processes of the pipelined loader (default: DATALOADER.NUM_WORKERS); 0 = decode in this thread")
@@ -386,7 +396,8 @@ def main(argv=None) -> Dict[str, float]:
     """train.py:183-255 on the evaluation path: build_trainer(cfg) and test().  MM_CLS_OP generates the classifiers from the exemplar set,
     writes mm_classifiers.pt / visual_tokens.pt and evaluates the test set; the zero-shot trainers take the classes and test items of the
     same job (build_splits; no exemplar is decoded) and the text classifier from DATASET.NAME's template(s), and write no model file.
-    The result block and acc_per_class.csv / f1_per_class.csv land in OUTPUT_DIR."""
+    The result block and acc_per_class.csv / f1_per_class.csv land in OUTPUT_DIR; --per-class-result adds the per-class block and
+    results["perclass_accuracy"], --confusion-matrix adds OUTPUT_DIR/cmat.pt."""
     from . import config, templates
     args = parse(argv)
     cfg = config.setup_cfg(args)                              # train.py:134-155
@@ -398,6 +409,9 @@ def main(argv=None) -> Dict[str, float]:
     split_cfg = cfg
     predict, images, k = args.predict is not None, [], None
     if predict:
+        for flag, on in (("--per-class-result", args.per_class_result), ("--confusion-matrix", args.confusion_matrix)):
+            if on:
+                raise SystemExit(f"{flag} belongs to the test pass: --predict ranks unlabelled images, there is nothing to count")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("--predict runs in one process: sharding the prediction pass over ranks is not implemented")
         k = 5 if args.topk is None else args.topk
@@ -478,7 +492,8 @@ def main(argv=None) -> Dict[str, float]:
         first.warm()
     dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
     tr = trainer.build_trainer(cfg, dm, clip_weights=clip_sd, tokenizer=BPETokenizer(args.bpe_path), device=args.device,
-                               reserve=(batch, 256, max(1024, len(classnames))), **kw)
+                               reserve=(batch, 256, max(1024, len(classnames))), per_class_result=args.per_class_result,
+                               compute_cmat=args.confusion_matrix, **kw)
     if load_classifiers:
         tr.model.load_classifiers(args.classifiers)
     elif not zeroshot:

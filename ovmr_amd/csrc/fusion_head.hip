@@ -8,23 +8,9 @@
 //     logits in fp32, then sum_n p[b,c,n] * w[c,n] (column order mm, vision, text).
 // All three are HBM/L2-bound row kernels; the logits themselves come from the MFMA GEMM.
 #include "common.h"
+#include "eval_common.h"
 
 namespace {
-
-// counts[key] += 1 for every lane with valid set, ONE atomic per distinct key and wave: the argmax of exemplar rows concentrates on few
-// classes (always with untrained weights, per class with trained ones: S consecutive rows share their label), and same-address atomics
-// serialise -- 16 000 rows on a handful of classes took 155 us (r04o trace), most of the cross-validation step.
-__device__ __forceinline__ void wave_histogram_add(int* counts, int key, bool valid) {
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(valid);
-    const int lane = threadIdx.x & 63;
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const int k = __builtin_amdgcn_readlane(key, leader);
-        const unsigned long long same = __builtin_amdgcn_ballot_w64(valid && key == k);
-        if (lane == leader) atomicAdd(counts + k, (int)__builtin_popcountll(same));
-        todo &= ~same;
-    }
-}
 
 __global__ __launch_bounds__(256) void xval_argmax_counts(const half_t* __restrict__ logits, int ld,
                                                           const int* __restrict__ labels, int rows, int C,

@@ -18,6 +18,8 @@
 int launch_text_ensemble(const half_t* feats, int T, int rows, int E, half_t* out, hipStream_t s);
 int launch_topk_rows(const void* out, int out_is_f32, long ld, int B, int C, int k, float* values, int32_t* indices, const int64_t* labels,
                      int* hits, hipStream_t s);   // topk.hip
+int launch_eval_detail(const void* out, int out_is_f32, long ld, const int64_t* labels, int B, int C, int k, int* counts, int* hits,
+                       int* class_hits, int* cmat, hipStream_t s);   // eval_detail.hip
 
 namespace {
 
@@ -935,6 +937,14 @@ int ovmr_topk_rows(const void* outputs, int dtype, long ld, int B, int C, int k,
     if (!outputs || !indices || B < 0 || k < 1 || k > C || k > 32 || ld < C || (dtype != OVMR_F16 && dtype != OVMR_F32) || !labels != !hits)
         return OVMR_E_ARG;
     return launch_topk_rows(outputs, dtype == OVMR_F32, ld, B, C, k, values, indices, labels, hits, (hipStream_t)stream);
+}
+
+int ovmr_eval_detail(const void* outputs, int dtype, long ld, const int64_t* labels, int B, int C, int k, int32_t* counts, int32_t* hits,
+                     int32_t* class_hits, int32_t* cmat, ovmr_stream stream) {
+    if (B == 0) return 0;
+    if (!outputs || !labels || !counts || B < 0 || C < 1 || k < 1 || k > C || k > 32 || ld < C || (dtype != OVMR_F16 && dtype != OVMR_F32))
+        return OVMR_E_ARG;
+    return launch_eval_detail(outputs, dtype == OVMR_F32, ld, labels, B, C, k, counts, hits, class_hits, cmat, (hipStream_t)stream);
 }
 
 int ovmr_fused_logits(ovmr_handle* h, const void* feats_f16, int B, const void* mm, const void* v, const void* t,

@@ -4,59 +4,16 @@
 // every NaN above +inf (NaNs among themselves by column), -0 == +0.  Column 0 of the result is the row argmax of eval_counts_kernel
 // (fusion_head.hip).
 //
-// One wave per row, four rows per 256-thread block, k selection rounds.  An element maps to a 64-bit key
+// One wave per row, four rows per 256-thread block, k selection rounds (topk_key / topk_round, eval_common.h: shared with
+// eval_detail.hip).  An element maps to a 64-bit key
 //     (order-preserving bits of the value: NaN -> 0xFFFFFFFF, -0 -> +0) << 32 | (0xFFFFFFFF - column)
 // so that "better" is "larger key" and no two elements of a row share a key.  Round j takes the largest key at or below `limit` = the
 // previous winner's key - 1: every lane scans its columns (16-byte loads where the row is aligned), the wave reduces by shuffles.  A row
 // is at most 87 KB (21 841 fp32 classes): rounds 1 .. k-1 re-read it from L2.  The kernel is latency-bound.
 #include "common.h"
+#include "eval_common.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned long long topk_key(float v, int c) {
-    unsigned u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0;                                     // -0 == +0
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                  // negative values reversed below the positive ones: -inf -> 0x007FFFFF, +inf -> 0xFF800000
-    if (v != v) u = 0xFFFFFFFFu;                                     // every NaN, of either sign: above +inf
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)c);
-}
-
-// the largest key <= limit of the row (0: none left; a real key is at least 0x007FFFFF << 32)
-template <typename T>
-__device__ __forceinline__ unsigned long long topk_round(const T* __restrict__ row, int C, int lane, unsigned long long limit) {
-    unsigned long long best = 0;
-    auto take = [&](float v, int c) {
-        const unsigned long long key = topk_key(v, c);
-        if (key <= limit && key > best) best = key;
-    };
-    constexpr int V = 16 / (int)sizeof(T);
-    if ((((uintptr_t)row) & 15) == 0) {
-        const int Cv = C / V * V;
-        for (int c = lane * V; c < Cv; c += 64 * V) {
-            if constexpr (sizeof(T) == 4) {
-                const float4 q = *(const float4*)(row + c);
-                take(q.x, c); take(q.y, c + 1); take(q.z, c + 2); take(q.w, c + 3);
-            } else {
-                const uint4 q = *(const uint4*)(row + c);
-                const unsigned u[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    half2_t h2 = *(const half2_t*)&u[i];
-                    take((float)h2[0], c + 2 * i); take((float)h2[1], c + 2 * i + 1);
-                }
-            }
-        }
-        for (int c = Cv + lane; c < C; c += 64) take((float)row[c], c);
-    } else
-        for (int c = lane; c < C; c += 64) take((float)row[c], c);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned hi = __shfl_xor((unsigned)(best >> 32), o, 64), lo = __shfl_xor((unsigned)best, o, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        if (other > best) best = other;
-    }
-    return best;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void topk_rows_kernel(const T* __restrict__ out, long ld, int rows, int C, int k,

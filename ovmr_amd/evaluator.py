@@ -6,6 +6,11 @@ the library's own row-argmax-and-count kernel (`ovmr_eval_counts`, csrc/fusion_h
 counting, on the [B, C] outputs) -- the reference does `.item()` and `.cpu().numpy()` per batch (:59-67), i.e. one host
 sync per batch of 256 images; here the host reads 3C + 1 integers once, in evaluate().
 
+Detail mode (`per_class=True` and / or `confusion=True`: the reference's TEST.PER_CLASS_RESULT / TEST.COMPUTE_CMAT, evaluator.py:38-40,
+69-73, 140-171) keeps everything an integer counter on the device as well: ONE `ovmr_eval_detail` launch per batch (csrc/eval_detail.hip)
+does the counting above plus the per-class matches and the [C, C] confusion counts; evaluate() prints the reference's `=> per-class
+result` block and writes `cmat.pt`, the array sklearn's confusion_matrix(normalize="true") returns.  With both off nothing changes.
+
 Outputs that live on the GPU go through the kernel and nothing else: without libovmr_hip.so `process` raises.  Host
 tensors (an evaluator built with device="cpu": host-side callers, the CPU tests of evaluate()'s arithmetic) are counted
 on the host.
@@ -20,8 +25,10 @@ import torch
 
 
 class Classification:
-    def __init__(self, num_classes: int, classnames: Optional[Sequence[str]] = None, device="cuda"):
+    def __init__(self, num_classes: int, classnames: Optional[Sequence[str]] = None, device="cuda", per_class: bool = False,
+                 confusion: bool = False):
         self.num_classes = num_classes
+        self.per_class, self.confusion = bool(per_class), bool(confusion)
         self.classnames = list(classnames) if classnames is not None else [str(i) for i in range(num_classes)]
         self.device = torch.device(device)
         self.reset()
@@ -31,6 +38,10 @@ class Classification:
         self._counts = torch.zeros(3 * self.num_classes + 1, dtype=torch.int32, device=self.device)
         self._topk = None                            # the `topk` of this pass, set by its first process()
         self._hits = None                            # int32 [1], topk > 1: rows whose label is among their k best columns
+        # detail mode, allocated by the first process() of the pass (the matches depend on its topk)
+        self._class_hits = None                      # int32 [C], per_class and topk > 1: such rows per label (at topk == 1 that is tp)
+        self._cmat = None                            # int32 [C, C], confusion: rows per (label, top-1 prediction)
+        self.confusion_counts = None                 # int64 [C, C] on the host, set by evaluate()
 
     @torch.no_grad()
     def process(self, mo: torch.Tensor, gt: torch.Tensor, topk: int = 1):
@@ -49,13 +60,23 @@ class Classification:
             self._topk = topk
             if topk > 1:
                 self._hits = torch.zeros(1, dtype=torch.int32, device=self.device)
+                if self.per_class:
+                    self._class_hits = torch.zeros(C, dtype=torch.int32, device=self.device)
+            if self.confusion:
+                self._cmat = torch.zeros((C, C), dtype=torch.int32, device=self.device)
         elif topk != self._topk:
             raise ValueError(f"process(topk={topk}) in a pass that began with topk={self._topk}: one pass uses one topk (reset() starts the next)")
         if self.device.type == "cpu":
-            self._process_host(mo, gt)
+            pred, ok = self._process_host(mo, gt)
+            gt = gt.long()
             if topk > 1:
                 order = torch.sort(mo.float(), dim=1, descending=True, stable=True)[1][:, :topk]     # the library's total order
-                self._hits += int((order == gt.long().unsqueeze(1)).any(dim=1).sum())
+                hit = (order == gt.unsqueeze(1)).any(dim=1)
+                self._hits += int(hit.sum())
+                if self._class_hits is not None:
+                    self._class_hits += torch.bincount(gt[ok & hit], minlength=C).int()
+            if self._cmat is not None:
+                self._cmat.index_put_((gt[ok], pred[ok]), torch.ones(int(ok.sum()), dtype=torch.int32), accumulate=True)
             return
         from . import runtime
         lib = runtime.load_library()                                      # raises without the HIP library: no fallback for device tensors
@@ -67,6 +88,10 @@ class Classification:
         gt = gt.to(self.device, non_blocking=True)
         if gt.dtype != torch.int64 or not gt.is_contiguous():
             gt = gt.long().contiguous()
+        if self.per_class or self.confusion:                              # ONE launch: counts, hits, per-class matches, confusion counts
+            if mo.shape[0]:
+                runtime.eval_detail(mo, gt, topk, self._counts, self._hits, self._class_hits, self._cmat)
+            return
         rc = lib.ovmr_eval_counts(runtime._ptr(mo), runtime.F32 if mo.dtype == torch.float32 else runtime.F16, mo.stride(0),
                                   runtime._ptr(gt), mo.shape[0], C, runtime._ptr(self._counts), runtime._stream())
         if rc != 0:
@@ -75,7 +100,7 @@ class Classification:
             runtime.topk_rows(mo, topk, gt, self._hits)
 
     def _process_host(self, mo, gt):
-        """The same three histograms for host tensors (mo.max(1)[1]: lowest column on ties)."""
+        """The same three histograms for host tensors (mo.max(1)[1]: lowest column on ties); returns (pred, rows with a label in [0, C))."""
         C = self.num_classes
         pred = mo.float().argmax(dim=1)
         gt = gt.long()
@@ -86,6 +111,7 @@ class Classification:
         c[2 * C:3 * C] += torch.bincount(gt[ok], minlength=C).int()
         c[C:2 * C] += torch.bincount(pred[ok], minlength=C).int()
         c[:C] += torch.bincount(gt[ok & (pred == gt)], minlength=C).int()
+        return pred, ok
 
     def counts(self):
         """(tp, n_pred, n_label) as int64 host tensors [C]; raises if a label outside [0, C) was seen."""
@@ -96,7 +122,8 @@ class Classification:
         return c[:C], c[C:2 * C], c[2 * C:3 * C]
 
     def evaluate(self, output_dir: Optional[str] = None) -> "OrderedDict[str, float]":
-        tp, n_pred, n_label = (t.double() for t in self.counts())
+        tp_i, n_pred_i, n_label_i = self.counts()
+        tp, n_pred, n_label = tp_i.double(), n_pred_i.double(), n_label_i.double()
         total = float(n_label.sum())
         correct = int(tp.sum()) if self._hits is None else int(self._hits.cpu()[0])        # evaluator.py:56-60
         acc = 100.0 * correct / max(total, 1.0)
@@ -126,4 +153,36 @@ class Classification:
                 w.writerow(["Label", "F1"])
                 for item_id, i in enumerate(labels):
                     w.writerow([item_id, self.per_class_f1[i]])
+        if self.per_class:                                                # evaluator.py:140-163, its format byte for byte
+            import numpy as np
+            matches = tp_i if self._class_hits is None else self._class_hits.cpu().long()      # top-k matches when topk > 1 (:56-58, 69-73)
+            print("=> per-class result")
+            accs = []
+            for label in range(self.num_classes):
+                total_c, correct_c = int(n_label_i[label]), int(matches[label])
+                if total_c == 0:                                          # _per_class_res has a key per label that occurred
+                    continue
+                acc_c = 100.0 * correct_c / total_c
+                accs.append(acc_c)
+                print(f"* class: {label} ({self.classnames[label]})\ttotal: {total_c:,}\tcorrect: {correct_c:,}\tacc: {acc_c:.1f}%")
+            mean_acc = float(np.mean(accs)) if accs else 0.0
+            print(f"* average: {mean_acc:.1f}%")
+            res["perclass_accuracy"] = mean_acc
+        if self.confusion:                                                # evaluator.py:165-171
+            C = self.num_classes
+            cm = self._cmat.cpu().long() if self._cmat is not None else torch.zeros((C, C), dtype=torch.int64)
+            self.confusion_counts = cm
+            if output_dir:
+                import numpy as np
+                os.makedirs(output_dir, exist_ok=True)
+                # sklearn.metrics.confusion_matrix(y_true, y_pred, normalize="true") from the counts: the classes that occur as a label
+                # or as a prediction, in increasing order; every row over its sum, 0 / 0 -> 0.  The same int64 / int64 division and
+                # nan_to_num as sklearn's own, so the array is its array bit for bit
+                present = ((n_label_i > 0) | (n_pred_i > 0)).numpy()
+                sub = cm.numpy()[present][:, present]
+                with np.errstate(all="ignore"):
+                    sub = np.nan_to_num(sub / sub.sum(axis=1, keepdims=True))
+                save_path = os.path.join(output_dir, "cmat.pt")
+                torch.save(sub, save_path)
+                print(f"Confusion matrix is saved to {save_path}")
         return res

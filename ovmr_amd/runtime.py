@@ -66,6 +66,7 @@ SIGNATURES = {
     "ovmr_unpack_rows": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "ovmr_eval_counts": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, c_p, c_p]),
     "ovmr_topk_rows": (c_i, [c_p, c_i, ctypes.c_long, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "ovmr_eval_detail": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "ovmr_head_plan": (c_i, [c_p, c_i, c_i]),
     "ovmr_zeroshot_logits": (c_i, [c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
     "ovmr_logit_scale": (ctypes.c_float, [c_p]),
@@ -149,6 +150,32 @@ def topk_rows(mo: torch.Tensor, k: int, labels: Optional[torch.Tensor] = None, h
     if rc != 0:
         raise OvmrError(f"ovmr_topk_rows failed with {rc} (B = {B}, C = {C}, k = {k})")
     return values, indices
+
+
+def eval_detail(mo: torch.Tensor, labels: torch.Tensor, k: int, counts: torch.Tensor, hits: Optional[torch.Tensor] = None,
+                class_hits: Optional[torch.Tensor] = None, cmat: Optional[torch.Tensor] = None):
+    """ovmr_eval_detail on the current stream: mo [B, C] fp16 / fp32 on the GPU (stride(1) == 1, stride(0) >= C), labels int64 [B];
+    counts int32 [3C + 1], hits int32 [1], class_hits int32 [C], cmat int32 [C, C] (the last three optional) accumulate
+    (include/ovmr_hip.h)."""
+    lib = load_library()
+    if mo.dim() != 2 or not mo.is_cuda or mo.dtype not in (torch.float16, torch.float32) or (mo.shape[1] > 1 and mo.stride(1) != 1):
+        raise ValueError(f"eval_detail takes a [B, C] fp16 / fp32 device tensor with unit column stride, got {tuple(mo.shape)} {mo.dtype} "
+                         f"on {mo.device}")
+    B, C = mo.shape
+    if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (B,)):
+        raise ValueError("labels must be a contiguous int64 [B] device tensor")
+    for name, t, n in (("counts", counts, 3 * C + 1), ("hits", hits, 1), ("class_hits", class_hits, C), ("cmat", cmat, C * C)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+            raise ValueError(f"{name} must be a contiguous int32 device tensor of {n} elements")
+    if counts is None:
+        raise ValueError("eval_detail needs counts")
+    with torch.cuda.device(mo.device):
+        ld = mo.stride(0) if B > 1 else max(C, mo.stride(0))
+        rc = lib.ovmr_eval_detail(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, _ptr(labels), B, C, int(k), _ptr(counts),
+                                  _ptr(hits), _ptr(class_hits), _ptr(cmat),
+                                  ctypes.c_void_p(torch.cuda.current_stream(mo.device).cuda_stream))
+    if rc != 0:
+        raise OvmrError(f"ovmr_eval_detail failed with {rc} (B = {B}, C = {C}, k = {k})")
 
 
 class Engine:

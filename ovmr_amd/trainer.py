@@ -43,7 +43,8 @@ class _EvalTrainer:
     CLIP_FETCHED_BY = ""          # where the reference downloads the CLIP weights (the FileNotFoundError names it)
     NOT_TRAINED = ""              # the NotImplementedError of forward_backward / train / save_model
 
-    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None):
+    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, per_class_result=False,
+                 compute_cmat=False):
         self.check_cfg(cfg)
         self.cfg, self.dm, self.device = cfg, dm, torch.device(device)
         self._clip_weights, self._tokenizer, self._reserve = clip_weights, tokenizer, reserve
@@ -55,7 +56,9 @@ class _EvalTrainer:
         self.epoch = 0
         self.output_dir = cfg.OUTPUT_DIR
         self.build_model()
-        self.evaluator = Classification(self.num_classes, list(dm.dataset.classnames), device=str(self.device))
+        # per_class_result / compute_cmat: what the reference reads from TEST.PER_CLASS_RESULT / TEST.COMPUTE_CMAT (evaluator.py:38, 165)
+        self.evaluator = Classification(self.num_classes, list(dm.dataset.classnames), device=str(self.device),
+                                        per_class=per_class_result, confusion=compute_cmat)
 
     def check_cfg(self, cfg):
         pass
@@ -159,9 +162,10 @@ class MM_CLS_OP(_EvalTrainer):
     CLIP_FETCHED_BY = "clip/clip.py:29-70"
     NOT_TRAINED = "training (autograd through CustomCLIP.forward, :310-338) is out of scope of the HIP hot path"
 
-    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, prompt_learner_state=None):
+    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, prompt_learner_state=None,
+                 per_class_result=False, compute_cmat=False):
         self._prompt_learner_state = prompt_learner_state
-        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve)
+        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve, per_class_result, compute_cmat)
 
     # :369-370
     def check_cfg(self, cfg):
