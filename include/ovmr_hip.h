@@ -65,10 +65,13 @@ const char* ovmr_last_error(const ovmr_handle* h);
 const char* ovmr_version(void);
 
 /* Kernel-variant switch used by tests/bench to A/B implementations: key in {"gemm","attn","ln_fold","xval_fused","gelu_exact","fuse_im2col","enc_chunk","last_q_cls","fused_head","head_max_grid"}.
- * "gemm" (default 8): 8 = 256-row LDS-DMA tiles with the ping-pong K loop (half-tile staging, counted waits) and, for latency-bound shapes
+ * "gemm" (default 8): which fp16 GEMM kernel a launch runs, and with which K loop, tile height and cache hints (gemm_f16_route in
+ *   csrc/gemm_f16.hip, exported as ovmr_debug_gemm_route):
+ *   8 = 256-row LDS-DMA tiles with the ping-pong K loop (half-tile staging, counted waits) and, for latency-bound shapes
  *   (at most one round -- 256 -- of 64 x 64 tiles: the text tower on a few dozen prompts, CLS-row chains), the 64 x 64 kernel that splits K
  *   over its waves; 7 = 8 without that kernel (A/B); 6 = the 256-row tiles with the double-buffered K loop; 9 = the 64 x 64 split-K kernel wherever it takes the shape (tests);
  *   0 = the 128x128 register-staged kernel everywhere (LayerNorm-folding and fused-argmax launches still take the tile kernel).
+ *   + 100 (debug hooks): QuickGELU epilogues in the one-rounding form, as "gelu_exact" = 0.
  * "attn" (default 3): which fp16 attention kernel a launch of L tokens and Lq <= L query rows runs (route() in csrc/attention.hip, exported
  *   as ovmr_debug_attention_route; the first line that applies):
  *     every value >= 1, Lq == L <= 32 (truncated text prompts)      the one-wave-per-(sequence, head) kernel, bit-equal to variant 0;
@@ -348,6 +351,19 @@ int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L
 /* The kernel an fp16 attention launch under option "attn" = variant runs (no launch, no GPU): 0 plain flash-style, 1 flash-style
  * LDS-DMA, 2 short sequences, 3 single-pass, 5 32x32x16 flash. */
 int ovmr_debug_attention_route(int variant, int L, int Lq, int causal);
+/* The plan of an fp16 GEMM launch under option "gemm" = variant (no launch, no GPU), for 16-byte-aligned operands with lda = ldw = K
+ * and every operand present that a feature of the 256-row kernel needs; stats: with the row statistics output; im2col: the image
+ * side R of a patch-gathering launch (rows_in = (R / 16)^2), 0 = A is a matrix.  out[10]:
+ *   [0] kernel: 0 none (the launch returns [1]), 1 the 128 x 128 kernel, 2 64 x 64 split-K, 3 256-row family tile kernel;
+ *   [1] return code of a launch that runs no kernel (0: empty shape);
+ *   [2] split-K: K-steps of 32 prefetched per wave, [3] groups of that many steps per wave;
+ *   tile kernel: [4] tile rows (128 / 256), [5] K loop (0 double-buffered, 1 iteration boundary inside the MFMA stream, 2 ping-pong),
+ *   [6] nontemporal A stream, [7] nontemporal C stores, [8] N tiles per group of the tile order (4, or all of them);
+ *   [9] QuickGELU in the one-rounding form (epilogues 2 and 7). */
+int ovmr_debug_gemm_route(int variant, int M, int N, int K, int epi, int ldc, int ldres, int stats, int im2col, int* out);
+/* The instantiations of the tile kernel the library holds, (epilogue, tile rows / 32, option bits) each: returns their number and
+ * writes the first `cap` of them to out[3 * cap].  The route reaches every one of them and no other (tests/test_gemm_route_cpu.py). */
+int ovmr_debug_gemm_tile_kernels(int* out, int cap);
 
 #ifdef __cplusplus
 }

@@ -46,7 +46,7 @@ struct GemmArgs {
     int epi;
     int rows_in, rows_out;      // EPI_PATCH: patches per image (G*G) and tokens per image (G*G+1)
     float scale;                // EPI_SCALE
-    int n_group;                // N tiles per L2 group (tile order, set by the launcher; 0 = all)
+    int n_group;                // N tiles per L2 group (tile order; launch_gemm_f16 fills it from the route's plan)
     // LayerNorm folding (see EPI_LN_BIAS).  Row statistics travel as per-row PARTIAL sums [M][slots][2] fp32
     // (sum, sum of squares), one slot per 256-column tile of the producing GEMM, summed in slot order by the consumer
     // (deterministic: no atomics).
@@ -54,9 +54,9 @@ struct GemmArgs {
     int ln_stride;                         // ... slots between the statistics of consecutive A rows (0 = ln_slots: dense; the CLS-row launch strides over tokens)
     const float* ln_g; const float* ln_b;  // EPI_LN_*: [N] fp32 each
     float* stats_out;                      // EPI_BIAS_RES, optional: partial statistics of the stored C rows, [M][N/256][2]
-    int nt_store;                          // v5: 0 = auto (streaming stores when C is much larger than the L2s), 1 = never, 2 = always
+    int nt_store;                          // unused (the route decides the store hint); kept because every kernel's instructions carry the offsets behind it
     float* argmax_out;                     // EPI_SCALE_ARGMAX: [M][ceil(N/256)][2] (value, column index bits)
-    int gelu_mode;                         // QuickGELU epilogues: 0 = the reference's three fp16 rounding points, 1 = quick_gelu_f32x2 (set from variant / 100)
+    int gelu_mode;                         // QuickGELU epilogues: 0 = the reference's three fp16 rounding points, 1 = quick_gelu_f32x2
     // EPI_PATCH, gemm_f16_v5 only: A is the fp16 IMAGE tensor [B, 3, R, R] itself and the K loop gathers the patch rows
     // (k = c * 256 + ky * 16 + kx, 16 x 16 patches) straight into LDS -- no im2col pass.  0 = A is the [M, K] matrix.
     int im2col_R;
@@ -127,8 +127,7 @@ __device__ __forceinline__ float wave_max(float v) {
     } while (0)
 
 // ---- launchers (one per .hip translation unit) -------------------------------------------
-int launch_gemm_f16(const GemmArgs& a, int variant, hipStream_t s);
-bool gemm_f16_is_small(int M, int N);   // latency-bound shape: variant 8 runs it on the 64 x 64 split-K kernel (gemm_f16_small.hip)
+int launch_gemm_f16(const GemmArgs& a, int variant, hipStream_t s);   // gemm_route.h: which kernel it runs
 int launch_gemm_f32(const GemmArgs& a, hipStream_t s);
 int launch_layernorm(const void* x, void* y, const float* g, const float* b, int rows, int D,
                      long in_row_stride, int is_f32, hipStream_t s);

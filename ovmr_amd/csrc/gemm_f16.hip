@@ -4,21 +4,23 @@
 // out-proj (K6), c_fc+QuickGELU (K7), c_proj (K8), the CLS/EOS projections (K9,K15) and the
 // classifier logits (K18,K21) of SURVEY.md section 2.3.
 //
-// Variant 0 ("t128"): 128x128x64 tile, 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 f16
+// Which kernel of the family a launch runs is decided in ONE place, gemm_f16_route at the end of this file (gemm_route.h: the plan).
+//
+// This file's kernel ("t128", all of variant 0): 128x128x64 tile, 4 waves (2x2), each wave 64x64 = 4x4 MFMA 16x16x32 f16
 // tiles; operands staged global -> registers -> LDS (double buffered, XOR-swizzled 128-byte
 // rows so every ds_read_b128 lane group hits 16 distinct 16-byte slots).
 // The MFMA is issued with W as the A operand and A as the B operand, so the accumulator holds
 // C^T: lane l owns row m = l&15 and four CONSECUTIVE columns n = 4*(l>>4)..+3, which turns the
 // epilogue (bias / residual / QuickGELU / positional add) into 8-byte vector loads and stores.
-#include "common.h"
 #include "gemm_epi.h"
+#include "gemm_route.h"
 
 namespace {
 
 constexpr int BK = 64;
 
 // ------------------------------------------------------------------------------------------
-// Variant 0: 128x128x64, register-staged double buffer.
+// 128x128x64, register-staged double buffer.
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_f16_t128(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -126,56 +128,141 @@ int launch_t128(const GemmArgs& a, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-}  // namespace
-
-int launch_gemm_f16_v5(const GemmArgs& a, int variant, hipStream_t s);  // gemm_f16_v5.hip: 256(128)x256x64 LDS-DMA tiles, fused epilogues
-int launch_gemm_f16_small(const GemmArgs& a, hipStream_t s);            // gemm_f16_small.hip: 64x64 tiles, K split over the waves (latency-bound shapes)
-
 // Shapes that are at most ONE round of 64 x 64 tiles on the 256 CUs: there the K loop of a tile kernel runs at one memory latency
 // per K-tile on a mostly idle machine and the split-K kernel (gemm_f16_small.hip) wins -- 8-9 us against 10-14 us at K = 512,
 // 20 against 28 at K = 2048, 27 against 43 at K = 3072, 3-5x at a few dozen rows; beyond one round its missing operand reuse costs
 // more than the latency it hides (profiles/r04d_small_gemm_bench.log: the rule matches the faster kernel on all 81 measured shapes
 // but the two within 5 %).
-bool gemm_f16_is_small(int M, int N) { return (long)((M + 63) / 64) * ((N + 63) / 64) <= 256; }
+bool one_round_of_s64(int M, int N) { return (long)((M + 63) / 64) * ((N + 63) / 64) <= 256; }
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// Which kernel runs a GEMM, by variant (+ 100: the one-rounding QuickGELU, common.h quick_gelu_f32x2):
+// GEMM_TILE: tile height, K loop, cache hints and tile order.  ping_pong: the variant asks for the ping-pong loop and K is a whole
+// number of its two-K-tile iterations.
+void plan_tile(const GemmArgs& a, bool ping_pong, GemmPlan& p) {
+    const int tiles_n = (a.N + 255) / 256;
+    const double t256 = (double)((a.M + 255) / 256) * tiles_n, t128 = (double)((a.M + 127) / 128) * tiles_n;
+    auto rounds = [](double t) { return ceil(t / 256.0); };                   // of the 256 CUs
+    auto eff = [&](double t) { return t / (rounds(t) * 256.0); };
+    // Ping-pong K loop on 256-row tiles against the double-buffered loop on 128-row tiles: a round of 128-row tiles takes ~0.74 of a
+    // round of 256-row tiles (r02d, batch 256: out_proj 19.8 vs 26.6 us, c_proj 59 vs 78 us per round), so the big tile wins unless the
+    // small one saves a whole round -- e.g. 591 tiles (batch 256, N = 768): 3 rounds against 5 x 0.74; the CLS-only tail (6 tiles)
+    // stays on 128-row tiles.  Without the ping-pong loop: grids far below one round of CUs (the CLS-only tail of the last vision
+    // block: 512 rows): the smaller tile doubles the workgroups and shortens each K-tile (out_proj 22.5 -> 14.0 us, c_proj 67.7 -> 42.6
+    // us at 512 rows).
+    const bool big = ping_pong ? rounds(t256) <= 0.74 * rounds(t128) : t256 >= 64 && eff(t256) + 0.08 >= eff(t128);
+    // (r02q, measured and removed: running the rows beyond the last whole round of 256-row tiles as a second launch of 128-row
+    // tiles -- batch-256 inference, N = 768: 2.31 rounds -> 2 + 0.78 -- took 6 % off out_proj (81 -> 76 us) but added 2 % to
+    // c_proj (K = 3072: the small-tile round is no shorter there); 0.1 % of a step.)
+    p.tile_rows = big ? 256 : 128;
+    const int tiles = (int)(big ? t256 : t128);
+    const bool res = a.epi == EPI_BIAS_RES, lnf = a.epi == EPI_LN_BIAS || a.epi == EPI_LN_BIAS_QGELU;
+    // The ping-pong loop exists for 256-row tiles only.  Where it does not run: the loop with the iteration boundary inside the MFMA
+    // stream for the LayerNorm-folding launches (qkv_ln 354 -> 343 us, c_fc_ln 525 -> 518 us; the plain bias / QuickGELU launches of
+    // the same shapes do not gain) and for the residual projections with K >= 2048 (c_proj 467 -> 449 us; at K = 768, 12 K-tiles, it
+    // is neutral to 2 % slower); the double-buffered loop otherwise.
+    p.loop = ping_pong && big ? LOOP_PINGPONG : (lnf || (res && a.K >= 2048)) ? LOOP_BOUNDARY : LOOP_DOUBLE;
+    // Residual projections with N <= 1024 (at most four N tiles share an A panel): the A stream is loaded with the nontemporal policy
+    // so that it does not push the W panels every tile re-reads out of the L2 (out_proj 146 -> 141 us, c_proj 477 -> 459 us).  With
+    // 9-12 N tiles per A panel the same hint costs 6-11 %, and on the W operand it always costs.
+    p.a_nt = res && tiles_n <= 4 && tiles >= 512;
+    // C written with the nontemporal hint does not evict the A / W panels the other tiles of the XCD are streaming from its 4 MiB L2
+    // (profiles/r01g_gemm_epilogue.md).  Not for the in-place residual updates (out_proj / c_proj: +4 % slower) nor for small outputs
+    // the next kernel reads straight back (logits for the argmax); the fused argmax stores no C at all.
+    p.nt_store = !res && a.epi != EPI_SCALE_ARGMAX && (size_t)a.M * a.N * 2 >= ((size_t)48 << 20);
+    // Tile order.  Measured (profiles/r01e_gemm_experiments.md): groups of 4-6 N tiles raise the L2 hit rate of qkv / c_fc from
+    // 65-68 % to 72-73 % but move the run time by < 2 %, and hurt c_proj: the order stays row-major (all N tiles in one group) --
+    // but with the ping-pong K loop (r02c, same-process A/B at batch 512) groups of 4 from 8 N tiles on take 1.5-2.5 % off qkv / c_fc
+    // (c_fc_ln 496 -> 484 us, qkv_ln 329 -> 325 us), nothing off the N = 768 shapes
+    p.n_group = p.loop == LOOP_PINGPONG && tiles_n >= 8 ? 4 : tiles_n;
+}
+
+}  // namespace
+
+bool gemm_f16_latency_bound(int variant, int M, int N) { return variant == 8 && one_round_of_s64(M, N); }
+int gemm_f16_pinned_variant(int variant, int M, int N) { return variant != 8 ? variant : one_round_of_s64(M, N) ? 9 : 7; }
+
+// Which kernel runs a GEMM, by variant (+ 100: the one-rounding QuickGELU, common.h quick_gelu_f32x2; the engine sets
+// GemmArgs::gelu_mode itself):
 //   0            the 128 x 128 register-staged kernel above for every shape;
 //   6            256-row tiles (gemm_f16_v5.hip) with the double-buffered K loop;
 //   8 (default)  256-row tiles with the ping-pong K loop, and the 64 x 64 split-K kernel (gemm_f16_small.hip) for latency-bound
-//                shapes (gemm_f16_is_small);
+//                shapes (one_round_of_s64);
 //   7            8 without the split-K kernel; 9: the split-K kernel wherever it takes the shape (both: tests, and the engine's
-//                K/V + Q launches, which pin the kernel the all-token launch would take).
-// A kernel that does not take a shape (M < 256, N < 128, K not a multiple of 128 ...) hands on: split-K -> 256-row -> 128 x 128.
-// What only the 256-row kernel does -- patch rows gathered from the image, the fused row argmax, the LayerNorm fold and its
-// statistics -- runs there under every variant (0 / 7 / 9: with the loop of 8); -4: shape not supported.
+//                K/V + Q launches, gemm_f16_pinned_variant).
+// The first kernel that takes the shape runs: split-K (K a multiple of 128, no positional add) -> 256-row (M >= 256, N >= 128,
+// 16-byte rows, 31-bit operand offsets) -> 128 x 128.  What only the 256-row kernel does -- patch rows gathered from the image, the
+// fused row argmax, the LayerNorm fold and its statistics -- runs there under every variant (0 / 7 / 9: with the loop of 8), and
+// is -4 on a shape it does not take.  -2: K, a stride or a tile-only feature's operands; -5: a variant without a K loop; -3: epilogue.
+GemmPlan gemm_f16_route(const GemmArgs& a, int variant) {
+    GemmPlan p = {};
+    auto run = [&p](int kernel, int rc = 0) { p.kernel = kernel; p.rc = rc; return p; };
+    auto none = [&run](int rc) { return run(GEMM_NONE, rc); };
+    const bool lnf = a.epi == EPI_LN_BIAS || a.epi == EPI_LN_BIAS_QGELU, res = a.epi == EPI_BIAS_RES, argmax = a.epi == EPI_SCALE_ARGMAX;
+    if (a.epi == EPI_BIAS_QGELU || a.epi == EPI_LN_BIAS_QGELU) p.gelu_mode = variant >= 100 ? variant / 100 : a.gelu_mode;
+    if (variant >= 100) variant %= 100;
+    if (a.M <= 0 || a.N <= 0) return none(0);
+    if (a.K <= 0 || (a.K % BK) != 0 || (a.lda & 7) || (a.ldw & 7)) return none(-2);  // caller pads K to 64
+    const bool tile_only = a.im2col_R || argmax || lnf || a.stats_out;
+    if (!tile_only && (variant == 9 || gemm_f16_latency_bound(variant, a.M, a.N)) && (a.K % 128) == 0 && aligned16(a.A) && aligned16(a.W) && a.epi != EPI_PATCH &&
+        a.epi >= EPI_NONE && a.epi <= EPI_SCALE) {
+        const int steps = a.K >> 7, tiles = ((a.M + 63) >> 6) * ((a.N + 63) >> 6);      // K-steps of 32 per wave; workgroups
+        // D = 4 (32 loads in flight per lane, 284 registers: one wave per SIMD) while the grid leaves at most one workgroup per CU
+        // anyway (the shapes variant 8 sends here); larger grids (variant 9 in the tests) keep two workgroups per CU resident (D <= 3)
+        p.depth = steps % 4 == 0 && tiles <= 256 ? 4 : steps % 3 == 0 ? 3 : steps % 2 == 0 ? 2 : 1;
+        p.groups = steps / p.depth;
+        return run(GEMM_S64);
+    }
+    const bool takes = a.M >= 256 && a.N >= 128 && (long)a.M * a.lda * 2 < 0x7fffffffL && (long)a.N * a.ldw * 2 < 0x7fffffffL &&
+                       (argmax ? a.argmax_out != nullptr
+                               : !(a.N & 7) && !(a.ldc & 7) && aligned16(a.C) && (!res || (!(a.ldres & 7) && aligned16(a.res))));
+    if ((tile_only || variant >= 1) && takes) {
+        if (a.im2col_R) {                                  // A = fp16 images [B, 3, R, R], 16 x 16 patches: K = 768, byte offsets in 32 bits
+            const int G = a.im2col_R >> 4;
+            if (a.epi != EPI_PATCH || a.K != 768 || (a.im2col_R & 15) || a.rows_in != G * G || !aligned16(a.A) ||
+                (long)((a.M + a.rows_in - 1) / a.rows_in) * 3 * a.im2col_R * a.im2col_R * 2 >= 0xffffffffL)
+                return none(-2);
+        }
+        if (lnf && ((a.N & 63) || !a.ln_stats || a.ln_slots < 1 || !a.ln_g || !a.ln_b)) return none(-2);
+        if (a.stats_out && (!res || (a.N & 255))) return none(-2);
+        const int loop = (variant == 0 || variant == 7 || variant == 9) ? 8 : variant;   // K loop of the 256-row kernel
+        if (loop != 6 && loop != 8) return none(-5);
+        if (a.epi < EPI_NONE || a.epi > EPI_SCALE_ARGMAX) return none(-3);
+        plan_tile(a, loop == 8 && (a.K % 128) == 0, p);   // ping-pong K loop: two K-tiles per iteration
+        return run(GEMM_TILE);
+    }
+    if (tile_only) return none(-4);
+    if (a.epi < EPI_NONE || a.epi > EPI_SCALE) return none(-3);
+    return run(GEMM_T128);
+}
+
+// The route for a launch with 16-byte-aligned operands, lda = ldw = K and every operand a tile-only feature needs present (no GPU).
+// im2col: the image side R, 0 = none.  out[10]: the GemmPlan, field by field (include/ovmr_hip.h).
+extern "C" int ovmr_debug_gemm_route(int variant, int M, int N, int K, int epi, int ldc, int ldres, int stats, int im2col, int* out) {
+    static float operand[4];
+    alignas(16) static char base[16];
+    GemmArgs a = {};
+    a.M = M; a.N = N; a.K = a.lda = a.ldw = K; a.epi = epi; a.ldc = ldc; a.ldres = ldres;
+    a.A = a.W = a.res = base; a.C = base;
+    a.ln_stats = a.ln_g = a.ln_b = operand; a.ln_slots = 1; a.argmax_out = operand; a.stats_out = stats ? operand : nullptr;
+    a.im2col_R = im2col; a.rows_in = (im2col >> 4) * (im2col >> 4); a.rows_out = a.rows_in + 1;
+    static_assert(sizeof(GemmPlan) == 10 * sizeof(int), "");
+    *(GemmPlan*)out = gemm_f16_route(a, variant);
+    return 0;
+}
+
 int launch_gemm_f16(const GemmArgs& a_in, int variant, hipStream_t s) {
+    const GemmPlan p = gemm_f16_route(a_in, variant);
     GemmArgs a = a_in;
-    if (variant >= 100) {
-        a.gelu_mode = variant / 100;
-        variant %= 100;
+    a.n_group = p.n_group;
+    a.gelu_mode = p.gelu_mode;
+    switch (p.kernel) {
+        case GEMM_T128:
+#define X(E) if (a.epi == E) return launch_t128<E>(a, s);
+            X(EPI_NONE) X(EPI_BIAS) X(EPI_BIAS_QGELU) X(EPI_BIAS_RES) X(EPI_PATCH) X(EPI_SCALE)
+#undef X
+            return -3;
+        case GEMM_S64: return launch_gemm_f16_small(a, p, s);
+        case GEMM_TILE: return launch_gemm_f16_v5(a, p, s);
     }
-    if (a.M <= 0 || a.N <= 0) return 0;
-    if (a.K <= 0 || (a.K % BK) != 0 || (a.lda & 7) || (a.ldw & 7)) return -2;  // caller pads K to 64
-    const int loop = (variant == 0 || variant == 7 || variant == 9) ? 8 : variant;   // K loop of the 256-row kernel
-    if (a.im2col_R || a.epi == EPI_SCALE_ARGMAX || a.epi == EPI_LN_BIAS || a.epi == EPI_LN_BIAS_QGELU || a.stats_out) {
-        const int rc = launch_gemm_f16_v5(a, loop, s);
-        return rc == -100 ? -4 : rc;
-    }
-    if (variant == 9 || (variant == 8 && gemm_f16_is_small(a.M, a.N))) {
-        const int rc = launch_gemm_f16_small(a, s);
-        if (rc != -100) return rc;
-    }
-    if (variant >= 1) {
-        const int rc = launch_gemm_f16_v5(a, loop, s);
-        if (rc != -100) return rc;
-    }
-    switch (a.epi) {
-        case EPI_NONE: return launch_t128<EPI_NONE>(a, s);
-        case EPI_BIAS: return launch_t128<EPI_BIAS>(a, s);
-        case EPI_BIAS_QGELU: return launch_t128<EPI_BIAS_QGELU>(a, s);
-        case EPI_BIAS_RES: return launch_t128<EPI_BIAS_RES>(a, s);
-        case EPI_PATCH: return launch_t128<EPI_PATCH>(a, s);
-        case EPI_SCALE: return launch_t128<EPI_SCALE>(a, s);
-    }
-    return -3;
+    return p.rc;
 }

@@ -13,9 +13,10 @@
 //     K-steps of 32 ahead (D x 8 loads of 16 bytes in flight per lane: the loop runs at the issue rate, not at one latency per step);
 //   * the four partial tiles are summed through LDS in wave order ((p0 + p1) + p2) + p3 -- deterministic -- wave w finishing
 //     rows 16 w .. 16 w + 15 of the tile with the shared epilogue (gemm_epi.h: same rounding points as the other kernels).
+// Which launches run here, and at which prefetch depth D, is decided by gemm_f16_route (gemm_f16.hip).
 // Same C^T accumulator convention as gemm_f16.hip: lane l owns row l & 15 and four consecutive columns 4 (l >> 4) ..+3.
-#include "common.h"
 #include "gemm_epi.h"
+#include "gemm_route.h"
 
 namespace {
 
@@ -107,32 +108,15 @@ __global__ __launch_bounds__(256) void gemm_f16_s64(GemmArgs a, int groups) {
     for (int j = 0; j < 4; ++j) epilogue_store<EPI>(a, m0 + w * 16 + fr, n0 + j * 16 + fg * 4, sum[j]);
 }
 
-template <int EPI>
-int launch_s64(const GemmArgs& a, hipStream_t s) {
-    const int steps = a.K >> 7;                                   // K-steps of 32 per wave
-    const int tiles = ((a.M + 63) >> 6) * ((a.N + 63) >> 6);
-    // D = 4 (32 loads in flight per lane, 284 registers: one wave per SIMD) while the grid leaves at most one workgroup per CU anyway
-    // (the shapes launch_gemm_f16 routes here); larger grids (variant 9 in the tests) keep two workgroups per CU resident (D <= 3)
-    if (steps % 4 == 0 && tiles <= 256) hipLaunchKernelGGL((gemm_f16_s64<EPI, 4>), dim3(tiles), dim3(256), 0, s, a, steps / 4);
-    else if (steps % 3 == 0) hipLaunchKernelGGL((gemm_f16_s64<EPI, 3>), dim3(tiles), dim3(256), 0, s, a, steps / 3);
-    else if (steps % 2 == 0) hipLaunchKernelGGL((gemm_f16_s64<EPI, 2>), dim3(tiles), dim3(256), 0, s, a, steps / 2);
-    else hipLaunchKernelGGL((gemm_f16_s64<EPI, 1>), dim3(tiles), dim3(256), 0, s, a, steps);
-    return (int)hipGetLastError();
-}
-
 }  // namespace
 
-// -100: shape / epilogue not taken (the caller falls back to the tile kernels).
-int launch_gemm_f16_small(const GemmArgs& a, hipStream_t s) {
-    if (a.K < 128 || (a.K & 127) || (a.lda & 7) || (a.ldw & 7) || ((uintptr_t)a.A & 15) || ((uintptr_t)a.W & 15) ||
-        a.im2col_R || a.stats_out)
-        return -100;
-    switch (a.epi) {
-        case EPI_NONE: return launch_s64<EPI_NONE>(a, s);
-        case EPI_BIAS: return launch_s64<EPI_BIAS>(a, s);
-        case EPI_BIAS_QGELU: return launch_s64<EPI_BIAS_QGELU>(a, s);
-        case EPI_BIAS_RES: return launch_s64<EPI_BIAS_RES>(a, s);
-        case EPI_SCALE: return launch_s64<EPI_SCALE>(a, s);
-    }
-    return -100;
+// every epilogue but the positional add, at every prefetch depth
+int launch_gemm_f16_small(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    const dim3 grid(((a.M + 63) >> 6) * ((a.N + 63) >> 6));
+#define X(E, D) if (a.epi == E && p.depth == D) hipLaunchKernelGGL((gemm_f16_s64<E, D>), grid, dim3(256), 0, s, a, p.groups); else
+#define DEPTHS(E) X(E, 1) X(E, 2) X(E, 3) X(E, 4)
+    DEPTHS(EPI_NONE) DEPTHS(EPI_BIAS) DEPTHS(EPI_BIAS_QGELU) DEPTHS(EPI_BIAS_RES) DEPTHS(EPI_SCALE) return -3;
+#undef DEPTHS
+#undef X
+    return (int)hipGetLastError();
 }

@@ -1,8 +1,10 @@
-// fp16 MFMA GEMM, variants 6 and 8 (the default): 256(128)x256x64 tiles, both operands streamed into LDS by LDS-DMA
-// (global_load_lds, 16 B per lane, XOR-swizzled 128-byte rows), 8 waves as 2 x 4.  K loops: variant 8 = the ping-pong loop
-// (four half-tiles per K-tile, counted vmcnt, the two wave rows one barrier apart: see OPT & 16 below; r02: qkv 369 -> 312,
-// c_fc 522 -> 461, c_proj 462 -> 387, out_proj 149 -> 132 us at batch 512); variant 6 = double buffer with a drain per K-tile
-// and software-pipelined fragment reads (also the fallback of 8 for an odd number of K-tiles and for 128-row tiles).
+// fp16 MFMA GEMM, the tile kernel of variants 6 and 8 (the default): 256(128)x256x64 tiles, both operands streamed into LDS by LDS-DMA
+// (global_load_lds, 16 B per lane, XOR-swizzled 128-byte rows), 8 waves as 2 x 4.  K loops: the ping-pong loop (four half-tiles per
+// K-tile, counted vmcnt, the two wave rows one barrier apart: see OPT_PINGPONG below; r02: qkv 369 -> 312, c_fc 522 -> 461,
+// c_proj 462 -> 387, out_proj 149 -> 132 us at batch 512); the double buffer with a drain per K-tile and software-pipelined fragment
+// reads; and that with the iteration boundary moved inside the MFMA stream (OPT_BOUNDARY).  Tile height, K loop and cache hints of a
+// launch are gemm_f16_route's decision (gemm_f16.hip, with the measurements behind each rule); the table at the end of this file holds
+// the instantiations it can ask for.
 //
 // Epilogue (measured with tools/gemm_bench.py variants 6 / 18 / 19, profiles/r01g_gemm_epilogue.md: with K = 768 the
 // epilogue was 24-44 % of the kernel, the K loop alone runs at 1.1-1.2 PFLOP/s):
@@ -13,21 +15,17 @@
 //     pairs; h(acc + bias) (+QuickGELU / scale / LN fold) is written to a per-wave LDS tile and read back row-major, so
 //     residual / positional rows are LOADED and results STORED 16 bytes per lane, 8 rows x 128 B per wave instruction;
 //   * residual rows (EPI_BIAS_RES) are requested before the accumulators are converted, not in front of each store;
-//   * large outputs are stored with the NONTEMPORAL hint (template bit 512): C then stops evicting the A / W panels the
+//   * large outputs are stored with the NONTEMPORAL hint (OPT_NT_STORE): C then stops evicting the A / W panels the
 //     other tiles of the XCD are streaming out of its 4 MiB L2 (qkv 404 -> 368 us, c_fc 587 -> 556 us);
 //   * EPI_BIAS_RES can emit per-row partial (sum, sum of squares) for the LayerNorm that follows (common.h);
 //   * ONE workgroup barrier in the epilogue (the staging tiles are wave-private; the barriers that used to separate the
 //     phases also drained the first half's global stores), packed fp32 / fp16 VALU forms, interior tiles without bounds
 //     compares.
-// K loop variants chosen per launch (launch_v5): the A stream with the nontemporal policy for the residual projections
-// (OPT & 1), and the iteration boundary moved inside the MFMA stream (OPT & 4) for K >= 2048 and the LN-folding launches.
 // Measured and removed (profiles/r01e_gemm_experiments.md, r01g_gemm_epilogue.md): L2 prefetch touches (every workgroup, and
 // designated prefetcher workgroups), staggered LDS-DMA issue, buffer_load ... lds, s_setprio around the MFMA stream, a
 // persistent one-workgroup-per-CU tile loop with the next tile's first K-tile prefetched under the epilogue, W fragments
 // straight from global memory, tile-contiguous C stores, residual as accumulator start value, x ping-pong buffers.
-#include "common.h"
-
-#include <algorithm>
+#include "gemm_route.h"
 
 namespace {
 
@@ -40,16 +38,21 @@ __device__ __forceinline__ float dpp_f32(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
 
-// OPT bits: 1 nontemporal LDS-DMA for the A operand, 4 K loop with the iteration boundary inside the MFMA stream,
-// 16 the ping-pong K loop (256-row tiles), 512 NT (nontemporal C stores), 2048 the fp32 QuickGELU form
+// OPT bits (the values are part of the kernels' names: bench.py, tests/test_isa_sync_templates.py)
+constexpr int OPT_A_NT = 1;           // nontemporal LDS-DMA for the A operand
+constexpr int OPT_BOUNDARY = 4;       // K loop with the iteration boundary inside the MFMA stream
+constexpr int OPT_PINGPONG = 16;      // the ping-pong K loop (256-row tiles)
+constexpr int OPT_NT_STORE = 512;     // nontemporal C stores (a template bit: the compiler merges a run-time branch around two stores of the
+                                      // same value and drops the hint)
+constexpr int OPT_GELU_F32 = 2048;    // the fp32 QuickGELU form
 template <int EPI, int MT, int OPT>
 __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_m, int tiles_n) {
     constexpr int BM = MT * 32;
     constexpr int A_BYTES = BM * 128, STAGE = (BM + BN5) * 128;
     constexpr int AJ = BM / 64;
-    constexpr bool NT = OPT & 512;
+    constexpr bool NT = OPT & OPT_NT_STORE;
     constexpr int EP = 128;                            // epilogue staging tile: 128-byte rows, swizzled 8-byte units (below)
-    constexpr bool GFAST = (OPT & 2048) != 0;          // QuickGELU: the one-rounding fp32 form (common.h quick_gelu_f32x2) instead of the reference's three fp16 rounding points
+    constexpr bool GFAST = (OPT & OPT_GELU_F32) != 0;  // QuickGELU: the one-rounding fp32 form (common.h quick_gelu_f32x2) instead of the reference's three fp16 rounding points
     constexpr bool LNF = EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_QGELU;   // LayerNorm folded into this GEMM (common.h)
     constexpr bool HAS_BIAS = EPI == EPI_BIAS || EPI == EPI_BIAS_QGELU || EPI == EPI_BIAS_RES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     const int wm = wave >> 2, wn = wave & 3;
 
     // block id -> tile.  XCD-aware: ids congruent mod 8 run on one XCD and get a contiguous range of tiles; inside the
-    // range N tiles come in groups of G with M fastest-but-one (a.n_group, see launch_v5).
+    // range N tiles come in groups of G with M fastest-but-one (a.n_group, set by gemm_f16_route).
     const int nwg = tiles_m * tiles_n;
     int bid = blockIdx.x;
     {
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
         char* base = smem + buf * STAGE;
 #pragma unroll
         for (int j = 0; j < AJ; ++j)
-            __builtin_amdgcn_global_load_lds((gptr_t)(a_tile(kt) + oa[j]), (lptr_t)(base + ldsA_w + j * 1024), 16, 0, (OPT & 1) ? 2 : 0);
+            __builtin_amdgcn_global_load_lds((gptr_t)(a_tile(kt) + oa[j]), (lptr_t)(base + ldsA_w + j * 1024), 16, 0, (OPT & OPT_A_NT) ? 2 : 0);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             __builtin_amdgcn_global_load_lds((gptr_t)((const char*)W + ob[j] + (long)kt * 128), (lptr_t)(base + ldsB_w + j * 1024), 16, 0, 0);
@@ -147,10 +150,12 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     const int b_row_off = A_BYTES + (wn * 64 + fr) * 128;
     const int ch0 = ((fg) ^ (fr & 7)) << 4, ch1 = ((4 + fg) ^ (fr & 7)) << 4;
 
-    constexpr bool PH8 = (OPT & 16) != 0 && MT == 8;
+    constexpr bool PH8 = (OPT & OPT_PINGPONG) != 0 && MT == 8;
     if (!PH8) stage(0, 0);
 
-    // epilogue constants -> LDS, under the latency of the first K-tile (first read after the K loop: many barriers later)
+    // epilogue constants -> LDS, under the latency of the first K-tile (first read after the K loop: many barriers later).  (The same
+    // block stands in the ping-pong prologue below: as one lambda called at both points it changed the register allocation and the
+    // schedule of every kernel with a bias or a LayerNorm fold.)
     if (PH8) {
     } else if (tid < BN5) {
         const int n = n0 + tid;
@@ -173,9 +178,9 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
         row_c[BM + r] = -rstd * mean;
     }
 
-    if constexpr ((OPT & 16) != 0 && MT == 8) {
+    if constexpr (PH8) {
     // ------------------------------------------------------------------------------------------------------------------
-    // Ping-pong K loop (OPT & 16; the 256x256 tile only), after the CDNA4 guide's "256^2 8-phase template":
+    // Ping-pong K loop (OPT_PINGPONG; the 256x256 tile only), after the CDNA4 guide's "256^2 8-phase template":
     //   * a K-tile is staged as FOUR 16 KiB half-tiles -- B0, A0, B1, A1 -- into 2 x 4 LDS slots (128 KiB as before);
     //     A half h holds the tile rows wm*128 + h*64 + [0,64) of BOTH wave rows, B half g the tile columns
     //     wn*64 + g*32 + [0,32) of all four wave columns, so every wave works on the same half-tiles at the same time
@@ -227,7 +232,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
         for (int j = 0; j < 2; ++j) {
             const unsigned dst = smem_lds + (unsigned)(buf * KBUF + which * SLOT + j * 1024) + wave_lds;   // scalar arithmetic only
             if (which & 1) {
-                if constexpr ((OPT & 1) != 0) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" :: "v"(sa8[hf][j]), "s"(ak), "s"(dst) : "memory", "m0");
+                if constexpr ((OPT & OPT_A_NT) != 0) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 nt" :: "v"(sa8[hf][j]), "s"(ak), "s"(dst) : "memory", "m0");
                 else asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(sa8[hf][j]), "s"(ak), "s"(dst) : "memory", "m0");
             } else {
                 asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(sb8[hf][j]), "s"(wk), "s"(dst) : "memory", "m0");
@@ -353,7 +358,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     __builtin_amdgcn_sched_barrier(0);
 #undef OVMR_PH_END
     } else
-    if (OPT & 4) {
+    if (OPT & OPT_BOUNDARY) {
     // K loop with the iteration boundary moved INSIDE the MFMA stream.  All of a K-tile's fragment reads are issued two steps
     // before its last MFMAs, so the wait for the next tile's LDS-DMA, the workgroup barrier, the next tile's first six fragment
     // reads and the LDS-DMA issue for the tile after it all happen in front of the last two steps (8 MFMAs per wave): the matrix
@@ -709,127 +714,38 @@ int launch_v5_k(const GemmArgs& b, int tiles_m, int tiles_n, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
-template <int EPI, int MT, int OPT>
-int launch_v5(const GemmArgs& a, hipStream_t s) {
-    constexpr int BM = MT * 32;
-    const int tiles_m = (a.M + BM - 1) / BM, tiles_n = (a.N + BN5 - 1) / BN5;
-    GemmArgs b = a;
-    if (b.n_group <= 0) {
-        // measured (profiles/r01e_gemm_experiments.md): groups of 4-6 raise the L2 hit rate of qkv / c_fc from 65-68 %
-        // to 72-73 % but move the run time by < 2 %, and hurt c_proj; the default therefore stays row-major (G = all)
-        // with the ping-pong K loop (r02c, same-process A/B at batch 512): groups of 4 N tiles take 1.5-2.5 % off qkv / c_fc
-        // (c_fc_ln 496 -> 484 us, qkv_ln 329 -> 325 us), nothing off the N = 768 shapes
-        b.n_group = ((OPT & 16) && MT == 8 && tiles_n >= 8) ? 4 : tiles_n;
-    }
-    if (b.nt_store == 0) {
-        // C written with the nontemporal hint does not evict the A / W panels the other tiles of the XCD are streaming from
-        // its 4 MiB L2 (profiles/r01g_gemm_epilogue.md).  Not for the in-place residual updates (out_proj / c_proj: +4 %
-        // slower) nor for small outputs the next kernel reads straight back (logits for the argmax).  The hint has to be
-        // a template parameter: a run-time branch around two stores of the same value is merged by the compiler, which
-        // drops the hint.
-        b.nt_store = b.epi != EPI_BIAS_RES && (size_t)b.M * b.N * 2 >= ((size_t)48 << 20) ? 2 : 1;
-    }
-    constexpr int XB = OPT & 2048;                      // QuickGELU form: carried into every K-loop choice below
-    constexpr int P8 = OPT & (16 | XB);                 // ping-pong K loop (256-row tiles; it replaces the OPT & 4 loop there)
-    constexpr bool PLAIN = (OPT & ~(16 | XB)) == 0;
-    constexpr bool OV_OK = !((OPT & 16) && MT == 8);
-    if constexpr (PLAIN && OV_OK && (EPI == EPI_LN_BIAS || EPI == EPI_LN_BIAS_QGELU)) {
-        // the LayerNorm-folding launches also run the K loop with the boundary inside the MFMA stream (qkv_ln 354 -> 343 us,
-        // c_fc_ln 525 -> 518 us; the plain bias / QuickGELU launches of the same shapes do not gain)
-        if (b.nt_store == 2) return launch_v5_k<EPI, MT, XB | 4 | 512>(b, tiles_m, tiles_n, s);
-        return launch_v5_k<EPI, MT, XB | 4>(b, tiles_m, tiles_n, s);
-    }
-    if constexpr (PLAIN && EPI != EPI_BIAS_RES) {
-        if (b.nt_store == 2) return launch_v5_k<EPI, MT, P8 | 512>(b, tiles_m, tiles_n, s);
-    }
-    if constexpr (PLAIN && EPI == EPI_BIAS_RES) {
-        // Residual projections.
-        // (1) N <= 1024 (at most four N tiles share an A panel): the A stream is loaded with the nontemporal policy so that it
-        //     does not push the W panels every tile re-reads out of the L2 (out_proj 146 -> 141 us, c_proj 477 -> 459 us).  With
-        //     9-12 N tiles per A panel the same hint costs 6-11 %, and on the W operand it always costs.
-        // (2) K >= 2048: the K loop with the iteration boundary inside the MFMA stream (OPT & 4): c_proj 467 -> 449 us; at
-        //     K = 768 (12 K-tiles) it is neutral to 2 % slower.
-        const bool a_nt = tiles_n <= 4 && tiles_m * tiles_n >= 512;
-        const bool ov = OV_OK && b.K >= 2048;
-        if (a_nt && ov) return launch_v5_k<EPI, MT, XB | 5>(b, tiles_m, tiles_n, s);
-        if (ov) return launch_v5_k<EPI, MT, XB | 4>(b, tiles_m, tiles_n, s);
-        if (a_nt) return launch_v5_k<EPI, MT, P8 | 1>(b, tiles_m, tiles_n, s);
-    }
-    return launch_v5_k<EPI, MT, OPT>(b, tiles_m, tiles_n, s);
-}
-
-template <int EPI, int OPT>
-int pick_v5(const GemmArgs& a, hipStream_t s) {
-    auto eff = [&](int bm) {
-        const double t = (double)((a.M + bm - 1) / bm) * ((a.N + BN5 - 1) / BN5);
-        return t / (ceil(t / 256.0) * 256.0);
-    };
-    const double t256 = (double)((a.M + 255) / 256) * ((a.N + BN5 - 1) / BN5);
-    bool big;
-    if ((OPT & 16) && (a.K % 128) == 0) {
-        // ping-pong K loop on 256-row tiles against the double-buffered loop on 128-row tiles: a round of 128-row tiles takes
-        // ~0.74 of a round of 256-row tiles (r02d, batch 256: out_proj 19.8 vs 26.6 us, c_proj 59 vs 78 us per round), so the
-        // big tile wins unless the small one saves a whole round -- e.g. 591 tiles (batch 256, N = 768): 3 rounds against
-        // 5 x 0.74; the CLS-only tail (6 tiles) stays on 128-row tiles.
-        const double t128 = (double)((a.M + 127) / 128) * ((a.N + BN5 - 1) / BN5);
-        big = ceil(t256 / 256.0) <= 0.74 * ceil(t128 / 256.0);
-    } else {
-        // grids far below one round of CUs (the CLS-only tail of the last vision block: 512 rows): the smaller tile doubles the
-        // workgroups and shortens each K-tile (out_proj 22.5 -> 14.0 us, c_proj 67.7 -> 42.6 us at 512 rows)
-        big = t256 >= 64 && eff(256) + 0.08 >= eff(128);
-    }
-    // (r02q, measured and removed: running the rows beyond the last whole round of 256-row tiles as a second launch of 128-row
-    // tiles -- batch-256 inference, N = 768: 2.31 rounds -> 2 + 0.78 -- took 6 % off out_proj (81 -> 76 us) but added 2 % to
-    // c_proj (K = 3072: the small-tile round is no shorter there); 0.1 % of a step.)
-    return big ? launch_v5<EPI, 8, OPT>(a, s) : launch_v5<EPI, 4, OPT>(a, s);
-}
-
-template <int EPI, int OPT>
-int pick_gelu(const GemmArgs& a, hipStream_t s) {      // QuickGELU form (GemmArgs::gelu_mode) -> template bit 2048
-    return a.gelu_mode ? pick_v5<EPI, OPT | 2048>(a, s) : pick_v5<EPI, OPT>(a, s);
-}
-
-template <int OPT>
-int dispatch_v5(const GemmArgs& a, hipStream_t s) {
-    switch (a.epi) {
-        case EPI_NONE: return pick_v5<EPI_NONE, OPT>(a, s);
-        case EPI_BIAS: return pick_v5<EPI_BIAS, OPT>(a, s);
-        case EPI_BIAS_QGELU: return pick_gelu<EPI_BIAS_QGELU, OPT>(a, s);
-        case EPI_BIAS_RES: return pick_v5<EPI_BIAS_RES, OPT>(a, s);
-        case EPI_PATCH: return pick_v5<EPI_PATCH, OPT>(a, s);
-        case EPI_SCALE: return pick_v5<EPI_SCALE, OPT>(a, s);
-        case EPI_LN_BIAS: return pick_v5<EPI_LN_BIAS, OPT>(a, s);
-        case EPI_LN_BIAS_QGELU: return pick_gelu<EPI_LN_BIAS_QGELU, OPT>(a, s);
-        case EPI_SCALE_ARGMAX: return pick_v5<EPI_SCALE_ARGMAX, OPT>(a, s);
-    }
-    return -3;
-}
+// Every instantiation gemm_f16_route can ask for, and no other: X(epilogue, MT, OPT).  The ping-pong loop exists for MT = 8 only;
+// F: the bits every entry of the group carries.  Residual projections: never the store hint; the boundary loop (K >= 2048) and the
+// nontemporal A stream.  LayerNorm fold: the boundary loop wherever the ping-pong loop does not run.  The argmax stores no C.
+#define V5_DOUBLE_PP(X, E, F) X(E, 4, (F)) X(E, 8, (F)) X(E, 8, (F) | OPT_PINGPONG)
+#define V5_BOUNDARY(X, E, F) X(E, 4, (F) | OPT_BOUNDARY) X(E, 8, (F) | OPT_BOUNDARY)
+#define V5_STORES(X, LOOPS, E, F) LOOPS(X, E, (F)) LOOPS(X, E, (F) | OPT_NT_STORE)
+#define V5_BOUNDARY_PP(X, E, F) V5_BOUNDARY(X, E, F) X(E, 8, (F) | OPT_PINGPONG)
+#define V5_TABLE(X)                                                                                                                \
+    V5_STORES(X, V5_DOUBLE_PP, EPI_NONE, 0) V5_STORES(X, V5_DOUBLE_PP, EPI_BIAS, 0)                                                 \
+    V5_STORES(X, V5_DOUBLE_PP, EPI_PATCH, 0) V5_STORES(X, V5_DOUBLE_PP, EPI_SCALE, 0)                                               \
+    V5_STORES(X, V5_DOUBLE_PP, EPI_BIAS_QGELU, 0) V5_STORES(X, V5_DOUBLE_PP, EPI_BIAS_QGELU, OPT_GELU_F32)                          \
+    V5_DOUBLE_PP(X, EPI_BIAS_RES, 0) V5_DOUBLE_PP(X, EPI_BIAS_RES, OPT_A_NT) V5_BOUNDARY(X, EPI_BIAS_RES, 0) V5_BOUNDARY(X, EPI_BIAS_RES, OPT_A_NT) \
+    V5_STORES(X, V5_BOUNDARY_PP, EPI_LN_BIAS, 0) V5_DOUBLE_PP(X, EPI_SCALE_ARGMAX, 0)                                               \
+    V5_STORES(X, V5_BOUNDARY_PP, EPI_LN_BIAS_QGELU, 0) V5_STORES(X, V5_BOUNDARY_PP, EPI_LN_BIAS_QGELU, OPT_GELU_F32)
 
 }  // namespace
 
-// variant 8: the default (ping-pong K loop); 6: the double-buffered K loop (also what 8 runs for an odd number of K-tiles and
-// for 128-row tiles)
-int launch_gemm_f16_v5(const GemmArgs& a, int variant, hipStream_t s) {
-    if (a.epi == EPI_SCALE_ARGMAX) {
-        if (a.M < 256 || a.N < 128 || !a.argmax_out || (long)a.M * a.lda * 2 >= 0x7fffffffL || (long)a.N * a.ldw * 2 >= 0x7fffffffL)
-            return -100;
-    } else
-    if (a.M < 256 || a.N < 128 || (a.N & 7) || (a.ldc & 7) || (a.epi == EPI_BIAS_RES && (a.ldres & 7)) ||
-        ((uintptr_t)a.C & 15) || (a.epi == EPI_BIAS_RES && ((uintptr_t)a.res & 15)) ||
-        (long)a.M * a.lda * 2 >= 0x7fffffffL || (long)a.N * a.ldw * 2 >= 0x7fffffffL)
-        return -100;
-    if (a.im2col_R) {                                  // A = fp16 images [B, 3, R, R], 16 x 16 patches: K = 768, byte offsets in 32 bits
-        const int G = a.im2col_R >> 4;
-        if (a.epi != EPI_PATCH || a.K != 768 || (a.im2col_R & 15) || a.rows_in != G * G || ((uintptr_t)a.A & 15) ||
-            (long)((a.M + a.rows_in - 1) / a.rows_in) * 3 * a.im2col_R * a.im2col_R * 2 >= 0xffffffffL)
-            return -2;
-    }
-    const bool lnf = a.epi == EPI_LN_BIAS || a.epi == EPI_LN_BIAS_QGELU;
-    if (lnf && ((a.N & 63) || !a.ln_stats || a.ln_slots < 1 || !a.ln_g || !a.ln_b)) return -2;
-    if (a.stats_out && (a.epi != EPI_BIAS_RES || (a.N & 255))) return -2;
-    switch (variant) {
-        case 6: return dispatch_v5<0>(a, s);
-        case 8: return (a.K % 128) == 0 ? dispatch_v5<16>(a, s) : dispatch_v5<0>(a, s);   // ping-pong K loop: two K-tiles per iteration
-        default: return -5;                                                                // unknown variant
-    }
+int launch_gemm_f16_v5(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+    const int mt = p.tile_rows / 32, tiles_m = (a.M + p.tile_rows - 1) / p.tile_rows, tiles_n = (a.N + BN5 - 1) / BN5;
+    const int opt = (p.a_nt ? OPT_A_NT : 0) | (p.loop == LOOP_BOUNDARY ? OPT_BOUNDARY : 0) | (p.loop == LOOP_PINGPONG ? OPT_PINGPONG : 0) |
+                    (p.nt_store ? OPT_NT_STORE : 0) | (p.gelu_mode ? OPT_GELU_F32 : 0);
+#define X(E, MT, OPT) if (a.epi == E && mt == MT && opt == (OPT)) return launch_v5_k<E, MT, (OPT)>(a, tiles_m, tiles_n, s);
+    V5_TABLE(X)
+#undef X
+    return -3;
+}
+
+// (epilogue, MT, OPT) of every entry of the table, for tests/test_gemm_route_cpu.py: returns their number, writes at most `cap`.
+extern "C" int ovmr_debug_gemm_tile_kernels(int* out, int cap) {
+    int n = 0;
+#define X(E, MT, OPT) if (n < cap) { out[3 * n] = E; out[3 * n + 1] = MT; out[3 * n + 2] = (OPT); } ++n;
+    V5_TABLE(X)
+#undef X
+    return n;
 }

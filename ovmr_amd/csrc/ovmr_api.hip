@@ -2,7 +2,7 @@
 // sequences of the OVMR hot path.  No call in the compute entry points allocates, copies to the
 // host or synchronises, so every one of them can be captured into a hipGraph by the caller.
 #include "../../include/ovmr_hip.h"
-#include "common.h"
+#include "gemm_route.h"
 
 #include <algorithm>
 #include <cmath>
@@ -224,10 +224,10 @@ struct HeadWs : Carver {
 };
 
 // LayerNorm folding applies when the v5 GEMM takes the shape (it then also emits the statistics): see common.h.
-// Not for latency-bound passes (gemm_f16_is_small: the N = W launches -- out_proj, c_proj -- then take the 64 x 64 split-K kernel,
-// which emits no statistics; the separate LayerNorm kernel costs ~4 us there).
+// Not for latency-bound passes (the N = W launches -- out_proj, c_proj -- then take the 64 x 64 split-K kernel under the default
+// variant, which emits no statistics; the separate LayerNorm kernel costs ~4 us there).
 bool can_fold_ln(const ovmr_handle* h, const Block& k, int M, int W) {
-    return h->ln_fold && k.in_wf && M >= 256 && (W % 256) == 0 && W / 256 <= 64 && !(h->gemm_variant == 8 && gemm_f16_is_small(M, W));
+    return h->ln_fold && k.in_wf && M >= 256 && (W % 256) == 0 && W / 256 <= 64 && !gemm_f16_latency_bound(h->gemm_variant, M, W);
 }
 
 GemmArgs gemm_ln(GemmArgs a, const float* stats, int slots, const float* g, const float* b) {
@@ -271,11 +271,11 @@ struct LnPart { int r0, n, M, step; half_t* C; int ldc; };
 int ln_linear(ovmr_handle* h, const LnLinear& l, const half_t* x, half_t* y, int rows, int W, const float* stats, int variant,
               std::initializer_list<LnPart> parts, hipStream_t s) {
     if (!stats) CK(launch_layernorm(x, y, l.ln_g, l.ln_b, rows, W, W, 0, s));
-    if (l.gelu && !h->gelu_exact) variant += 100;            // the one-rounding QuickGELU (common.h quick_gelu_f32x2)
     const int slots = W / 256, epi = l.gelu ? (stats ? EPI_LN_BIAS_QGELU : EPI_BIAS_QGELU) : (stats ? EPI_LN_BIAS : EPI_BIAS);
     for (const LnPart& p : parts) {
         GemmArgs a = gemm(stats ? x : y, p.step * W, (stats ? l.wf : l.w) + (size_t)p.r0 * W, W, p.C, p.ldc, p.M, p.n, W, epi, stats ? nullptr : l.b + p.r0);
         if (stats) { a = gemm_ln(a, stats, slots, l.g + p.r0, l.bf + p.r0); a.ln_stride = p.step * slots; }
+        a.gelu_mode = l.gelu && !h->gelu_exact;              // the one-rounding QuickGELU (common.h quick_gelu_f32x2)
         CK(launch_gemm_f16(a, variant, s));
     }
     return 0;
@@ -301,10 +301,10 @@ int run_block_f16(ovmr_handle* h, const Block& k, half_t* x, half_t* y, half_t* 
         // ... and of the in-projection itself only K and V are needed for every token: with at least 256 images (a full row tile of
         // CLS rows) the Q third runs as its own launch over the CLS rows (A and C strided by a sequence; bit-identical values),
         // a third of this block's largest GEMM less.  Both launches take the kernel the all-token launch of last_q_cls = 0 would
-        // take -- the split-K kernel, 9, if [M, 3W] is a latency-bound shape, else the tile kernels, 7 -- so that the K summation
+        // take (gemm_f16_pinned_variant: the split-K kernel if [M, 3W] is a latency-bound shape, else the tile kernels) so that the K summation
         // order, and with it every bit, is the same either way (folded launches run the 256-row kernel under either number).
-        const int v = h->gemm_variant != 8 ? h->gemm_variant : (gemm_f16_is_small(M, 3 * W) ? 9 : 7);
-        CK(ln_linear(h, in_proj(k), x, y, M, W, stats, v, {{W, 2 * W, M, 1, qkv + W, 3 * W}, {0, W, nseq, L, qkv, L * 3 * W}}, s));
+        CK(ln_linear(h, in_proj(k), x, y, M, W, stats, gemm_f16_pinned_variant(h->gemm_variant, M, 3 * W),
+                     {{W, 2 * W, M, 1, qkv + W, 3 * W}, {0, W, nseq, L, qkv, L * 3 * W}}, s));
     } else
         CK(ln_linear(h, in_proj(k), x, y, M, W, stats, h->gemm_variant, {{0, 3 * W, M, 1, qkv, 3 * W}}, s));
     if (cls_rows)

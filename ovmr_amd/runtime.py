@@ -86,6 +86,8 @@ SIGNATURES = {
                                       c_i, c_p]),
     "ovmr_debug_attention_q": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "ovmr_debug_attention_route": (c_i, [c_i, c_i, c_i, c_i]),
+    "ovmr_debug_gemm_route": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i)]),
+    "ovmr_debug_gemm_tile_kernels": (c_i, [ctypes.POINTER(c_i), c_i]),
 }
 
 _lib = None

@@ -36,44 +36,82 @@ CHEAP_FP64 = 1 << 32                    # M * N * K up to which the fp64 product
 STATS_MAX = 64.0
 
 
-# ---- which kernel instantiation a launch runs: launch_gemm_f16, gemm_f16_is_small, launch_gemm_f16_small / launch_s64,
-# ---- launch_gemm_f16_v5, pick_v5 and launch_v5 as they stand, restated --------------------------------------------------------------
+# ---- which kernel instantiation a launch runs: the dispatcher as it stood BEFORE the library had a routing function -- launch_gemm_f16
+# ---- trying the split-K launcher, the tile kernel's launcher and the 128 x 128 kernel in turn, each with its own shape test, and the
+# ---- tile launcher's chain of tile height, K loop and hints -- restated branch by branch, in that order.  The library's gemm_f16_route
+# ---- (csrc/gemm_f16.hip) is held to this by test_gemm_route_cpu.py; nothing here calls the library. ----
+
+EPI_LN_BIAS, EPI_LN_BIAS_QGELU, EPI_SCALE_ARGMAX = 6, 7, 8
+
 
 def is_small(M, N):
     return ((M + 63) // 64) * ((N + 63) // 64) <= 256
 
 
-def _route_v5(loop, M, N, K, epi, ldc, ldres):
-    """gemm_f16_v5.hip: None where launch_gemm_f16_v5 returns -100 (operand pointers are 16-byte aligned and lda = K here), else
+def _err(rc):
+    return ("err", rc)
+
+
+def _route_v5(loop, M, N, K, epi, ldc, ldres, stats=False, im2col=0):
+    """gemm_f16_v5.hip: None where the tile kernel's launcher did not take the shape and handed on (operand pointers are 16-byte aligned, lda = K and the operands of
+    the LayerNorm fold and the argmax are present here), ("err", rc) where it returned an error, else
     ("v5", tile rows, K loop, "a_nt" | "", "nt" | "", "g4" | "")."""
-    if M < 256 or N < 128 or (N & 7) or (ldc & 7) or (epi == EPI_BIAS_RES and (ldres & 7)) or M * K * 2 >= 0x7fffffff or N * K * 2 >= 0x7fffffff:
+    far = M * K * 2 >= 0x7fffffff or N * K * 2 >= 0x7fffffff
+    if epi == EPI_SCALE_ARGMAX:                                           # stores no C: no test of N & 7, ldc
+        if M < 256 or N < 128 or far:
+            return None
+    elif M < 256 or N < 128 or (N & 7) or (ldc & 7) or (epi == EPI_BIAS_RES and (ldres & 7)) or far:
         return None
-    pp = loop == 8 and K % 128 == 0                                       # launch_gemm_f16_v5: dispatch_v5<16>, else <0>
+    if im2col:                                                            # rows_in = (R / 16)^2 here
+        rows_in = (im2col >> 4) ** 2
+        if epi != EPI_PATCH or K != 768 or (im2col & 15) or (M + rows_in - 1) // rows_in * 3 * im2col * im2col * 2 >= 0xffffffff:
+            return _err(-2)
+    lnf = epi in (EPI_LN_BIAS, EPI_LN_BIAS_QGELU)
+    if lnf and (N & 63):
+        return _err(-2)
+    if stats and (epi != EPI_BIAS_RES or (N & 255)):
+        return _err(-2)
+    if loop not in (6, 8):
+        return _err(-5)
+    if not 0 <= epi <= 8:
+        return _err(-3)
+    pp = loop == 8 and K % 128 == 0                                       # the ping-pong loop is asked for: two K-tiles per iteration
     tn = (N + 255) // 256
     t256, t128 = ((M + 255) // 256) * tn, ((M + 127) // 128) * tn
-    if pp:                                                                # pick_v5
+    if pp:                                                                # tile height
         big = math.ceil(t256 / 256.0) <= 0.74 * math.ceil(t128 / 256.0)
     else:
         eff = lambda t: t / (math.ceil(t / 256.0) * 256.0)
         big = t256 >= 64 and eff(t256) + 0.08 >= eff(t128)
     bm = 256 if big else 128
     tm = (M + bm - 1) // bm
-    pp8 = pp and big                                                      # launch_v5 / the kernel: the ping-pong loop is for 256-row tiles
-    nt = epi != EPI_BIAS_RES and M * N * 2 >= (48 << 20)
+    pp8 = pp and big                                                      # the kernel: the ping-pong loop is for 256-row tiles
+    # the store hint: for every epilogue but BIAS_RES by size; the argmax epilogue stores nothing (its kernels with the bit
+    # and without were the same instructions): no hint
+    nt = epi not in (EPI_BIAS_RES, EPI_SCALE_ARGMAX) and M * N * 2 >= (48 << 20)
     a_nt = epi == EPI_BIAS_RES and tn <= 4 and tm * tn >= 512
-    ov = epi == EPI_BIAS_RES and not pp8 and K >= 2048
+    ov = not pp8 and (lnf or (epi == EPI_BIAS_RES and K >= 2048))         # the boundary loop: LayerNorm fold, or BIAS_RES at K >= 2048
     return ("v5", bm, "pingpong" if pp8 else "boundary" if ov else "double", "a_nt" if a_nt else "", "nt" if nt else "",
             "g4" if pp8 and tn >= 8 else "")
 
 
-def route(variant, M, N, K, epi, ldc=0, ldres=0, stats=False):
-    """The kernel a launch under `variant` runs: ("t128",), ("s64", prefetch depth D, K groups per wave) or _route_v5's tuple."""
+def route(variant, M, N, K, epi, ldc=0, ldres=0, stats=False, im2col=0):
+    """The kernel a launch under `variant` runs: ("t128",), ("s64", prefetch depth D, K groups per wave) or _route_v5's tuple; ("err", rc)
+    where the launch returns rc without one (0: empty shape).  variant + 100 runs the same kernel (one_rounding_gelu).  im2col: the
+    image side R of a patch-gathering launch."""
     ldc = ldc or N
     ldres = ldres or ldc
+    if variant >= 100:
+        variant %= 100
+    if M <= 0 or N <= 0:
+        return _err(0)
+    if K <= 0 or K % 64:
+        return _err(-2)
     loop = 8 if variant in (0, 7, 9) else variant
-    if stats:
-        return _route_v5(loop, M, N, K, epi, ldc, ldres)
-    if (variant == 9 or (variant == 8 and is_small(M, N))) and K >= 128 and K % 128 == 0 and epi != EPI_PATCH:
+    if im2col or stats or epi in (EPI_LN_BIAS, EPI_LN_BIAS_QGELU, EPI_SCALE_ARGMAX):   # what only the tile kernel does
+        r = _route_v5(loop, M, N, K, epi, ldc, ldres, stats, im2col)
+        return _err(-4) if r is None else r
+    if (variant == 9 or (variant == 8 and is_small(M, N))) and K >= 128 and K % 128 == 0 and epi in (EPI_NONE, EPI_BIAS, EPI_BIAS_QGELU, EPI_BIAS_RES, EPI_SCALE):
         steps, tiles = K >> 7, ((M + 63) >> 6) * ((N + 63) >> 6)
         D = 4 if steps % 4 == 0 and tiles <= 256 else 3 if steps % 3 == 0 else 2 if steps % 2 == 0 else 1
         return ("s64", D, steps // D)
@@ -81,7 +119,12 @@ def route(variant, M, N, K, epi, ldc=0, ldres=0, stats=False):
         r = _route_v5(loop, M, N, K, epi, ldc, ldres)
         if r is not None:
             return r
-    return ("t128",)
+    return ("t128",) if 0 <= epi <= EPI_SCALE else _err(-3)
+
+
+def one_rounding_gelu(variant, epi):
+    """variant + 100: the QuickGELU epilogues in the one-rounding form (the tile kernel: template bit 2048)."""
+    return variant >= 100 and epi in (EPI_BIAS_QGELU, EPI_LN_BIAS_QGELU)
 
 
 # ---- the cases -------------------------------------------------------------------------------------------------------------
@@ -136,7 +179,7 @@ CASES = [
     _f16(300, 1003, 3072, R_, {0: T128, 6: T128}),                         # N & 7, odd ldc = ldres
     _f16(6 * 49, 136, 128, P_, {0: T128}, rows=(49, 50)),                  # EPI_PATCH, rows_in -> rows_out = 49 -> 50
     _f16(4 * 196, 264, 192, P_, {0: T128, 6: _v5(128, "double"), 8: _v5(128, "double"), 9: _v5(128, "double")}, rows=(196, 197)),
-    # -- the split-K 64 x 64 kernel: variant 9 always, variant 8 when gemm_f16_is_small.  launch_s64: depth 4 if steps % 4 == 0 and at most
+    # -- the split-K 64 x 64 kernel: variant 9 always, variant 8 when is_small.  Depth 4 if steps % 4 == 0 and at most
     #    256 tiles, else 3 / 2 / 1 by divisibility; steps = K / 128 = 1, 2, 3, 5, 16, 24, 32; ragged M and N.
     _f16(63, 72, 128, N_, {8: ("s64", 1, 1), 9: ("s64", 1, 1)}),
     _f16(65, 130, 256, B_, {8: ("s64", 2, 1), 9: ("s64", 2, 1)}),
@@ -147,12 +190,12 @@ CASES = [
     _f16(64, 64, 4096, N_, {8: ("s64", 4, 8), 9: ("s64", 4, 8)}),
     _f16(65, 130, 192, B_, {8: T128, 9: T128}),                            # K % 128 != 0: the split-K kernel hands on (M < 256: to t128)
     _f16(300, 136, 320, R_, {8: _v5(128, "double"), 9: _v5(128, "double")}),  # ... and to the tile kernel
-    # -- more than 256 tiles of 64 x 64: variant 8 is past gemm_f16_is_small (18 x 16 = 288 tiles), variant 9 runs depth 2 / 3 there.
+    # -- more than 256 tiles of 64 x 64: variant 8 is past is_small (18 x 16 = 288 tiles), variant 9 runs depth 2 / 3 there.
     #    t256 = 20 < 64: 128-row tiles under 6; under 8 ceil(20/256) = 1 > 0.74 * ceil(36/256): 128-row tiles, double-buffered loop.
     _f16(1100, 1024, 128, R_, {6: _v5(128, "double"), 8: _v5(128, "double"), 9: ("s64", 1, 1)}),          # BIAS_RES: neither a_nt nor ov
     _f16(1100, 1024, 2048, R_, {6: _v5(128, "boundary"), 8: _v5(128, "boundary"), 9: ("s64", 2, 8)}),     # ov alone (K >= 2048, 128-row tiles)
     _f16(1100, 1000, 3072, B_, {9: ("s64", 3, 8), 8: _v5(128, "double")}),
-    # -- variant 6 and variant 8 off the ping-pong loop (K % 128 != 0): pick_v5's small-tile rule t256 >= 64 && eff(256) + 0.08 >= eff(128)
+    # -- variant 6 and variant 8 off the ping-pong loop (K % 128 != 0): the small-tile rule t256 >= 64 && eff(256) + 0.08 >= eff(128)
     _f16(300, 256, 64, B_, {6: _v5(128, "double"), 8: _v5(128, "double")}),                               # t256 = 2 < 64; ONE K-tile
     _f16(300, 256, 192, S_, {6: _v5(128, "double"), 8: _v5(128, "double")}),
     _f16(22 * 256 - 19, 768, 320, R_, {6: _v5(128, "double"), 8: _v5(128, "double")}),                    # t256 = 66 >= 64, eff .26 + .08 < .52
@@ -168,15 +211,15 @@ CASES = [
     _f16(44 * 256 - 19, 768, 384, B_, {8: _v5(256, "pingpong")}),                                         # tiles_n = 3; three iterations
     _f16(88 * 49, 2048, 128, P_, {8: _v5(256, "pingpong", g4="g4"), 6: _v5(256, "double")}, rows=(49, 50)),  # EPI_PATCH on 256-row tiles
     _f16(_PP_M, 2048, 128, R_, {8: _v5(256, "pingpong", g4="g4"), 6: _v5(256, "double")}),                # BIAS_RES in place, neither a_nt nor ov
-    _f16(_PP_M, 2048, 2048, R_, {6: _v5(256, "boundary"), 8: _v5(256, "pingpong", g4="g4")}),             # ov alone on 256-row tiles (variant 6: OV_OK)
+    _f16(_PP_M, 2048, 2048, R_, {6: _v5(256, "boundary"), 8: _v5(256, "pingpong", g4="g4")}),             # ov alone on 256-row tiles (variant 6: no ping-pong loop)
     # -- BIAS_RES in place with the nontemporal A stream: tiles_n <= 4 and at least 512 tiles.
     #    130 900 x 128: 512 tiles of 256 rows (eff 1.0 under 6; 2 <= 0.74 * 4 under 8): a_nt alone, OPT 1 and OPT 16 | 1.
     _f16(130900, 128, 128, R_, {6: _v5(256, "double", "a_nt"), 8: _v5(256, "pingpong", "a_nt")}),
     #    43 600 x 520: t256 = 513 -> 3 rounds, t128 = 1023 -> 4: 3 > 0.74 * 4, the one window where variant 8 prefers 128-row tiles at
     #    512 tiles or more (the engine's batch 221 of 197-token images); under 6 eff .67 + .08 < 1.0 as well.
-    _f16(43600, 520, 128, R_, {6: _v5(128, "double", "a_nt"), 8: _v5(128, "double", "a_nt")}),            # a_nt alone (P8 | 1)
-    _f16(43600, 520, 2048, R_, {6: _v5(128, "boundary", "a_nt"), 8: _v5(128, "boundary", "a_nt")}),       # a_nt and ov (XB | 5)
-    #    32 700 x 1000: 128 x 4 = 512 tiles of 256 rows; under variant 6 ov holds on 256-row tiles too: XB | 5 with MT = 8
+    _f16(43600, 520, 128, R_, {6: _v5(128, "double", "a_nt"), 8: _v5(128, "double", "a_nt")}),            # a_nt alone (OPT 1)
+    _f16(43600, 520, 2048, R_, {6: _v5(128, "boundary", "a_nt"), 8: _v5(128, "boundary", "a_nt")}),       # a_nt and ov (OPT 5)
+    #    32 700 x 1000: 128 x 4 = 512 tiles of 256 rows; under variant 6 ov holds on 256-row tiles too: OPT 5 with MT = 8
     _f16(32700, 1000, 2048, R_, {6: _v5(256, "boundary", "a_nt"), 8: _v5(256, "pingpong", "a_nt")}),
     # -- nontemporal stores: M * N * 2 >= 48 MiB, every epilogue but BIAS_RES / PATCH; K = 128.
     #    8200 x 3072: 256-row tiles (396 -> 2 <= 0.74 * 4; eff .77 + .08 >= .76); 10 800 x 3072: 128-row tiles (516 -> 3 > 0.74 * 4; .67 + .08 < 1.0)

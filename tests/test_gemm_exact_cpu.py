@@ -1,5 +1,5 @@
 """CPU companion of test_hip_gemm_exact.py: every case of gemm_exact.CASES keeps the exactness promise, the case list reaches every
-branch of the GEMM dispatcher it names (gemm_exact.route restates launch_gemm_f16 / pick_v5 / launch_v5), and the comparator the GPU
+branch of the GEMM dispatcher it names (gemm_exact.route restates the dispatcher that gemm_f16_route replaced, branch by branch), and the comparator the GPU
 test applies -- bit equality with the reference -- rejects the defects it is there for, planted into a torch emulation of the kernel
 (gemm_exact.emulate).  Pure torch: no library, no GPU.
 
@@ -94,7 +94,7 @@ def test_every_case_takes_the_branch_it_is_listed_for():
     with pytest.raises(AssertionError):
         G.assert_coverage([G.Case("f16", *s, {}) for s in old])
     got = G.reached()
-    assert (G.EPI_BIAS_RES, ("v5", 128, "boundary", "a_nt", "", "")) in got       # XB | 5: launched by no earlier kernel test
+    assert (G.EPI_BIAS_RES, ("v5", 128, "boundary", "a_nt", "", "")) in got       # boundary loop + nontemporal A stream on 128-row tiles: launched by no earlier kernel test
     f32 = [c for c in G.CASES if c.kind == "f32"]
     for vals, field in (((1, 63, 64, 65, 300), "M"), ((4, 100, 128, 130), "N"), ((32, 96, 512, 2048), "K"), ((0, 1, 3), "epi")):
         assert set(vals) <= {getattr(c, field) for c in f32}

@@ -1,4 +1,4 @@
-"""The GEMM family held to exact values: every case of gemm_exact.CASES -- one per branch of launch_gemm_f16 / pick_v5 / launch_v5, plus
+"""The GEMM family held to exact values: every case of gemm_exact.CASES -- one per branch of the GEMM dispatcher (gemm_f16_route), plus
 the fp32 kernel -- on operands for which every partial sum is exact in fp32 (gemm_exact.py: the method, the case table and which branch
 each case takes; test_gemm_exact_cpu.py: the comparator rejects a lost product, a changed rounding point, a neighbour's bias).  The
 expected output is ONE bit pattern whatever the K order, so for every case and every variant in {0, 6, 8, 9}

@@ -888,7 +888,7 @@ def test_config_c2_vit_b16_hundred_classes_eight_shots(golden, O):
 
 
 def test_config_c2_hundred_classes_eight_shots(O):
-    """BASELINE config 2 shape (100 classes x 8 shots) on the 'small' model with PLAIN random weights, shuffled class order, ragged
+    """BASELINE config 2 shape (100 classes x 8 shots) on the 'small' model with plain random weights, shuffled class order, ragged
     last batch (100 = 3*32 + 4): every classifier row against the oracle; the fusion weights against the kernel's own counters and, on
     the (at least 80) classes no near-tied argmax of the oracle can touch, against the oracle's exactly."""
     from ovmr_amd import modules
