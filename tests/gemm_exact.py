@@ -400,7 +400,11 @@ def epilogue(c, acc, bias, res, pos, one_rounding=False):
 
 def gelu_forms(acc, bias):
     """(the function x * sigmoid(1.702 x) in fp64, the reference's fp16 form as fp32) on the exact x = acc + bias."""
-    x = (acc + bias.float()).double()
+    return gelu_forms_of((acc + bias.float()).double())
+
+
+def gelu_forms_of(x):
+    """gelu_forms on a given fp64 x (gemm_ln_exact.py: the output of the LayerNorm fold)."""
     u = _h(x.float())
     return x * torch.sigmoid(1.702 * x), _h(u * _h(torch.sigmoid(_h(1.702 * u))))
 
