@@ -201,6 +201,17 @@ int ovmr_fused_logits(ovmr_handle* h, const void* feats_f16, int B, const void* 
                       const void* v_f16, const void* t_f16, const float* w_f32, int C, int mode,
                       float* out_f32, ovmr_stream stream);
 
+/* All four eval modes of :348-363 from ONE pass over the head (EVAL_MODE all: the four columns of the reference's result tables without
+ * four runs).  Operands as for ovmr_fused_logits, all three classifiers and w required.  out_f32: four planes [B, C] fp32 with dense rows,
+ * plane p at out_f32 + p * plane_stride, plane_stride >= B * C elements (so a row slice of a [4, Btot, C] tensor can be handed in); the
+ * plane index is the OVMR_MODE_* value: 0 fusion = sum_m w[c][m] p_m, 1 text = p_t, 2 vision = p_v, 3 multimodal = p_mm.  Contract: plane p
+ * is bit-equal to what ovmr_fused_logits(..., mode = p, ...) writes on the same handle, options and operands.  It takes the implementation
+ * ovmr_head_plan(h, B, C) names, under the same options ("fused_head", "head_max_grid", "gemm") and in the same workspace; asynchronous, no
+ * allocation, no synchronisation; B == 0 returns 0.  OVMR_E_ARG with nothing written: a NULL classifier, w or output, plane_stride < B * C,
+ * C < 1. */
+int ovmr_fused_logits_all(ovmr_handle* h, const void* feats_f16, int B, const void* mm_f16, const void* v_f16, const void* t_f16,
+                          const float* w_f32, int C, float* out_f32, long plane_stride, ovmr_stream stream);
+
 /* Which implementation ovmr_fused_logits runs for B query rows and C classes on this handle: 1 = the one-launch head, 0 = scale + GEMMs +
  * softmax (-1: bad arguments / not finalized).  Both keep the reference's rounding points (:357-363) but sum K in different orders, so a
  * logit may land on the neighbouring fp16 value: a caller that splits one batch over several calls and promises the unsplit call's bits

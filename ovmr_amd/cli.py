@@ -15,6 +15,15 @@ runs the zero-shot trainers of trainers/zsclip.py on the same folder data set, a
 ranks the job's classes for UNLABELLED images (a directory, or a text file of paths) instead of the test pass: OUTPUT_DIR/predictions.csv holds
 `image,rank,label,classname,score` (any of the three trainers; `--classifiers` loads a generated file instead of generating again).
 
+    python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --eval_mode all
+
+evaluates the four modes of the reference's result tables (fusion, text, vision, multimodal; trainers/mm_classifier_one_prompt.py:348-363)
+in ONE test pass -- the exemplars are drawn, the classifiers generated and every test image decoded and encoded once instead of four
+times: a `=> eval mode: <mode>` line and the result block per mode, a four-line summary, the results keyed `<mode>/accuracy` ..., and
+acc_per_class.csv / f1_per_class.csv / cmat.pt in OUTPUT_DIR/<mode>/ (mm_classifiers.pt / visual_tokens.pt in OUTPUT_DIR, once).  Each
+mode's figures and files are those of its own single-mode run.  Not with `--predict` (a ranked prediction needs one mode); the zero-shot
+trainers ignore EVAL_MODE.
+
     python -m ovmr_amd.cli --eval-only --trainer ZeroshotCLIP ... --per-class-result --confusion-matrix
 
 adds the reference's `=> per-class result` block (and `perclass_accuracy` in the results) and OUTPUT_DIR/cmat.pt, the row-normalised
@@ -408,6 +417,8 @@ def main(argv=None) -> Dict[str, float]:
     shots, batch, seed = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE, cfg.SEED
     split_cfg = cfg
     predict, images, k = args.predict is not None, [], None
+    if predict and cfg.EVAL_MODE == "all" and not zeroshot:
+        raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
     if predict:
         for flag, on in (("--per-class-result", args.per_class_result), ("--confusion-matrix", args.confusion_matrix)):
             if on:

@@ -22,7 +22,7 @@ from typing import Any, Dict, Iterable, List, Sequence
 DEFAULTS: Dict[str, Any] = {
     "OUTPUT_DIR": "./output",
     "SEED": -1,
-    "EVAL_MODE": "multimodal",                       # train.py:129
+    "EVAL_MODE": "multimodal",                       # train.py:129; "all" (not in the reference): the four modes in one test pass
     "EVAL_TAU": 10,                                  # train.py:130
     "DATASET.ROOT": "",
     "DATASET.NAME": "",
@@ -57,7 +57,7 @@ IGNORED_PREFIXES = ("OPTIM.", "TRAIN.", "TEST.EVALUATOR", "TEST.PER_CLASS_RESULT
                     "VERSION", "RESUME", "USE_CUDA", "VERBOSE", "TEXT_ONLY", "GPU_NUMS", "TASK_ID", "FS_CLASSIFIER", "CLASSIFIER_PARAMETERS",
                     "STAGE_NUM", "USE_CLIP_TEXT")
 
-CHOICES = {"DATASET.SUBSAMPLE_CLASSES": ("all", "base", "new"), "EVAL_MODE": ("text", "vision", "multimodal", "fusion"),
+CHOICES = {"DATASET.SUBSAMPLE_CLASSES": ("all", "base", "new"), "EVAL_MODE": ("text", "vision", "multimodal", "fusion", "all"),
            "INPUT.INTERPOLATION": ("bilinear", "bicubic", "nearest")}
 
 

@@ -172,7 +172,10 @@ int launch_preprocess_u8(const uint8_t* in, half_t* out, int B, int R, const flo
 // one-launch classifier head (head_fused.hip); -100: shape not taken
 size_t head_fused_ws_bytes(int B, int C);
 int head_fused_sync_ints();
+// plane_stride > 0: the all-modes form -- `out` is four planes [B, C], plane_stride floats apart (fusion, text, vision, multimodal)
 int launch_head_fused(const half_t* feats, int B, int D, float scale, const half_t* const* clf, int n_mod, int C, const float* w,
-                      float* out, half_t* raw_out, void* ws, int* sync, int n_cu, int max_grid, hipStream_t s);
+                      float* out, long plane_stride, half_t* raw_out, void* ws, int* sync, int n_cu, int max_grid, hipStream_t s);
 int launch_fused_softmax(const half_t* l0, const half_t* l1, const half_t* l2, const float* w, int n_mod,
                          float* out, int B, int C, hipStream_t s);
+int launch_fused_softmax_all(const half_t* l0, const half_t* l1, const half_t* l2, const float* w, float* out, long plane_stride,
+                             int B, int C, hipStream_t s);

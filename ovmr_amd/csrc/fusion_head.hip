@@ -164,9 +164,12 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float* red) 
 }
 
 // out[b][c] = sum_m softmax_c(float(l_m[b]))[c] * w[c][m]   (w == nullptr: single modality, weight 1)
-__global__ __launch_bounds__(256) void fused_softmax_kernel(const half_t* __restrict__ l0, const half_t* __restrict__ l1,
-                                                            const half_t* __restrict__ l2, const float* __restrict__ w,
-                                                            int n_mod, float* __restrict__ out, int C) {
+// ALL (three modalities and w): `out` is four planes plane_stride floats apart -- that sum, then the softmaxes of l2, l1, l0 themselves
+// (plane = OVMR_MODE_* value: fusion, text, vision, multimodal), each bit-equal to what the single-modality launch writes.
+template <bool ALL>
+__device__ __forceinline__ void fused_softmax_row(const half_t* __restrict__ l0, const half_t* __restrict__ l1,
+                                                  const half_t* __restrict__ l2, const float* __restrict__ w,
+                                                  int n_mod, float* __restrict__ out, int C, long plane_stride) {
     __shared__ float red[4];
     const int b = blockIdx.x;
     const half_t* ls[3] = {l0 + (long)b * C, l1 ? l1 + (long)b * C : nullptr, l2 ? l2 + (long)b * C : nullptr};
@@ -184,9 +187,22 @@ __global__ __launch_bounds__(256) void fused_softmax_kernel(const half_t* __rest
         for (int m = 0; m < n_mod; ++m) {
             const float p = __expf((float)ls[m][c] - mx[m]) * inv[m];
             acc += w ? p * w[c * 3 + m] : p;
+            if constexpr (ALL) out[(3 - m) * plane_stride + (long)b * C + c] = p;
         }
         out[(long)b * C + c] = acc;
     }
+}
+
+__global__ __launch_bounds__(256) void fused_softmax_kernel(const half_t* __restrict__ l0, const half_t* __restrict__ l1,
+                                                            const half_t* __restrict__ l2, const float* __restrict__ w,
+                                                            int n_mod, float* __restrict__ out, int C) {
+    fused_softmax_row<false>(l0, l1, l2, w, n_mod, out, C, 0);
+}
+
+__global__ __launch_bounds__(256) void fused_softmax_all_kernel(const half_t* __restrict__ l0, const half_t* __restrict__ l1,
+                                                                const half_t* __restrict__ l2, const float* __restrict__ w,
+                                                                float* __restrict__ out, int C, long plane_stride) {
+    fused_softmax_row<true>(l0, l1, l2, w, 3, out, C, plane_stride);
 }
 
 }  // namespace
@@ -222,5 +238,13 @@ int launch_fused_softmax(const half_t* l0, const half_t* l1, const half_t* l2, c
                          float* out, int B, int C, hipStream_t s) {
     if (B <= 0) return 0;
     hipLaunchKernelGGL(fused_softmax_kernel, dim3(B), dim3(256), 0, s, l0, l1, l2, w, n_mod, out, C);
+    return (int)hipGetLastError();
+}
+
+int launch_fused_softmax_all(const half_t* l0, const half_t* l1, const half_t* l2, const float* w, float* out, long plane_stride,
+                             int B, int C, hipStream_t s) {
+    if (B <= 0) return 0;
+    if (!l0 || !l1 || !l2 || !w || !out || plane_stride < (long)B * C) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(fused_softmax_all_kernel, dim3(B), dim3(256), 0, s, l0, l1, l2, w, out, C, plane_stride);
     return (int)hipGetLastError();
 }

@@ -28,7 +28,11 @@
 //     live in device memory owned by the handle; the last workgroup to leave re-arms them -- nothing on the host, replayable from
 //     a hipGraph, safe with several handles in flight, each used from ONE stream at a time (the counters and the workspace belong to the
 //     handle: two launches on one handle must be stream-ordered -- include/ovmr_hip.h says so for every entry point);
-//   * raw mode (zero-shot CLIP, one classifier, fp16 logits out): one pass, no counters.
+//   * raw mode (zero-shot CLIP, one classifier, fp16 logits out): one pass, no counters;
+//   * all-modes form (EVAL_MODE all: the four columns of the reference's result tables from ONE launch): phase 2 holds the three
+//     softmaxes p_mm, p_v, p_t of a tile when it writes their weighted sum -- the single modes ARE those p_m (:348-363) -- so it stores
+//     them too, into three further planes of the output (plane = OVMR_MODE_* value: fusion, text, vision, multimodal).  Everything
+//     before the stores is the fusion launch's; each plane is bit-equal to what the single-mode launch writes.
 #include "common.h"
 
 #include <algorithm>
@@ -59,14 +63,17 @@ __device__ __forceinline__ void hf_wait(int* counter, int target) {
     while (aload(counter) < target) __builtin_amdgcn_s_sleep(2);
 }
 
-// BM: query rows per tile (32 or 64).  RAW: one classifier, fp16 logits out, no softmax.
-template <int BM, bool RAW>
+// BM: query rows per tile (32 or 64).  RAW: one classifier, fp16 logits out, no softmax.  ALL (not RAW; three classifiers and w): `out` is
+// four planes plane_stride floats apart -- the weighted sum, then p_t, p_v, p_mm.  plane_stride is the LAST argument and read by ALL alone:
+// the other instantiations keep their code, only the hidden arguments behind it move by 8 bytes.
+template <int BM, bool RAW, bool ALL = false>
 __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __restrict__ feats, int B, int D, float scale,
                                                          const half_t* __restrict__ c0, const half_t* __restrict__ c1,
                                                          const half_t* __restrict__ c2, int n_mod, int C,
                                                          const float* __restrict__ w, float* __restrict__ out,
                                                          half_t* __restrict__ raw_out, float* __restrict__ partial, float* __restrict__ merged,
-                                                         int* __restrict__ leftover, int* sync, int Tc, int n_tiles) {
+                                                         int* __restrict__ leftover, int* sync, int Tc, int n_tiles, long plane_stride) {
+    static_assert(!(RAW && ALL), "the all-modes form writes probabilities");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     constexpr int QB = BM / 32;                              // 32-query blocks per tile
     const int ldf = D + 8;                                   // LDS row stride in halves: + 16 B, so that the 16 lanes of a ds_read_b128 pass hit 64 distinct banks
@@ -285,6 +292,7 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __rest
                 for (int kq = 0; kq < 4; ++kq) {
                     const int c = cw0 + 8 * kq + 4 * h;
                     float4_t o;
+                    float4_t om[ALL ? 3 : 1];                    // ALL: p_mm, p_v, p_t of these four classes
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float a = 0.f;
@@ -293,16 +301,24 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __rest
                             if (m >= n_mod) break;
                             const float pr = __expf(acc[m][qb][4 * kq + e] - M[m]) * inv[m];
                             a += w ? pr * w[(long)min(c + e, C - 1) * 3 + m] : pr;
+                            if constexpr (ALL) om[m][e] = pr;
                         }
                         o[e] = a;
                     }
                     if (row < B) {
-                        float* dst = out + (long)row * C + c;
-                        if (c + 3 < C && (C & 3) == 0) *(float4_t*)dst = o;
-                        else {
+                        auto store = [&](float* dst, const float4_t& val) {
+                            if (c + 3 < C && (C & 3) == 0) *(float4_t*)dst = val;
+                            else {
 #pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (c + e < C) dst[e] = o[e];
+                                for (int e = 0; e < 4; ++e)
+                                    if (c + e < C) dst[e] = val[e];
+                            }
+                        };
+                        float* dst = out + (long)row * C + c;
+                        store(dst, o);
+                        if constexpr (ALL) {                     // classifier m (mm, v, t) is mode 3 - m (OVMR_MODE_MULTIMODAL, _VISION, _TEXT)
+#pragma unroll
+                            for (int m = 0; m < 3; ++m) store(dst + (3 - m) * plane_stride, om[m]);
                         }
                     }
                 }
@@ -393,12 +409,13 @@ __global__ __launch_bounds__(256, 2) void head_fused_kernel(const half_t* __rest
     }
 }
 
-template <int BM, bool RAW>
+template <int BM, bool RAW, bool ALL = false>
 int launch_one(const half_t* feats, int B, int D, float scale, const half_t* const* clf, int n_mod, int C, const float* w,
-               float* out, half_t* raw_out, float* partial, float* merged, int* leftover, int* sync, int Tc, size_t lds, int max_grid, hipStream_t s) {
+               float* out, long plane_stride, half_t* raw_out, float* partial, float* merged, int* leftover, int* sync, int Tc, size_t lds,
+               int max_grid, hipStream_t s) {
     const int Tr = (B + BM - 1) / BM, n_tiles = Tr * Tc;
-    auto kern = head_fused_kernel<BM, RAW>;
-    static size_t lds_set[OVMR_MAX_DEVICES] = {};            // per (BM, RAW) and device: the largest dynamic LDS size granted so far
+    auto kern = head_fused_kernel<BM, RAW, ALL>;
+    static size_t lds_set[OVMR_MAX_DEVICES] = {};            // per (BM, RAW, ALL) and device: the largest dynamic LDS size granted so far
     if (lds > 64 * 1024) {
         int dev = 0;
         HIP_CHECK_RET(hipGetDevice(&dev));
@@ -410,7 +427,7 @@ int launch_one(const half_t* feats, int B, int D, float scale, const half_t* con
     }
     const int grid = RAW ? n_tiles : std::max(1, std::min(n_tiles, max_grid > 0 ? max_grid : n_tiles));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, feats, B, D, scale, clf[0], n_mod > 1 ? clf[1] : nullptr,
-                       n_mod > 2 ? clf[2] : nullptr, n_mod, C, w, out, raw_out, partial, merged, leftover, sync, Tc, n_tiles);
+                       n_mod > 2 ? clf[2] : nullptr, n_mod, C, w, out, raw_out, partial, merged, leftover, sync, Tc, n_tiles, plane_stride);
     return (int)hipGetLastError();
 }
 
@@ -429,10 +446,13 @@ int head_fused_sync_ints() { return HF_SYNC_INTS; }
 // -100: shape not taken (D not a multiple of 64, a feature row that does not fit LDS): the caller runs the five-launch path.
 // `sync`: head_fused_sync_ints() zero-initialised ints owned by the handle.  `ws`: head_fused_ws_bytes(B, C) bytes.  max_grid > 0 caps the grid
 // (tests: a grid smaller than the tile count makes workgroups take several tiles and exercises the recompute queue).
+// plane_stride > 0: the all-modes form (three classifiers, w and `out` required; four planes of `out`, plane_stride floats apart).
 int launch_head_fused(const half_t* feats, int B, int D, float scale, const half_t* const* clf, int n_mod, int C, const float* w,
-                      float* out, half_t* raw_out, void* ws, int* sync, int n_cu, int max_grid, hipStream_t s) {
+                      float* out, long plane_stride, half_t* raw_out, void* ws, int* sync, int n_cu, int max_grid, hipStream_t s) {
     if (B <= 0) return 0;
     if (D % 64 || D > 4096 || n_mod < 1 || n_mod > 3 || C < 1) return -100;
+    const bool all = plane_stride > 0;
+    if (all && (n_mod != 3 || !w || !out || raw_out || plane_stride < (long)B * C)) return (int)hipErrorInvalidValue;
     const int Tc = (C + HF_BN - 1) / HF_BN;
     const bool raw = raw_out != nullptr;
     // 32-row tiles while there is at most one per CU (more, smaller workgroups: C = 1000, B = 256 -> 64 of them), else 64-row tiles
@@ -444,8 +464,10 @@ int launch_head_fused(const half_t* feats, int B, int D, float scale, const half
     float* partial = (float*)ws;
     float* merged = partial + 3 * rows * Tc * 2;
     int* leftover = (int*)(merged + 3 * rows * 2);
-    if (raw) return BM == 32 ? launch_one<32, true>(feats, B, D, scale, clf, 1, C, nullptr, nullptr, raw_out, nullptr, nullptr, nullptr, nullptr, Tc, lds, 0, s)
-                             : launch_one<64, true>(feats, B, D, scale, clf, 1, C, nullptr, nullptr, raw_out, nullptr, nullptr, nullptr, nullptr, Tc, lds, 0, s);
-    return BM == 32 ? launch_one<32, false>(feats, B, D, scale, clf, n_mod, C, w, out, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s)
-                    : launch_one<64, false>(feats, B, D, scale, clf, n_mod, C, w, out, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s);
+    if (raw) return BM == 32 ? launch_one<32, true>(feats, B, D, scale, clf, 1, C, nullptr, nullptr, 0, raw_out, nullptr, nullptr, nullptr, nullptr, Tc, lds, 0, s)
+                             : launch_one<64, true>(feats, B, D, scale, clf, 1, C, nullptr, nullptr, 0, raw_out, nullptr, nullptr, nullptr, nullptr, Tc, lds, 0, s);
+    if (all) return BM == 32 ? launch_one<32, false, true>(feats, B, D, scale, clf, 3, C, w, out, plane_stride, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s)
+                             : launch_one<64, false, true>(feats, B, D, scale, clf, 3, C, w, out, plane_stride, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s);
+    return BM == 32 ? launch_one<32, false>(feats, B, D, scale, clf, n_mod, C, w, out, 0, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s)
+                    : launch_one<64, false>(feats, B, D, scale, clf, n_mod, C, w, out, 0, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s);
 }

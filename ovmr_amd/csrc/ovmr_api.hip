@@ -968,7 +968,7 @@ int ovmr_fused_logits(ovmr_handle* h, const void* feats_f16, int B, const void* 
         // one launch: scaled features staged once, the (up to) three products, both rounding points, softmax and weighted sum (head_fused.hip)
         const half_t* cl[3] = {(const half_t*)clf[0], n_mod > 1 ? (const half_t*)clf[1] : nullptr, n_mod > 2 ? (const half_t*)clf[2] : nullptr};
         const int rc = launch_head_fused((const half_t*)feats_f16, B, D, h->logit_scale_exp, cl, n_mod, C, mode == OVMR_MODE_FUSION ? w : nullptr,
-                                         out_f32, nullptr, h->ws, h->head_sync, h->n_cu, h->head_max_grid, s);
+                                         out_f32, 0, nullptr, h->ws, h->head_sync, h->n_cu, h->head_max_grid, s);
         if (rc != -100) { CK(rc); return 0; }
     }
     const int chunk = (int)std::min<long>(std::max<long>(1, h->logit_elems_cap / C), 65536);
@@ -985,6 +985,33 @@ int ovmr_fused_logits(ovmr_handle* h, const void* feats_f16, int B, const void* 
     return 0;
 }
 
+// The four eval modes of one batch from one pass over the head (EVAL_MODE all): the route, the options and the workspace of
+// ovmr_fused_logits(mode = fusion); the launch that writes the weighted sum also stores the three softmaxes it is made of.
+int ovmr_fused_logits_all(ovmr_handle* h, const void* feats_f16, int B, const void* mm, const void* v, const void* t,
+                          const float* w, int C, float* out_f32, long plane_stride, ovmr_stream stream) {
+    if (h && B == 0) return 0;
+    if (!h || !feats_f16 || !mm || !v || !t || !w || !out_f32 || B < 0 || C < 1 || plane_stride < (long)B * C) return OVMR_E_ARG;
+    if (int rc = need_finalized(h)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int D = h->d.embed_dim;
+    const half_t* cl[3] = {(const half_t*)mm, (const half_t*)v, (const half_t*)t};           // column order mm, v, t (:361)
+    if (head_takes_one_launch(h, B, C)) {
+        const int rc = launch_head_fused((const half_t*)feats_f16, B, D, h->logit_scale_exp, cl, 3, C, w, out_f32, plane_stride, nullptr,
+                                         h->ws, h->head_sync, h->n_cu, h->head_max_grid, s);
+        if (rc != -100) { CK(rc); return 0; }
+    }
+    const int chunk = (int)std::min<long>(std::max<long>(1, h->logit_elems_cap / C), 65536);
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int Bc = std::min(chunk, B - b0);
+        const HeadWs ws(h, h->ws, 3);
+        CK(launch_scale_f16((const half_t*)feats_f16 + (size_t)b0 * D, ws.sf, h->logit_scale_exp, (long)Bc * D, s));
+        for (int m = 0; m < 3; ++m)
+            CK(launch_gemm_f16(gemm(ws.sf, D, cl[m], D, ws.l[m], C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
+        CK(launch_fused_softmax_all(ws.l[0], ws.l[1], ws.l[2], w, out_f32 + (size_t)b0 * C, plane_stride, Bc, C, s));   // every plane advances by b0 * C
+    }
+    return 0;
+}
+
 int ovmr_zeroshot_logits(ovmr_handle* h, const void* feats_f16, int B, const void* text_f16, int C, void* out_f16,
                          ovmr_stream stream) {
     if (h && B == 0) return 0;
@@ -994,7 +1021,7 @@ int ovmr_zeroshot_logits(ovmr_handle* h, const void* feats_f16, int B, const voi
     const int D = h->d.embed_dim;
     if (h->fused_head) {                           // scale, product and the fp16 rounding of the logits in one launch
         const half_t* cl[3] = {(const half_t*)text_f16, nullptr, nullptr};
-        const int rc = launch_head_fused((const half_t*)feats_f16, B, D, h->logit_scale_exp, cl, 1, C, nullptr, nullptr, (half_t*)out_f16,
+        const int rc = launch_head_fused((const half_t*)feats_f16, B, D, h->logit_scale_exp, cl, 1, C, nullptr, nullptr, 0, (half_t*)out_f16,
                                          nullptr, nullptr, h->n_cu, 0, s);
         if (rc != -100) { CK(rc); return 0; }
     }

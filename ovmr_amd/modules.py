@@ -729,7 +729,8 @@ class CustomCLIP(_TwoInFlight):
 
     @torch.no_grad()
     def forward(self, image, label=None, eval_set_loader=None, scale_no=None):
-        """:294-364, evaluation branch: [B,3,R,R] -> [B,C] fp32."""
+        """:294-364, evaluation branch: [B,3,R,R] -> [B,C] fp32; with cfg.EVAL_MODE == "all" [4,B,C], the four modes of :348-363 in
+        runtime.ALL_MODES order (fusion, text, vision, multimodal), each plane bit-equal to what its own EVAL_MODE returns."""
         if eval_set_loader is None and self.mm_classifier is None:
             raise NotImplementedError("the training branch of CustomCLIP.forward (autograd) is out of scope; "
                                       "pass eval_set_loader= to generate the classifiers")
@@ -745,9 +746,12 @@ class CustomCLIP(_TwoInFlight):
     def _forward_on(self, engine: Engine, image, out=None):
         image_features = engine.encode_image(image, normalize=True)                # :305-307
         mode = self.cfg.EVAL_MODE
-        if mode not in ("text", "vision", "multimodal", "fusion"):
+        if mode not in ("text", "vision", "multimodal", "fusion", "all"):
             raise ValueError(f"unknown EVAL_MODE {mode}")
         kw = {} if out is None else {"out": out}             # (only the split forward hands an output slice in)
+        if mode == "all":                                    # one pass over the head, four planes (ovmr_fused_logits_all)
+            return engine.fused_logits_all(image_features, self.mm_classifier, self.visual_classifer,
+                                           self.zero_shot_classifier, self.fusion_weight, **kw)
         return engine.fused_logits(image_features, self.mm_classifier, self.visual_classifer,
                                    self.zero_shot_classifier, self.fusion_weight, mode, **kw)
 
@@ -776,28 +780,36 @@ class CustomCLIP(_TwoInFlight):
         if not hasattr(self, "_split_stream"):
             self._split_stream = torch.cuda.Stream(self.device)
         st, twin = self._split_stream, self._twin()
-        out = torch.empty((B, C), dtype=torch.float32, device=self.device)
+        rows = (slice(None),) if self.cfg.EVAL_MODE == "all" else ()      # [4, B, C]: each handle writes its rows of every plane
+        out = torch.empty(((4,) if rows else ()) + (B, C), dtype=torch.float32, device=self.device)
         st.wait_stream(cur)                                  # the image (and `out`) exist for the side stream
         with torch.cuda.stream(st):
-            self._forward_on(twin, image[half:], out=out[half:])
-        self._forward_on(self.engine, image[:half], out=out[:half])
+            self._forward_on(twin, image[half:], out=out[rows + (slice(half, None),)])
+        self._forward_on(self.engine, image[:half], out=out[rows + (slice(None, half),)])
         cur.wait_stream(st)
         image.record_stream(st)
         out.record_stream(st)
         return out
 
     # ------------------------------------------------------------------ ranked prediction (no counterpart in the reference's API)
+    def _one_mode(self, what: str):
+        if self.cfg.EVAL_MODE == "all":
+            raise ValueError(f"{what}: a ranked prediction needs one mode; EVAL_MODE all yields four outputs per image "
+                             "(set EVAL_MODE to fusion, text, vision or multimodal)")
+
     @torch.no_grad()
     def predict_topk(self, image, k: int, eval_set_loader=None):
         """forward(image) followed by ovmr_topk_rows on its output, on the same stream: (values fp32 [B, k], indices int64 [B, k]), the k
         most probable classes of every image, best first."""
+        self._one_mode("predict_topk")
         return self._topk(self.forward(image, eval_set_loader=eval_set_loader), k)
 
     @torch.no_grad()
     def predict_topk_batches(self, batches: Iterable, k: int, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
         """predict_topk for every image batch, in order, over forward_batches (two batches in flight): one (values, indices) pair per batch."""
-        for out in self.forward_batches(batches, eval_set_loader=eval_set_loader, overlap=overlap, stable_inputs=stable_inputs):
-            yield self._topk(out, k)
+        self._one_mode("predict_topk_batches")               # (raised by the call, not by the first next())
+        outs = self.forward_batches(batches, eval_set_loader=eval_set_loader, overlap=overlap, stable_inputs=stable_inputs)
+        return (self._topk(out, k) for out in outs)
 
     @torch.no_grad()
     def load_classifiers(self, path: str):

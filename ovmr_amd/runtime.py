@@ -20,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libovmr_hip.so")
 
 F16, F32, I64, I32 = 0, 1, 2, 3
 MODES = {"fusion": 0, "text": 1, "vision": 2, "multimodal": 3}
+ALL_MODES = ("fusion", "text", "vision", "multimodal")          # EVAL_MODE all: the plane order of ovmr_fused_logits_all (plane = MODES value)
 
 c_p = ctypes.c_void_p
 c_i = ctypes.c_int
@@ -62,6 +63,7 @@ SIGNATURES = {
     "ovmr_xval_counts": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     "ovmr_fusion_weights": (c_i, [c_p, c_p, c_p, c_i, ctypes.c_float, c_p, c_p]),
     "ovmr_fused_logits": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p]),
+    "ovmr_fused_logits_all": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, ctypes.c_long, c_p]),
     "ovmr_pack_rows": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "ovmr_unpack_rows": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "ovmr_eval_counts": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, c_p, c_p]),
@@ -457,6 +459,21 @@ class Engine:
         assert out.shape == (feats.shape[0], C) and out.dtype == torch.float32 and out.is_contiguous()
         self._ck(self.lib.ovmr_fused_logits(self.h, _ptr(feats), feats.shape[0], _ptr(cl[0]), _ptr(cl[1]), _ptr(cl[2]),
                                             _ptr(w), C, MODES[mode], _ptr(out), _stream()), "ovmr_fused_logits")
+        return out
+
+    def fused_logits_all(self, feats, mm, v, t, w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The four eval modes of one batch from one pass over the head (ovmr_fused_logits_all): [4, B, C] fp32 in ALL_MODES order, plane p
+        bit-equal to fused_logits(mode = ALL_MODES[p]).  `out` may be a row slice big[:, r0:r1] of a contiguous [4, Btot, C] tensor."""
+        feats = self._dev(feats, torch.float16)
+        mm, v, t = (self._dev(x, torch.float16) for x in (mm, v, t))
+        w = self._dev(w, torch.float32)
+        B, C = feats.shape[0], mm.shape[0]
+        if out is None:
+            out = torch.empty((4, B, C), dtype=torch.float32, device=self.device)
+        assert out.shape == (4, B, C) and out.dtype == torch.float32 and out.is_cuda
+        assert B == 0 or (out.stride(2) == 1 and out.stride(1) == C and out.stride(0) >= B * C), "dense [B, C] planes, a plane stride apart"
+        self._ck(self.lib.ovmr_fused_logits_all(self.h, _ptr(feats), B, _ptr(mm), _ptr(v), _ptr(t), _ptr(w), C, _ptr(out),
+                                                out.stride(0) if B else 0, _stream()), "ovmr_fused_logits_all")
         return out
 
     def head_plan(self, B: int, C: int) -> int:

@@ -32,6 +32,7 @@ import torch
 
 from . import checkpoint, modules
 from .evaluator import Classification
+from .runtime import ALL_MODES
 
 TRAINER_REGISTRY: Dict[str, type] = {}
 
@@ -57,11 +58,15 @@ class _EvalTrainer:
         self.output_dir = cfg.OUTPUT_DIR
         self.build_model()
         # per_class_result / compute_cmat: what the reference reads from TEST.PER_CLASS_RESULT / TEST.COMPUTE_CMAT (evaluator.py:38, 165)
-        self.evaluator = Classification(self.num_classes, list(dm.dataset.classnames), device=str(self.device),
-                                        per_class=per_class_result, confusion=compute_cmat)
+        self._evaluator_args = dict(per_class=per_class_result, confusion=compute_cmat)
+        self.evaluator = self._new_evaluator()
+        self.mode_evaluators = None                  # EVAL_MODE all: one Classification per mode of ALL_MODES, made by the first such test()
 
     def check_cfg(self, cfg):
         pass
+
+    def _new_evaluator(self) -> Classification:
+        return Classification(self.num_classes, list(self.dm.dataset.classnames), device=str(self.device), **self._evaluator_args)
 
     def build_model(self):
         raise NotImplementedError
@@ -126,10 +131,33 @@ class _EvalTrainer:
 
         topk = int(getattr(getattr(self.cfg, "TEST", None), "TOPK", 1))          # evaluator.process(mo, gt, topk), evaluator.py:50
         kw = {"topk": topk} if topk != 1 else {}
+        per_mode = False
         for output in self.outputs(inputs()):
-            self.evaluator.process(output, labels.popleft(), **kw)
+            label = labels.popleft()
+            if output.dim() == 3:                    # [4, B, C] (EVAL_MODE all): plane p is mode ALL_MODES[p]'s output, counted by evaluator p
+                if not per_mode:
+                    per_mode = True
+                    if self.mode_evaluators is None:
+                        self.mode_evaluators = [self._new_evaluator() for _ in ALL_MODES]
+                    for ev in self.mode_evaluators:
+                        ev.reset()
+                for ev, plane in zip(self.mode_evaluators, output):
+                    ev.process(plane, label, **kw)
+            else:
+                self.evaluator.process(output, label, **kw)
         self.after_test()
-        self.results = self.evaluator.evaluate(self.output_dir or None)
+        if not per_mode:
+            self.results = self.evaluator.evaluate(self.output_dir or None)
+            return list(self.results.values())[0]
+        # one result block and one set of files (OUTPUT_DIR/<mode>/) per mode, every key prefixed "<mode>/"; then the table's four rows
+        self.results = OrderedDict()
+        for mode, ev in zip(ALL_MODES, self.mode_evaluators):
+            print(f"=> eval mode: {mode}")
+            res = ev.evaluate(os.path.join(self.output_dir, mode) if self.output_dir else None)
+            self.results.update((f"{mode}/{k}", v) for k, v in res.items())
+        for mode in ALL_MODES:
+            r = self.results
+            print(f"=> {mode}: accuracy {r[mode + '/accuracy']:.1f}%, error {r[mode + '/error_rate']:.1f}%, macro_f1 {r[mode + '/macro_f1']:.1f}%")
         return list(self.results.values())[0]
 
     def ranked(self, inputs, k):

@@ -9,7 +9,10 @@
 # and the results (the evaluator's figures, per-class CSVs and, as a by-product of the first forward, mm_classifiers.pt / visual_tokens.pt)
 # go to
 #   output_ovmr/base2new/test_<SUB_CLASSES>_<EVAL_MODE>_tau<EVAL_TAU>/<DATASET>/shots_<SHOTS>/MM_CLS_OP/<CFG>/seed<SEED>
-# (skipped when that directory exists).  Everything else -- environment, GPU selection, multi-rank launch, DRY_RUN=1 -- is
+# (skipped when that directory exists).  EVAL_MODE=all (not in the reference, which needs four runs for the four columns of its result
+# tables) evaluates fusion, text, vision and multimodal in ONE test pass: the directory is .../test_<SUB_CLASSES>_all_tau<EVAL_TAU>/...,
+# with mm_classifiers.pt / visual_tokens.pt once and the per-class CSVs (and cmat.pt) of each mode in its sub-directory fusion/, text/,
+# vision/, multimodal/.  Everything else -- environment, GPU selection, multi-rank launch, DRY_RUN=1 -- is
 # scripts/generate_classifier.sh, which this script runs with those two directories; MODEL_DIR / DIR in the environment still win.
 set -e
 if [ $# -lt 7 ]; then
