@@ -175,6 +175,21 @@ int ovmr_embed_tokens(ovmr_handle* h, const int64_t* ids, int N, int L, void* ou
 int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S,
                          float* tokens_f32, ovmr_stream stream);
 
+/* The same generator for classes with their OWN exemplar counts.  trainers/mm_classifier_one_prompt.py:167-169 runs the aggregator
+ * over cat([cls_token, feats]) of a [num_cls, num_ins, D] tensor: the reference has no counterpart for unequal counts, it takes
+ * num_ins rows of every class by position (:238-245).  Here class c of the call owns shots[c] consecutive rows of feats [R, embed_dim]
+ * fp16 (class after class, R = sum of the shots) and the aggregator runs over its n_ctx + shots[c] tokens, no padding and no
+ * duplicates.  shots_host: HOST int32 [Cb], read before the call returns (the library plans its chunks -- runs of whole classes whose
+ * packed rows fit the aggregator's workspace, at least one class each -- and its grids from it); offsets_dev: DEVICE int32 [Cb + 1],
+ * the exclusive prefix sum of the same shots (the kernels index from it; every index made from it is clamped to the call's rows, so
+ * two views that disagree give wrong values, never an access outside the buffers).  Asynchronous, allocation-free, capturable.
+ * THE CONTRACT: tokens[c] is bit-identical to what ovmr_generate_tokens returns for class c alone with S = shots[c] on the same
+ * handle, whatever else shares the call and wherever the chunk boundaries fall; a call whose counts are all S equals the uniform call.
+ * OVMR_E_SHAPE before any launch, naming the class: a count < 1, n_ctx + shots[c] > 128; also when the shots do not add up to R.
+ * Cb == 0 returns 0. */
+int ovmr_generate_tokens_ragged(ovmr_handle* h, const void* feats_f16, const int32_t* shots_host, const int32_t* offsets_dev,
+                                int Cb, int R, float* tokens_f32, ovmr_stream stream);
+
 /* PromptLearner.update_prompts (:156-157): out[c] = cat(base[row(c)][:2], half(tokens[c]),
  * base[row(c)][2:-n_ctx]); row(c) = labels[c] (int64) or 0 when labels == NULL (the "a ." template
  * broadcast, :173).  base: [*, context_length, width] fp16; out: [Cb, context_length, width] fp16. */
@@ -355,6 +370,11 @@ int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B
 int ovmr_debug_gemm_strided(int variant, const void* A, int lda, const void* W, int ldw, const void* bias, const void* res,
                             int ldres, void* C, int ldc, int M, int N, int K, int epi, float scale, const float* gamma,
                             const float* beta, int row_step, ovmr_stream stream);
+/* fp32 attention (hd = 64) over nseq sequences packed row after row: sequence b is the rows [offsets[b] + b * n_ctx,
+ * offsets[b + 1] + (b + 1) * n_ctx) of qkv [M, 3 * H * 64], offsets_dev a DEVICE int32 [nseq + 1] exclusive prefix sum, every length
+ * in [1, max_len]; out [M, H * 64].  Row by row the arithmetic of ovmr_debug_attention(f32 = 1).  -2 for max_len > 128. */
+int ovmr_debug_attention_f32_varlen(const void* qkv, void* out, const int32_t* offsets_dev, int nseq, int n_ctx, int max_len, int H,
+                                    ovmr_stream stream);
 /* fp16 attention for the first Lq <= L queries of every sequence (the last vision block runs Lq = 1, the CLS query):
  * out [B*Lq, H*64], row b*Lq + q.  Lq > L returns OVMR_E_SHAPE. */
 int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L, int Lq, int H, int causal,

@@ -110,25 +110,39 @@ class FolderLoader:
     CustomCLIP.forward_prompt that every batch it receives is its own."""
 
     def __init__(self, items: Sequence[Tuple[str, int]], batch_size: int, size: int, rank: int = 0, world: int = 1,
-                 num_classes: int = 0, interpolation: str = "bicubic", mean=PIXEL_MEAN, std=PIXEL_STD):
+                 num_classes: int = 0, interpolation: str = "bicubic", mean=PIXEL_MEAN, std=PIXEL_STD, ragged: bool = False):
+        """ragged: `items` is a ragged exemplar set (layout_exemplars_ragged).  A batch then holds whole classes, at most
+        `batch_size` rows, and carries "shots" (host int64 [n_cls]); `.shots` is int32 [C], the rows of every class of the vocabulary."""
         self.bs, self.size = batch_size, size
         self.tfm = dict(interpolation=interpolation, mean=mean, std=std)
         self.presharded = world > 1
+        self.shots = None
+        if ragged:
+            from .shard import vocabulary_shots
+            self.shots = vocabulary_shots(items, num_classes)
         if world > 1:
             from .shard import shard_range
             lo, hi = shard_range(num_classes or (1 + max(l for _, l in items)), rank, world)
             items = [it for it in items if lo <= it[1] < hi]
         self.items = list(items)
+        if ragged:
+            from .shard import ragged_batches
+            self.spans = ragged_batches(self.items, self.bs)
+        else:
+            self.spans = [(s, min(s + self.bs, len(self.items)), None) for s in range(0, len(self.items), self.bs)]
 
     def __len__(self):
-        return (len(self.items) + self.bs - 1) // self.bs
+        return len(self.spans)
 
     def __iter__(self):
         import torch
-        for s in range(0, len(self.items), self.bs):
-            chunk = self.items[s:s + self.bs]
+        for a, b, shots in self.spans:
+            chunk = self.items[a:b]
             imgs = torch.stack([test_transform(p, self.size, **self.tfm) for p, _ in chunk])
-            yield {"img": imgs, "label": torch.tensor([l for _, l in chunk], dtype=torch.long)}
+            batch = {"img": imgs, "label": torch.tensor([l for _, l in chunk], dtype=torch.long)}
+            if shots is not None:
+                batch["shots"] = torch.tensor(shots, dtype=torch.long)
+            yield batch
 
 
 def fewshot_items(items: Sequence[Tuple[str, int]], shots: int, seed: int = 1) -> List[Tuple[str, int]]:
@@ -177,10 +191,28 @@ def layout_exemplars(few: Sequence[Tuple[str, int]], shots: int, seed: int = 1) 
     return out
 
 
+def layout_exemplars_ragged(few: Sequence[Tuple[str, int]], shots: int) -> List[Tuple[str, int]]:
+    """The eval-set loader's row order in ragged mode (`--ragged-shots`): every class's rows consecutively, classes in order of first
+    appearance, a class's rows in the order given -- and exactly the rows given: a class with fewer than NUM_SHOTS images is NOT filled
+    up (a duplicate would double an exemplar's weight in the aggregator's softmax and vote twice in the F1 preference).  More than
+    NUM_SHOTS rows are refused as in `layout_exemplars`, a row listed twice as well."""
+    per: Dict[int, List[Tuple[str, int]]] = {}
+    for it in few:
+        per.setdefault(it[1], []).append(it)
+    out = []
+    for label, its in per.items():
+        if len(its) > shots:
+            raise ValueError(f"class {label} has {len(its)} exemplar rows, more than DATASET.NUM_SHOTS = {shots}")
+        if len({p for p, _ in its}) != len(its):
+            raise ValueError(f"class {label} lists an exemplar image twice: a ragged exemplar set holds no duplicates")
+        out.extend(its)
+    return out
+
+
 def read_exemplar_list(path: str, num_classes: int, shots: int) -> List[Tuple[str, int]]:
     """`--exemplar-list`: one `<image path> <label>` per line.  Checked before anything is decoded: every label inside
     [0, num_classes), every file present, at most NUM_SHOTS rows per class (fewer are filled up with replacement by
-    `layout_exemplars`, as RandomClassSampler does) -- a malformed list fails here with the offending line, not as shifted class
+    `layout_exemplars`, as RandomClassSampler does; under `--ragged-shots` they stay as they are) -- a malformed list fails here with the offending line, not as shifted class
     groups inside forward_prompt."""
     few: List[Tuple[str, int]] = []
     per: Dict[int, int] = {}
@@ -296,6 +328,9 @@ def parse(argv=None):
     ap.add_argument("--test-split", default="val")
     ap.add_argument("--exemplar-list", default="", help="text file, one `<image path> <label>` per line: use exactly these exemplars (e.g. a "
                     "reference run's few-shot set) instead of drawing NUM_SHOTS per class under --seed; labels are those BEFORE class subsampling")
+    ap.add_argument("--ragged-shots", action="store_true", help="every class uses exactly the exemplars it has: min(available, DATASET.NUM_SHOTS) "
+                    "images, drawn as without the flag, and NO filling of short classes with duplicates; with --exemplar-list the listed rows as "
+                    "they are (1 to NUM_SHOTS per class).  A class without any exemplar is an error that names it")
     ap.add_argument("--predict", metavar="PATH", default=None, help="ranked prediction on UNLABELLED images instead of the test pass: a directory "
                     "(every image file below it, sorted by path) or a text file with one image path per line; writes OUTPUT_DIR/predictions.csv")
     ap.add_argument("--topk", type=int, default=None, metavar="K", help="classes per image of --predict, best first (default 5; 1 <= K <= min(32, classes))")
@@ -315,11 +350,12 @@ def parse(argv=None):
     return ap.parse_args(argv)
 
 
-def build_splits(cfg, eval_split: str = "train", test_split: str = "val", exemplar_list: str = ""):
+def build_splits(cfg, eval_split: str = "train", test_split: str = "val", exemplar_list: str = "", ragged: bool = False):
     """What the reference's dataset class hands the DataManager (datasets/imagenet.py:16-64), for a folder dataset: the few-shot
     draw of `eval_split` under cfg.SEED (or the images listed in `exemplar_list`), THEN the class subsampling of
     DATASET.SUBSAMPLE_CLASSES applied to the exemplar and the test items alike (:60-62), the class names of the surviving labels in
-    label order.  Returns (classnames, exemplar items laid out NUM_SHOTS rows per class, test items)."""
+    label order.  Returns (classnames, exemplar items laid out NUM_SHOTS rows per class, test items); with `ragged` the exemplar items
+    are every class's own rows, unfilled (layout_exemplars_ragged)."""
     from . import config
     shots, seed, sub = cfg.DATASET.NUM_SHOTS, cfg.SEED, cfg.DATASET.SUBSAMPLE_CLASSES
     root = cfg.DATASET.ROOT
@@ -330,6 +366,11 @@ def build_splits(cfg, eval_split: str = "train", test_split: str = "val", exempl
         few = read_exemplar_list(exemplar_list, len(folders), shots)
     else:
         few = fewshot_items(eval_all, shots, seed)
+    if ragged:
+        missing = sorted(set(range(len(folders))) - {l for _, l in few})
+        if missing:
+            raise SystemExit("no exemplar image for class " + ", ".join(f"{all_names[y]!r} (folder {folders[y]!r})" for y in missing[:8])
+                             + (f" and {len(missing) - 8} more" if len(missing) > 8 else ""))
     all_labels = sorted({l for _, l in few})                  # the label set `subsample_classes` splits (train_x, oxford_pets.py:160-168)
     few, test_items = config.subsample_classes(few, test_items, subsample=sub)
     half = -(-len(all_labels) // 2)
@@ -337,7 +378,7 @@ def build_splits(cfg, eval_split: str = "train", test_split: str = "val", exempl
     if sub == "all" and kept != list(range(len(folders))):
         raise SystemExit(f"{len(folders) - len(kept)} class folder(s) of {eval_split!r} hold no exemplar image")
     classnames = [all_names[y] for y in kept]                 # lab2cname of the relabelled train_x (base_dataset.py get_lab2cname)
-    return classnames, layout_exemplars(few, shots, seed), test_items
+    return classnames, layout_exemplars_ragged(few, shots) if ragged else layout_exemplars(few, shots, seed), test_items
 
 
 BACKBONES = {"ViT-B/16": (768, 16, 12), "ViT-B/32": (768, 32, 12), "ViT-L/14": (1024, 14, 24), "ViT-L/14@336px": (1024, 14, 24)}   # clip/clip.py:32-40 (ViT entries)
@@ -386,10 +427,10 @@ def _loader_factory(args, cfg, size: int, tfm: dict):
     """loader(items, batch, rank, world, n_classes): the pipelined loader, or with no decode workers the in-thread FolderLoader."""
     workers = cfg.DATALOADER.NUM_WORKERS if args.workers is None else args.workers
     if workers <= 0:
-        return lambda items, batch, rank=0, world=1, n_classes=0: FolderLoader(items, batch, size, rank, world, n_classes, **tfm)
+        return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False: FolderLoader(items, batch, size, rank, world, n_classes, ragged=ragged, **tfm)
     from .loader import PipelinedFolderLoader
     kw = dict(workers=workers, prefetch=args.prefetch, device=args.device, fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
-    return lambda items, batch, rank=0, world=1, n_classes=0: PipelinedFolderLoader(items, batch, size, rank, world, n_classes, **kw)
+    return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False: PipelinedFolderLoader(items, batch, size, rank, world, n_classes, ragged=ragged, **kw)
 
 
 def _report_pipeline(results: dict, name: str, loader) -> None:
@@ -468,7 +509,8 @@ def main(argv=None) -> Dict[str, float]:
     if seed >= 0:
         print(f"Setting fixed seed: {seed}")                  # train.py:157-159
         torch.manual_seed(seed)
-    classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if predict else args.test_split, args.exemplar_list)
+    ragged = bool(args.ragged_shots) and not zeroshot and not load_classifiers
+    classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if predict else args.test_split, args.exemplar_list, ragged)
     if predict:
         if k > len(classnames):
             raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
@@ -494,7 +536,17 @@ def main(argv=None) -> Dict[str, float]:
         kw["prompt_learner_state"] = pl_state
     rank, world = (dist.get_rank(), dist.get_world_size()) if not zeroshot and dist.is_available() and dist.is_initialized() else (0, 1)
     loader = _loader_factory(args, cfg, spec.image_resolution, tfm)
-    eval_loader = None if zeroshot or load_classifiers else loader(exemplars, batch // shots * shots, rank, world, len(classnames))
+    if zeroshot or load_classifiers:
+        eval_loader = None
+    elif ragged:
+        try:
+            eval_loader = loader(exemplars, batch, rank, world, len(classnames), ragged=True)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        n = np.sort(eval_loader.shots.numpy())
+        print(f"ragged exemplar set: {int(n.sum()):,} images of {len(n):,} classes, shots per class min {int(n[0])} / median {float(np.median(n)):g} / max {int(n[-1])}")
+    else:
+        eval_loader = loader(exemplars, batch // shots * shots, rank, world, len(classnames))
     test_loader = loader(test_items, batch)
     # the decode workers start while the engine takes the weights; on rank 0 one ring (sized for the larger batch) serves both loaders,
     # ranks > 0 never touch the test set: theirs is sized for the exemplar batches alone

@@ -149,32 +149,37 @@ __global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ 
     }
     __syncthreads();
     if (tid >= L) return;
-    float qv[64], o[64];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        float4_t t = *(const float4_t*)(base + (long)tid * ld + c * 4);
-        qv[c * 4] = t[0]; qv[c * 4 + 1] = t[1]; qv[c * 4 + 2] = t[2]; qv[c * 4 + 3] = t[3];
+    attn::f32_row(base + (long)tid * ld, sK, sV, L, scale, out + ((long)b * L + tid) * D + h * 64);
+}
+
+// fp32, sequences of different lengths (each <= 128) packed row after row: sequence b of the launch is the rows
+// [start(b), start(b + 1)) of qkv [M, 3 H 64], start(b) = offsets[b] - base + b * n_ctx (`offsets`: a DEVICE exclusive prefix sum of
+// the classes' shots, `base` its value at the launch's first class; every class has n_ctx rows in front of its shots).  One workgroup
+// per (sequence, head), K and V in LDS sized by the launch's longest sequence (`cap` rows each), a thread per query row through the
+// same attn::f32_row as attn_f32_small: a row's bits depend on its own sequence alone.
+// A device array sets addresses here, so every start is clamped to [0, M] and a workgroup takes at most `cap` rows: offsets that
+// disagree with the host's plan give wrong values, never an access outside qkv / out / LDS.
+__global__ __launch_bounds__(128) void attn_f32_varlen(const float* __restrict__ qkv, float* __restrict__ out,
+                                                       const int* __restrict__ offsets, int base_off, int n_ctx, int M, int cap,
+                                                       int H, float scale) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    float* sK = sm;
+    float* sV = sm + cap * 64;
+    const int tid = threadIdx.x;
+    const int h = blockIdx.x % H, b = blockIdx.x / H;
+    const int D = H * 64, ld = 3 * D;
+    auto start = [&](int s) { return (int)min(max((long)offsets[s] - base_off + (long)s * n_ctx, 0L), (long)M); };
+    const int r0 = start(b);
+    const int L = min(max(start(b + 1) - r0, 0), cap);
+    const float* base = qkv + (long)r0 * ld + h * 64;
+    for (int i = tid; i < L * 16; i += blockDim.x) {
+        const int row = i >> 4, c = i & 15;
+        *(float4_t*)(sK + row * 64 + c * 4) = *(const float4_t*)(base + D + (long)row * ld + c * 4);
+        *(float4_t*)(sV + row * 64 + c * 4) = *(const float4_t*)(base + 2 * D + (long)row * ld + c * 4);
     }
-#pragma unroll
-    for (int d = 0; d < 64; ++d) o[d] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    for (int key = 0; key < L; ++key) {
-        float s = 0.f;
-#pragma unroll
-        for (int d = 0; d < 64; ++d) s += qv[d] * sK[key * 64 + d];
-        s *= scale;
-        const float mn = fmaxf(m, s);
-        const float alpha = __expf(m - mn), p = __expf(s - mn);
-        l = l * alpha + p;
-#pragma unroll
-        for (int d = 0; d < 64; ++d) o[d] = o[d] * alpha + p * sV[key * 64 + d];
-        m = mn;
-    }
-    const float inv = 1.0f / l;
-    float* op = out + ((long)b * L + tid) * D + h * 64;
-#pragma unroll
-    for (int c = 0; c < 16; ++c)
-        *(float4_t*)(op + c * 4) = (float4_t){o[c * 4] * inv, o[c * 4 + 1] * inv, o[c * 4 + 2] * inv, o[c * 4 + 3] * inv};
+    __syncthreads();
+    if (tid >= L) return;
+    attn::f32_row(base + (long)tid * ld, sK, sV, L, scale, out + (long)(r0 + tid) * D + h * 64);
 }
 
 // Which kernel a launch of `variant` runs: 0 attn_f16_v0, 1 attn_f16_v1, 2 attn_f16_short, 3 attn_f16_v3, 5 attn_f16_v5
@@ -226,5 +231,15 @@ int launch_attention_f32(const float* qkv, float* out, int B, int L, int H, hipS
     if (L > 128) return -2;
     const size_t lds = (size_t)2 * L * 64 * sizeof(float);
     hipLaunchKernelGGL(attn_f32_small, dim3(B * H), dim3(128), lds, s, qkv, out, L, H, 0.125f);
+    return (int)hipGetLastError();
+}
+
+int launch_attention_f32_varlen(const float* qkv, float* out, const int* offsets, int base_off, int nseq, int n_ctx, int max_len,
+                                int M, int H, hipStream_t s) {
+    if (nseq <= 0 || M <= 0) return 0;
+    if (max_len < 1 || max_len > 128) return -2;
+    const size_t lds = (size_t)2 * max_len * 64 * sizeof(float);
+    hipLaunchKernelGGL(attn_f32_varlen, dim3((unsigned)nseq * H), dim3(128), lds, s, qkv, out, offsets, base_off, n_ctx, M, max_len, H,
+                       0.125f);
     return (int)hipGetLastError();
 }

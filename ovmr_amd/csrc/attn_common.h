@@ -142,4 +142,38 @@ __device__ __forceinline__ void store_row4(half_t* op, const float4_t (&o)[4], f
     }
 }
 
+// ---- the fp32 kernels (attention.hip: attn_f32_small, attn_f32_varlen) ----------------------------------------------------
+// One query row against the L keys of its own (sequence, head), K and V in LDS as [key][64] fp32: keys in increasing order, s summed
+// over d in increasing order and then scaled, the online maximum, __expf, l and o updated in this order, one reciprocal at the end.
+// Both kernels go through this one function, and the library is built with -ffp-contract=off and without fast-math: a row's bits do
+// not depend on which kernel ran it, on L of any other sequence, or on where the row sits in the launch.
+__device__ __forceinline__ void f32_row(const float* __restrict__ qrow, const float* sK, const float* sV, int L, float scale,
+                                        float* __restrict__ orow) {
+    float qv[64], o[64];
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+        float4_t t = *(const float4_t*)(qrow + c * 4);
+        qv[c * 4] = t[0]; qv[c * 4 + 1] = t[1]; qv[c * 4 + 2] = t[2]; qv[c * 4 + 3] = t[3];
+    }
+#pragma unroll
+    for (int d = 0; d < 64; ++d) o[d] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    for (int key = 0; key < L; ++key) {
+        float s = 0.f;
+#pragma unroll
+        for (int d = 0; d < 64; ++d) s += qv[d] * sK[key * 64 + d];
+        s *= scale;
+        const float mn = fmaxf(m, s);
+        const float alpha = __expf(m - mn), p = __expf(s - mn);
+        l = l * alpha + p;
+#pragma unroll
+        for (int d = 0; d < 64; ++d) o[d] = o[d] * alpha + p * sV[key * 64 + d];
+        m = mn;
+    }
+    const float inv = 1.0f / l;
+#pragma unroll
+    for (int c = 0; c < 16; ++c)
+        *(float4_t*)(orow + c * 4) = (float4_t){o[c * 4] * inv, o[c * 4 + 1] * inv, o[c * 4 + 2] * inv, o[c * 4 + 3] * inv};
+}
+
 }  // namespace attn

@@ -140,6 +140,9 @@ int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq,
 int launch_attention_f16_short(const half_t* qkv, half_t* out, int n_groups, const int* nseq, const int* L, const long* row0, int H,
                                int causal, hipStream_t s);
 int launch_attention_f32(const float* qkv, float* out, int B, int L, int H, hipStream_t s);
+// sequences of n_ctx + shots rows packed row after row, from a device prefix sum of the shots (attention.hip, attn_f32_varlen)
+int launch_attention_f32_varlen(const float* qkv, float* out, const int* offsets, int base_off, int nseq, int n_ctx, int max_len,
+                                int M, int H, hipStream_t s);
 int launch_im2col(const void* img, int img_is_f32, half_t* out, int B, int R, int P, int Kpad, hipStream_t s);
 int launch_fill_cls(half_t* x, const half_t* cls_pos, int B, int L, int W, hipStream_t s);
 int launch_l2norm_f16(half_t* x, int rows, int D, hipStream_t s);
@@ -158,6 +161,9 @@ int launch_unpack_rows(const half_t* gathered, int rows, int C, int D, int n_ctx
                        hipStream_t s);
 int launch_agg_input(const float* cls_token, const half_t* feats, float* x, int Cb, int S, int n_ctx, int D, hipStream_t s);
 int launch_agg_output(const float* x, float* tokens, int Cb, int La, int n_ctx, int D, hipStream_t s);
+int launch_agg_input_ragged(const float* cls_token, const half_t* feats, const int* offsets, int base, float* x, int Cb, int M, int R,
+                            int n_ctx, int D, hipStream_t s);
+int launch_agg_output_ragged(const float* x, const int* offsets, int base, float* tokens, int Cb, int M, int n_ctx, int D, hipStream_t s);
 int launch_assemble_prompts(const half_t* base, const int64_t* labels, const float* tokens, half_t* out,
                             int Cb, int Lctx, int n_ctx, int D, hipStream_t s);
 int launch_argmax_counts(const half_t* logits, int ld, const int* labels, int R, int C, int* tp, int* n_pred, hipStream_t s);

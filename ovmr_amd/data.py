@@ -30,3 +30,31 @@ class ResidentEvalSet:
         step = self.cpb * self.shots
         for s in range(0, self.images.shape[0], step):
             yield {"img": self.images[s:s + step], "label": self._labels[s:s + step]}
+
+
+class ResidentRaggedSet:
+    """The ragged counterpart: images [R, 3, Res, Res] laid out class after class, `row_labels` [R] (host) the class of every row, a
+    class owning as many rows as it has.  Yields whole classes, at most `batch_rows` rows at a time, with "shots" (host int64, one
+    count per class of the batch); `.shots` is int32 [num_classes], the rows of every class of the vocabulary.  With world > 1 the
+    set is class-sharded (`presharded`): a rank keeps the classes of its `shard_range`."""
+
+    def __init__(self, images: torch.Tensor, row_labels, batch_rows: int, rank: int = 0, world: int = 1, num_classes: int = 0):
+        from .shard import ragged_batches, shard_range, vocabulary_shots
+        items = [(i, int(l)) for i, l in enumerate(torch.as_tensor(row_labels).tolist())]
+        assert images.shape[0] == len(items)
+        self.images, self.presharded = images, world > 1
+        self.shots = vocabulary_shots(items, num_classes)
+        if world > 1:
+            lo, hi = shard_range(self.shots.shape[0], rank, world)
+            items = [it for it in items if lo <= it[1] < hi]
+        self.items = items
+        self.spans = ragged_batches(items, batch_rows)
+
+    def __len__(self) -> int:
+        return len(self.spans)
+
+    def __iter__(self) -> Iterator[dict]:
+        for a, b, shots in self.spans:
+            rows = torch.tensor([i for i, _ in self.items[a:b]], dtype=torch.long)
+            yield {"img": self.images[rows.to(self.images.device)], "label": torch.tensor([l for _, l in self.items[a:b]], dtype=torch.long),
+                   "shots": torch.tensor(shots, dtype=torch.long)}

@@ -239,15 +239,26 @@ class PipelinedFolderLoader:
     def __init__(self, items: Sequence[Tuple[str, int]], batch_size: int, size: int, rank: int = 0, world: int = 1,
                  num_classes: int = 0, workers: int = 8, prefetch: int = 3, device: str = "cuda:0", chunk: int = 8,
                  fast_decode: bool = False, interpolation: str = "bicubic", mean=PIXEL_MEAN, std=PIXEL_STD,
-                 device_resize: bool = True, raw_cap_bytes: int = 768 * 1024):
+                 device_resize: bool = True, raw_cap_bytes: int = 768 * 1024, ragged: bool = False):
+        """ragged: `items` is a ragged exemplar set (cli.layout_exemplars_ragged).  A batch then holds whole classes, at most
+        `batch_size` rows, and carries "shots" (host int64 [n_cls]); `.shots` is int32 [C], the rows of every class of the vocabulary."""
         self.bs, self.size = int(batch_size), int(size)
         self.interpolation, self.mean, self.std = interpolation, mean, std
         self.presharded = world > 1
+        self.shots = None
+        if ragged:
+            from .shard import vocabulary_shots
+            self.shots = vocabulary_shots(items, num_classes)
         if world > 1:
             from .shard import shard_range
             lo, hi = shard_range(num_classes or (1 + max(l for _, l in items)), rank, world)
             items = [it for it in items if lo <= it[1] < hi]
         self.items = list(items)
+        if ragged:
+            from .shard import ragged_batches
+            self.spans = ragged_batches(self.items, self.bs)
+        else:                                        # (start, end, shots of the batch's classes: None outside ragged mode)
+            self.spans = [(s, min(s + self.bs, len(self.items)), None) for s in range(0, len(self.items), self.bs)]
         self.workers, self.prefetch, self.chunk, self.fast = max(1, int(workers)), max(2, int(prefetch)), max(1, int(chunk)), fast_decode
         self.device = torch.device(device)
         crop = self.size * self.size * 3
@@ -255,7 +266,7 @@ class PipelinedFolderLoader:
         self.stats: Dict[str, float] = {}
 
     def __len__(self):
-        return (len(self.items) + self.bs - 1) // self.bs
+        return len(self.spans)
 
     def warm(self) -> "PipelinedFolderLoader":
         """Start (or find) the decode pool now: the worker interpreters come up while the caller is still loading weights."""
@@ -302,7 +313,7 @@ class PipelinedFolderLoader:
             slot = b % slots
             if copied[slot] is not None:
                 copied[slot].synchronize()
-            chunk_items = self.items[b * B:(b + 1) * B]
+            chunk_items = self.items[self.spans[b][0]:self.spans[b][1]]
             metas[slot] = {}
             pending[slot] = (len(chunk_items) + self.chunk - 1) // self.chunk
             for ci, s in enumerate(range(0, len(chunk_items), self.chunk)):
@@ -338,7 +349,8 @@ class PipelinedFolderLoader:
                     metas[s][ci] = ms
                     pending[s] -= 1
                 t_wait += time.perf_counter() - tw
-                n = min(B, len(self.items) - b * B)
+                first, last, shots = self.spans[b]
+                n = last - first
                 batch_metas = [m for ci in sorted(metas[slot]) for m in metas[slot][ci]]
                 assert len(batch_metas) == n
                 n_host += sum(m[3] for m in batch_metas)
@@ -367,8 +379,10 @@ class PipelinedFolderLoader:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(compute)
                 timers.append(ev)
-                labels = torch.tensor([l for _, l in self.items[b * B:b * B + n]], dtype=torch.long)
-                yield {"img": dev_f16[k][:n], "label": labels}
+                batch = {"img": dev_f16[k][:n], "label": torch.tensor([l for _, l in self.items[first:last]], dtype=torch.long)}
+                if shots is not None:
+                    batch["shots"] = torch.tensor(shots, dtype=torch.long)
+                yield batch
                 consumed[k] = torch.cuda.Event()
                 consumed[k].record(torch.cuda.current_stream(self.device))
             if timers:

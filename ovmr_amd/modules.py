@@ -271,12 +271,18 @@ class PromptLearner:
         return torch.cat([prompt_tokens[:, :2], ins_tokens.type(self.prompt_tokens.dtype),
                           prompt_tokens[:, 2:-self.n_ctx]], dim=1)
 
-    def forward(self, exemplar_img_feats: torch.Tensor, label: torch.Tensor, ori_text_len: torch.Tensor):
-        """:159-176 -> (mm_prompts_list, mm_lens, v_prompts_list, v_lens, agg_img_token_)."""
+    def forward(self, exemplar_img_feats: torch.Tensor, label: torch.Tensor, ori_text_len: torch.Tensor, shots=None):
+        """:159-176 -> (mm_prompts_list, mm_lens, v_prompts_list, v_lens, agg_img_token_).  shots (a host sequence, one count per class
+        of `label`): the features are packed [R, D], class after class, and every class's tokens come from exactly its own shots[c]
+        rows (Engine.generate_tokens_ragged: per class the reference's arithmetic at num_ins = shots[c]); prompts, lengths and tokens
+        are returned as without it."""
         e = self.engine
         mm_lens = ori_text_len + self.n_ctx                                                     # :163
         v_lens = torch.ones_like(ori_text_len, dtype=torch.int32) + self.n_ctx                  # :165
-        tokens = e.generate_tokens(exemplar_img_feats)                                          # :167-169
+        if shots is not None:
+            tokens = e.generate_tokens_ragged(exemplar_img_feats, shots)
+        else:
+            tokens = e.generate_tokens(exemplar_img_feats)                                      # :167-169
         mm = e.assemble_prompts(self.prompt_tokens, label, tokens)                              # :171
         v = e.assemble_prompts(self.visual_prompt_temp, None, tokens)                           # :173
         return [mm], mm_lens, [v], v_lens, tokens
@@ -410,6 +416,76 @@ class _ImageEncoder:
         return self.engine.encode_image(image, normalize=False)
 
 
+class _RaggedRows:
+    """The exemplar rows of a generation in ragged mode: a batch that carries "shots" (a HOST int64 tensor, one count per class; the
+    batch's rows are class after class, "label" per row as ever) gives every class exactly the images it has.  The reference has no
+    such mode: it takes NUM_SHOTS rows of every class by position (trainers/mm_classifier_one_prompt.py:237-245).  Keeps the packed
+    features and their per-row labels for the cross-validation (CustomCLIP.eval_feat4cls / eval_row_labels) and the vocabulary's
+    n_label = shots (the loader's `.shots`, int32 [C], known on every rank from the item list)."""
+
+    def __init__(self, model, loader, world: int):
+        self.model, self.loader, self.world = model, loader, world
+        self.rows, self.labels, self.counted, self.uniform_seen = [], [], [], False
+        n = getattr(loader, "shots", None)            # (a uniform loader may call its one count `shots`: only a per-class array is meant)
+        self.vocabulary_shots = n if isinstance(n, (torch.Tensor, np.ndarray)) and n.ndim == 1 else None
+
+    def takes(self, batch, batch_idx: int) -> bool:
+        if "shots" not in batch:
+            if self.rows:
+                raise RuntimeError(f"eval-set batch {batch_idx} carries no \"shots\" while earlier batches did: one mode per loader")
+            self.uniform_seen = True
+            return False
+        m = self.model
+        if self.uniform_seen:
+            raise RuntimeError(f"eval-set batch {batch_idx} carries \"shots\" while earlier batches did not: one mode per loader")
+        if m.aug_times > 1 or isinstance(batch["img"], (list, tuple)):
+            raise NotImplementedError("ragged exemplar sets (batches with \"shots\") do not take DATALOADER.K_TRANSFORMS > 1")
+        # (every rank sees every batch of a loader that is not presharded, so every rank raises HERE, before the first collective)
+        if self.world > 1 and not bool(getattr(self.loader, "presharded", False)):
+            raise RuntimeError("ragged exemplar sets with more than one rank need a presharded (class-sharded) eval-set loader: the "
+                               "round-robin bound of the all-gather assumes TEST.BATCH_SIZE // NUM_SHOTS classes per batch")
+        if self.world > 1 and self.vocabulary_shots is None:
+            raise RuntimeError("ragged exemplar sets with more than one rank need the loader's `.shots` (int32 [C], the whole vocabulary)")
+        return True
+
+    def encode(self, batch):
+        """-> (feats [R, D] fp16, the classes' labels [n_cls] on the device, shots as a host list)."""
+        m, dev = self.model, self.model.device
+        shots = batch["shots"]
+        if not isinstance(shots, torch.Tensor) or shots.is_cuda:
+            raise ValueError("a batch's \"shots\" is a HOST int64 tensor [n_cls]")
+        shots = [int(n) for n in shots.tolist()]
+        label = batch["label"]
+        if sum(shots) != label.shape[0] or min(shots, default=1) < 1:
+            raise ValueError(f"a batch's shots {shots} do not describe its {label.shape[0]} rows")
+        first = torch.tensor([0] + shots[:-1], dtype=torch.long).cumsum(0)
+        exemplar_label = label.to(dev, non_blocking=True)
+        feats = m.engine.encode_image(batch["img"], normalize=True)
+        self.rows.append(feats)
+        self.labels.append(exemplar_label.to(torch.int32))
+        exemplar_label = exemplar_label[first.to(dev)]
+        self.counted.append((exemplar_label, torch.tensor(shots, dtype=torch.int32)))
+        return feats, exemplar_label, shots
+
+    def finish(self):
+        m, dev = self.model, self.model.device
+        if self.uniform_seen or (not self.rows and self.vocabulary_shots is None):
+            return                                                                  # uniform mode: nothing of this class's is used
+        C, D = len(m.tokenized_prompts), m.engine.spec.embed_dim
+        m.eval_feat4cls = torch.cat(self.rows) if self.rows else torch.zeros((0, D), dtype=torch.float16, device=dev)
+        m.eval_row_labels = torch.cat(self.labels) if self.labels else torch.zeros(0, dtype=torch.int32, device=dev)
+        n_label = self.vocabulary_shots
+        if n_label is not None:
+            n_label = torch.as_tensor(n_label).to(device=dev, dtype=torch.int32)
+            if n_label.shape != (C,):
+                raise ValueError(f"the loader's shots describe {tuple(n_label.shape)} classes, the vocabulary has {C}")
+        else:                                                                       # one process: the batches have said it all
+            n_label = torch.zeros(C, dtype=torch.int32, device=dev)
+            for labels, shots in self.counted:
+                n_label[labels] = shots.to(dev)
+        m._ragged_n_label = n_label
+
+
 class CustomCLIP(_TwoInFlight):
     """trainers/mm_classifier_one_prompt.py:179-364 (evaluation / classifier-generation branch)."""
 
@@ -490,6 +566,8 @@ class CustomCLIP(_TwoInFlight):
         self.inference_text_initialized = torch.zeros(C, dtype=torch.int32, device=dev)
         self.visual_tokens = torch.ones((C, n_ctx, D), **f16)
         self.eval_feat4cls = torch.zeros((C, S, D), **f16)
+        self.eval_row_labels = None           # ragged mode: eval_feat4cls is then the packed [R_local, D] rows, these their int32 labels
+        self._ragged_n_label = None
         # text rows: precomputed by PromptLearner.__init__ (:118-126) for < 5000 classes in one process; otherwise
         # (large vocabularies, or class-sharded ranks) each exemplar batch encodes the prompts of its own classes
         streamed_text = pl.zero_shot_classifier is None or getattr(self, "_text_streamed", False)
@@ -506,7 +584,24 @@ class CustomCLIP(_TwoInFlight):
         local_labels = []
         presharded = bool(getattr(eval_set_loader, "presharded", False))
         cpb = max(1, self.cfg.DATALOADER.TEST.BATCH_SIZE // S)
+        ragged = _RaggedRows(self, eval_set_loader, world)
         for batch_idx, batch in enumerate(eval_set_loader):
+            if ragged.takes(batch, batch_idx):                                      # every class uses exactly the images it has
+                if not presharded and batch_idx % world != rank:
+                    continue
+                feats, exemplar_label, shots = ragged.encode(batch)
+                mm_p, mm_l, v_p, v_l, tokens = pl(feats, exemplar_label, pl.eos_index[exemplar_label], shots=shots)
+                if streamed_text:
+                    mm, v, t = self.get_mm_v_feats(mm_p, mm_l, v_p, v_l, self.tokenized_prompts[exemplar_label])
+                    text_clf[exemplar_label] = t
+                else:
+                    mm, v = self.get_mm_v_feats(mm_p, mm_l, v_p, v_l)
+                self.mm_classifier[exemplar_label] = mm
+                self.visual_classifer[exemplar_label] = v
+                self.inference_text_initialized.index_fill_(0, exemplar_label, 1)
+                self.visual_tokens[exemplar_label] = tokens.half()
+                local_labels.append(exemplar_label)
+                continue
             if world > 1 and not presharded and batch["label"].shape[0] // S > cpb:
                 # every rank iterates over every batch of a round-robin loader, so every rank raises HERE, before any of them
                 # has entered the all-gather whose block size assumes at most `cpb` classes per batch (shard.local_class_bound)
@@ -532,6 +627,7 @@ class CustomCLIP(_TwoInFlight):
                                                                                     #  a synchronisation in the middle of the head)
             self.visual_tokens[exemplar_label] = tokens.half()                      # :255
             local_labels.append(exemplar_label)
+        ragged.finish()
         return torch.cat(local_labels) if local_labels else torch.zeros(0, dtype=torch.long, device=dev)
 
     @torch.no_grad()
@@ -688,17 +784,24 @@ class CustomCLIP(_TwoInFlight):
         e, dev, dist = self.engine, self.device, self._dist
         C, S = len(self.tokenized_prompts), self.test_num_ins
         counts = torch.zeros((3, 2, C), dtype=torch.int32, device=dev)
-        if local.numel():
-            rows = self.eval_feat4cls[local].flatten(0, 1)
-            row_labels = local.to(torch.int32).unsqueeze(1).expand(-1, S).reshape(-1)   # :261 (repeat_interleave: five launches for the same rows)
+        ragged = getattr(self, "eval_row_labels", None) is not None
+        if ragged or local.numel():
+            if ragged:                                                              # the packed rows as they are, a label per row
+                rows, row_labels = self.eval_feat4cls, self.eval_row_labels
+            else:
+                rows = self.eval_feat4cls[local].flatten(0, 1)
+                row_labels = local.to(torch.int32).unsqueeze(1).expand(-1, S).reshape(-1)   # :261 (repeat_interleave: five launches for the same rows)
             for m, clf in enumerate((mm_classifier, v_classifier, t_classifier)):   # order :272
                 e.xval_counts(rows, row_labels, clf, counts[m, 0], counts[m, 1])
         if dist:
             from .shard import all_reduce_counts
             counts = all_reduce_counts(counts, dist)                                # ONE all-reduce
-        if getattr(self, "_n_label_key", None) != (C, S):
-            self._n_label, self._n_label_key = torch.full((C,), S, dtype=torch.int32, device=dev), (C, S)
-        n_label = self._n_label
+        if ragged:                                                                  # a class has as many rows as it has images
+            n_label = self._ragged_n_label
+        else:
+            if getattr(self, "_n_label_key", None) != (C, S):
+                self._n_label, self._n_label_key = torch.full((C,), S, dtype=torch.int32, device=dev), (C, S)
+            n_label = self._n_label
         self.xval_counts = counts
         return e.fusion_weights(counts, n_label, tau)
 
@@ -712,9 +815,15 @@ class CustomCLIP(_TwoInFlight):
         C, S, D = len(self.tokenized_prompts), self.test_num_ins, e.spec.embed_dim
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
         self.eval_feat4cls = torch.zeros((C, S, D), dtype=torch.float16, device=dev)
+        self.eval_row_labels = self._ragged_n_label = None
         presharded = bool(getattr(eval_set_loader, "presharded", False))
         local_labels = []
+        ragged = _RaggedRows(self, eval_set_loader, world)
         for batch_idx, batch in enumerate(eval_set_loader):
+            if ragged.takes(batch, batch_idx):
+                if presharded or batch_idx % world == rank:
+                    local_labels.append(ragged.encode(batch)[1])
+                continue
             if not presharded and batch_idx % world != rank:
                 continue
             image = self._batch_images(batch, dev)
@@ -722,6 +831,7 @@ class CustomCLIP(_TwoInFlight):
             exemplar_label = label.reshape(image.shape[0] // S, S)[:, 0]              # :261
             self.eval_feat4cls[exemplar_label] = e.encode_image(image, normalize=True).reshape(-1, S, D)   # :263-267
             local_labels.append(exemplar_label)
+        ragged.finish()
         local = torch.cat(local_labels) if local_labels else torch.zeros(0, dtype=torch.long, device=dev)
         clfs = [c.to(device=dev, dtype=torch.float16).contiguous() for c in (mm_classifier, v_classifier, t_classifier)]
         self.fusion_weight = self._xval_fusion_weight(local, *clfs, 10.0)

@@ -59,6 +59,7 @@ SIGNATURES = {
     "ovmr_encode_text_ensemble": (c_i, [c_p, c_p, c_i, c_i, ctypes.POINTER(ctypes.c_int32), c_p, c_p]),
     "ovmr_embed_tokens": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "ovmr_generate_tokens": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
+    "ovmr_generate_tokens_ragged": (c_i, [c_p, c_p, ctypes.POINTER(ctypes.c_int32), c_p, c_i, c_i, c_p, c_p]),
     "ovmr_assemble_prompts": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     "ovmr_xval_counts": (c_i, [c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     "ovmr_fusion_weights": (c_i, [c_p, c_p, c_p, c_i, ctypes.c_float, c_p, c_p]),
@@ -86,6 +87,7 @@ SIGNATURES = {
     "ovmr_debug_attention": (c_i, [c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "ovmr_debug_gemm_strided": (c_i, [c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_p, c_p,
                                       c_i, c_p]),
+    "ovmr_debug_attention_f32_varlen": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "ovmr_debug_attention_q": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "ovmr_debug_attention_route": (c_i, [c_i, c_i, c_i, c_i]),
     "ovmr_debug_gemm_route": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i)]),
@@ -393,6 +395,26 @@ class Engine:
         Cb, S, D = feats.shape
         out = torch.empty((Cb, self.n_ctx, D), dtype=torch.float32, device=self.device)
         self._ck(self.lib.ovmr_generate_tokens(self.h, _ptr(feats), Cb, S, _ptr(out), _stream()), "ovmr_generate_tokens")
+        return out
+
+    def generate_tokens_ragged(self, feats: torch.Tensor, shots) -> torch.Tensor:
+        """ovmr_generate_tokens_ragged: feats [R, D], class after class, class c owning shots[c] rows -> tokens [Cb, n_ctx, D] fp32, each
+        class bit-identical to generate_tokens on its rows alone.  `shots` is a HOST sequence (list, numpy array or CPU tensor): the
+        library's host array and the kernels' device prefix sum are both built here from this ONE list, so they cannot disagree."""
+        if isinstance(shots, torch.Tensor):
+            if shots.is_cuda:
+                raise ValueError("shots must live on the host: the library plans its launches from them")
+            shots = shots.tolist()
+        shots = [int(n) for n in shots]
+        feats = self._dev(feats, torch.float16)
+        if feats.dim() != 2:
+            raise ValueError(f"generate_tokens_ragged takes packed [R, D] features, got {tuple(feats.shape)}")
+        Cb, (R, D) = len(shots), feats.shape
+        host = (ctypes.c_int32 * max(1, Cb))(*shots)
+        offsets = self._dev(np.concatenate([[0], np.cumsum(np.asarray(shots, dtype=np.int64))]).astype(np.int32))
+        out = torch.empty((Cb, self.n_ctx, D), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.ovmr_generate_tokens_ragged(self.h, _ptr(feats), host, _ptr(offsets), Cb, R, _ptr(out), _stream()),
+                 "ovmr_generate_tokens_ragged")
         return out
 
     def assemble_prompts(self, base: torch.Tensor, labels: Optional[torch.Tensor], tokens: torch.Tensor) -> torch.Tensor:

@@ -41,6 +41,38 @@ def local_class_bound(num_classes: int, world: int, presharded: bool, classes_pe
     return -(-num_classes // world) + 2 * max(1, classes_per_batch)
 
 
+def ragged_batches(items, batch_size: int) -> List[Tuple[int, int, List[int]]]:
+    """The batches of a ragged exemplar set: `items` [(path, label)] laid out class after class (cli.layout_exemplars_ragged) ->
+    [(start, end, shots of the batch's classes)], whole classes per batch, as many as fit `batch_size` rows.  A class with more rows
+    than a batch holds is refused here, before anything is decoded."""
+    runs: List[Tuple[int, int, int]] = []                      # (label, start, end) of every run of equal labels
+    for i, it in enumerate(items):
+        if runs and runs[-1][0] == it[1]:
+            runs[-1] = (it[1], runs[-1][1], i + 1)
+        else:
+            runs.append((it[1], i, i + 1))
+    if len({r[0] for r in runs}) != len(runs):
+        raise ValueError("a ragged exemplar set lists every class's rows consecutively (cli.layout_exemplars_ragged)")
+    out: List[Tuple[int, int, List[int]]] = []
+    for label, a, b in runs:
+        if b - a > batch_size:
+            raise ValueError(f"class {label} has {b - a} exemplar rows, more than one batch of DATALOADER.TEST.BATCH_SIZE = {batch_size} holds")
+        if out and b - out[-1][0] <= batch_size:
+            out[-1] = (out[-1][0], b, out[-1][2] + [b - a])
+        else:
+            out.append((a, b, [b - a]))
+    return out
+
+
+def vocabulary_shots(items, num_classes: int) -> torch.Tensor:
+    """int32 [num_classes]: the exemplar rows of every class of the WHOLE item list (what a ragged loader publishes as `.shots`: every
+    rank knows it from the list, so the F1 preference's n_label needs no collective)."""
+    n = torch.zeros(max(num_classes, 1 + max((it[1] for it in items), default=-1)), dtype=torch.int32)
+    for it in items:
+        n[it[1]] += 1
+    return n
+
+
 def _staged(t: torch.Tensor, dist) -> torch.Tensor:
     """gloo moves host memory: stage device tensors through the CPU (CPU tests, or several ranks sharing one GPU)."""
     return t.cpu() if dist.get_backend() == "gloo" and t.is_cuda else t

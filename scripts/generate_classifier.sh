@@ -7,6 +7,7 @@
 # (output_ovmr/generated_classifiers, skipped when it exists), same files in it (mm_classifiers.pt, visual_tokens.pt).  What this path
 # needs in addition, from the environment: CLIP_WEIGHTS (OpenAI CLIP .pt: there is no download here) and OVMR_BPE_PATH (default:
 # $OVMR_REF/clip/bpe_simple_vocab_16e6.txt.gz).  DATA, MODEL_DIR, CFG, SHOTS, LOADEP, WORKERS may be overridden the same way.
+# RAGGED=1 passes --ragged-shots: every class uses exactly the exemplars it has, up to SHOTS, and none twice.
 # DRY_RUN=1 prints the command line instead of running it.
 # GPU_ID selects the device with HIP_VISIBLE_DEVICES; a comma-separated list starts one rank per GPU (torch.distributed.run, RCCL):
 # the classes are sharded over the ranks.
@@ -31,12 +32,13 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 HERE=$(cd "$(dirname "$0")/.." && pwd)
 export PYTHONPATH=$HERE${PYTHONPATH:+:$PYTHONPATH}
 N=$(echo "$GPUS" | awk -F, '{print NF}')
+if [ "${RAGGED:-0}" = 1 ]; then RAGGED_FLAG=--ragged-shots; else RAGGED_FLAG=; fi
 ARGS=(--root "$DATA" --seed "$SEED" --trainer $TRAINER
       --dataset-config-file "$REF/configs/datasets/${DATASET}.yaml"
       --config-file "$REF/configs/trainers/${TRAINER}/${CFG}.yaml"
       --output-dir "$DIR" --model-dir "$MODEL_DIR" --load-epoch "$LOADEP"
       --eval_mode "$EVAL_MODE" --eval_tau "$EVAL_TAU" --n_ctx "$N_CTX" --eval-only
-      --clip-weights "$CLIP_WEIGHTS" ${WORKERS:+--workers "$WORKERS"}
+      --clip-weights "$CLIP_WEIGHTS" ${WORKERS:+--workers "$WORKERS"} ${RAGGED_FLAG:+$RAGGED_FLAG}
       DATASET.NUM_SHOTS "$SHOTS" DATASET.SUBSAMPLE_CLASSES "$SUB")
 if [ -n "$DRY_RUN" ]; then                     # print the command instead of running it (tests/test_next_rows_cpu.py)
     [ "$N" -gt 1 ] && echo "ranks $N"
