@@ -171,7 +171,9 @@ int ovmr_encode_text_ensemble(ovmr_handle* h, const int64_t* ids, int T, int C, 
 int ovmr_embed_tokens(ovmr_handle* h, const int64_t* ids, int N, int L, void* out_f16, ovmr_stream stream);
 
 /* PromptLearner.forward, visual-token generator part (trainers/mm_classifier_one_prompt.py:167-169):
- * feats [Cb, S, embed_dim] fp16 -> tokens [Cb, n_ctx, embed_dim] fp32 (aggregator in fp32). */
+ * feats [Cb, S, embed_dim] fp16 -> tokens [Cb, n_ctx, embed_dim] fp32 (aggregator in fp32).  The arithmetic mode of the sequence
+ * table ovmr_generate_tokens_ragged reads (AggSeqs, csrc/common.h): the same generator, the same kernels (agg_input_kernel,
+ * attn_f32_small, agg_output_kernel), class c's rows at c * (n_ctx + S) computed, no device array loaded. */
 int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S,
                          float* tokens_f32, ovmr_stream stream);
 
@@ -372,7 +374,8 @@ int ovmr_debug_gemm_strided(int variant, const void* A, int lda, const void* W, 
                             const float* beta, int row_step, ovmr_stream stream);
 /* fp32 attention (hd = 64) over nseq sequences packed row after row: sequence b is the rows [offsets[b] + b * n_ctx,
  * offsets[b + 1] + (b + 1) * n_ctx) of qkv [M, 3 * H * 64], offsets_dev a DEVICE int32 [nseq + 1] exclusive prefix sum, every length
- * in [1, max_len]; out [M, H * 64].  Row by row the arithmetic of ovmr_debug_attention(f32 = 1).  -2 for max_len > 128. */
+ * in [1, max_len]; out [M, H * 64].  The table mode of attn_f32_small, the kernel ovmr_debug_attention(f32 = 1) runs in its uniform
+ * mode: row by row the same arithmetic.  -2 for max_len > 128. */
 int ovmr_debug_attention_f32_varlen(const void* qkv, void* out, const int32_t* offsets_dev, int nseq, int n_ctx, int max_len, int H,
                                     ovmr_stream stream);
 /* fp16 attention for the first Lq <= L queries of every sequence (the last vision block runs Lq = 1, the CLS query):

@@ -11,7 +11,7 @@
 //     O^T is lane local;
 //   * V is transposed while it is staged ([d][key] rows of 136 B, conflict-free ds_read_b64);
 //     K rows are XOR-swizzled 128-byte rows (conflict-free ds_read_b128).
-// fp32 kernel (aggregator, L = n_ctx + shots <= 128): one thread per query row, K/V in LDS.
+// fp32 kernel (aggregator, sequences of n_ctx + shots <= 128 rows, equal or each its own): one thread per query row, K/V in LDS.
 #include "attn_common.h"
 #include "../../include/ovmr_hip.h"
 
@@ -132,16 +132,22 @@ __global__ __launch_bounds__(256) void attn_f16_v0(const half_t* __restrict__ qk
     }
 }
 
-// fp32, L <= 128: one thread per query row, single-pass online softmax.
-__global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ qkv, float* __restrict__ out,
-                                                      int L, int H, float scale) {
+// fp32, sequences of at most 128 rows packed row after row (AggSeqs, common.h): one workgroup per (sequence, head), K and V in LDS sized
+// by the launch's longest sequence (q.len rows each), a thread per query row through attn::f32_row, single-pass online softmax.  A
+// row's bits depend on its own sequence alone.  TABLE: the starts come from the device prefix sum, clamped, and a workgroup takes at
+// most q.len rows; uniform: sequence b is the rows [b * q.len, (b + 1) * q.len), nothing loaded.
+template <bool TABLE>
+__global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ qkv, float* __restrict__ out, const AggSeqs q,
+                                                      int H, float scale) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* sK = sm;
-    float* sV = sm + L * 64;
+    float* sV = sm + q.len * 64;
     const int tid = threadIdx.x;
     const int h = blockIdx.x % H, b = blockIdx.x / H;
     const int D = H * 64, ld = 3 * D;
-    const float* base = qkv + (long)b * L * ld + h * 64;
+    const long r0 = q.start<TABLE>(b);
+    const int L = TABLE ? (int)min(max(q.start<TABLE>(b + 1) - r0, 0L), (long)q.len) : q.len;
+    const float* base = qkv + r0 * ld + h * 64;
     for (int i = tid; i < L * 16; i += blockDim.x) {
         const int row = i >> 4, c = i & 15;
         *(float4_t*)(sK + row * 64 + c * 4) = *(const float4_t*)(base + D + (long)row * ld + c * 4);
@@ -149,37 +155,7 @@ __global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ 
     }
     __syncthreads();
     if (tid >= L) return;
-    attn::f32_row(base + (long)tid * ld, sK, sV, L, scale, out + ((long)b * L + tid) * D + h * 64);
-}
-
-// fp32, sequences of different lengths (each <= 128) packed row after row: sequence b of the launch is the rows
-// [start(b), start(b + 1)) of qkv [M, 3 H 64], start(b) = offsets[b] - base + b * n_ctx (`offsets`: a DEVICE exclusive prefix sum of
-// the classes' shots, `base` its value at the launch's first class; every class has n_ctx rows in front of its shots).  One workgroup
-// per (sequence, head), K and V in LDS sized by the launch's longest sequence (`cap` rows each), a thread per query row through the
-// same attn::f32_row as attn_f32_small: a row's bits depend on its own sequence alone.
-// A device array sets addresses here, so every start is clamped to [0, M] and a workgroup takes at most `cap` rows: offsets that
-// disagree with the host's plan give wrong values, never an access outside qkv / out / LDS.
-__global__ __launch_bounds__(128) void attn_f32_varlen(const float* __restrict__ qkv, float* __restrict__ out,
-                                                       const int* __restrict__ offsets, int base_off, int n_ctx, int M, int cap,
-                                                       int H, float scale) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* sK = sm;
-    float* sV = sm + cap * 64;
-    const int tid = threadIdx.x;
-    const int h = blockIdx.x % H, b = blockIdx.x / H;
-    const int D = H * 64, ld = 3 * D;
-    auto start = [&](int s) { return (int)min(max((long)offsets[s] - base_off + (long)s * n_ctx, 0L), (long)M); };
-    const int r0 = start(b);
-    const int L = min(max(start(b + 1) - r0, 0), cap);
-    const float* base = qkv + (long)r0 * ld + h * 64;
-    for (int i = tid; i < L * 16; i += blockDim.x) {
-        const int row = i >> 4, c = i & 15;
-        *(float4_t*)(sK + row * 64 + c * 4) = *(const float4_t*)(base + D + (long)row * ld + c * 4);
-        *(float4_t*)(sV + row * 64 + c * 4) = *(const float4_t*)(base + 2 * D + (long)row * ld + c * 4);
-    }
-    __syncthreads();
-    if (tid >= L) return;
-    attn::f32_row(base + (long)tid * ld, sK, sV, L, scale, out + (long)(r0 + tid) * D + h * 64);
+    attn::f32_row(base + (long)tid * ld, sK, sV, L, scale, out + (r0 + tid) * D + h * 64);
 }
 
 // Which kernel a launch of `variant` runs: 0 attn_f16_v0, 1 attn_f16_v1, 2 attn_f16_short, 3 attn_f16_v3, 5 attn_f16_v5
@@ -226,20 +202,12 @@ int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq,
     return (int)hipGetLastError();
 }
 
-int launch_attention_f32(const float* qkv, float* out, int B, int L, int H, hipStream_t s) {
-    if (B <= 0 || L <= 0) return 0;
-    if (L > 128) return -2;
-    const size_t lds = (size_t)2 * L * 64 * sizeof(float);
-    hipLaunchKernelGGL(attn_f32_small, dim3(B * H), dim3(128), lds, s, qkv, out, L, H, 0.125f);
-    return (int)hipGetLastError();
-}
-
-int launch_attention_f32_varlen(const float* qkv, float* out, const int* offsets, int base_off, int nseq, int n_ctx, int max_len,
-                                int M, int H, hipStream_t s) {
-    if (nseq <= 0 || M <= 0) return 0;
-    if (max_len < 1 || max_len > 128) return -2;
-    const size_t lds = (size_t)2 * max_len * 64 * sizeof(float);
-    hipLaunchKernelGGL(attn_f32_varlen, dim3((unsigned)nseq * H), dim3(128), lds, s, qkv, out, offsets, base_off, n_ctx, M, max_len, H,
-                       0.125f);
+int launch_attention_f32(const float* qkv, float* out, const AggSeqs& q, int H, hipStream_t s) {
+    if (q.nseq <= 0 || q.M <= 0) return 0;
+    if (q.len < 1 || q.len > 128) return -2;
+    const size_t lds = (size_t)2 * q.len * 64 * sizeof(float);
+    const dim3 grid((unsigned)q.nseq * H);
+    if (q.offsets) hipLaunchKernelGGL(attn_f32_small<true>, grid, dim3(128), lds, s, qkv, out, q, H, 0.125f);
+    else hipLaunchKernelGGL(attn_f32_small<false>, grid, dim3(128), lds, s, qkv, out, q, H, 0.125f);
     return (int)hipGetLastError();
 }

@@ -142,7 +142,7 @@ __device__ __forceinline__ void store_row4(half_t* op, const float4_t (&o)[4], f
     }
 }
 
-// ---- the fp32 kernels (attention.hip: attn_f32_small, attn_f32_varlen) ----------------------------------------------------
+// ---- the fp32 kernels (attention.hip: attn_f32_small, both modes) ---------------------------------------------------------
 // One query row against the L keys of its own (sequence, head), K and V in LDS as [key][64] fp32: keys in increasing order, s summed
 // over d in increasing order and then scaled, the online maximum, __expf, l and o updated in this order, one reciprocal at the end.
 // Both kernels go through this one function, and the library is built with -ffp-contract=off and without fast-math: a row's bits do

@@ -120,6 +120,27 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// The sequences of one fp32 aggregator pass (ovmr_generate_tokens, ovmr_generate_tokens_ragged): class c of the pass owns the rows
+// [start(c), start(c + 1)) of the pass's M packed rows -- n_ctx cls_token rows, then its shots, the rows first_shot(c) ... of feats.
+// The three kernels that read it (attn_f32_small, agg_input_kernel, agg_output_kernel) take the mode as a template parameter:
+//   TABLE    `offsets` is a DEVICE exclusive prefix sum of the classes' shots, `base` its value at the pass's first class, `len` the
+//            longest sequence.  A device array sets addresses, so every start is clamped to [0, M] (and the kernels clamp what they
+//            build from it to `len` rows of LDS and the R rows of feats): offsets that disagree with the host's plan give wrong values,
+//            never an access outside the buffers.
+//   uniform  (offsets == nullptr) every class has len - n_ctx shots and `base` shots of the call lie before the pass: the arithmetic
+//            mode of the same table, computed and never loaded -- the uniform call has no device array and may not make one.
+struct AggSeqs {
+    const int* offsets;
+    int base, nseq, n_ctx, len, M;
+    template <bool TABLE> __device__ __forceinline__ long start(int c) const {
+        if (!TABLE) return (long)c * len;
+        return min(max((long)offsets[c] - base + (long)c * n_ctx, 0L), (long)M);
+    }
+    template <bool TABLE> __device__ __forceinline__ long first_shot(int c) const {
+        return TABLE ? (long)offsets[c] : base + (long)c * (len - n_ctx);
+    }
+};
+
 #define HIP_CHECK_RET(expr)                                   \
     do {                                                      \
         hipError_t _e = (expr);                               \
@@ -139,10 +160,7 @@ int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq,
 // up to 4 groups of sequences of at most 32 tokens in one launch (attention_short.hip); -100: not taken
 int launch_attention_f16_short(const half_t* qkv, half_t* out, int n_groups, const int* nseq, const int* L, const long* row0, int H,
                                int causal, hipStream_t s);
-int launch_attention_f32(const float* qkv, float* out, int B, int L, int H, hipStream_t s);
-// sequences of n_ctx + shots rows packed row after row, from a device prefix sum of the shots (attention.hip, attn_f32_varlen)
-int launch_attention_f32_varlen(const float* qkv, float* out, const int* offsets, int base_off, int nseq, int n_ctx, int max_len,
-                                int M, int H, hipStream_t s);
+int launch_attention_f32(const float* qkv, float* out, const AggSeqs& q, int H, hipStream_t s);   // attention.hip, attn_f32_small
 int launch_im2col(const void* img, int img_is_f32, half_t* out, int B, int R, int P, int Kpad, hipStream_t s);
 int launch_fill_cls(half_t* x, const half_t* cls_pos, int B, int L, int W, hipStream_t s);
 int launch_l2norm_f16(half_t* x, int rows, int D, hipStream_t s);
@@ -159,11 +177,9 @@ int launch_pack_rows(const half_t* mm, const half_t* v, const half_t* t, const h
                      int bound, half_t* block, hipStream_t s);
 int launch_unpack_rows(const half_t* gathered, int rows, int C, int D, int n_ctx, half_t* mm, half_t* v, half_t* t, half_t* tokens, int* seen,
                        hipStream_t s);
-int launch_agg_input(const float* cls_token, const half_t* feats, float* x, int Cb, int S, int n_ctx, int D, hipStream_t s);
-int launch_agg_output(const float* x, float* tokens, int Cb, int La, int n_ctx, int D, hipStream_t s);
-int launch_agg_input_ragged(const float* cls_token, const half_t* feats, const int* offsets, int base, float* x, int Cb, int M, int R,
-                            int n_ctx, int D, hipStream_t s);
-int launch_agg_output_ragged(const float* x, const int* offsets, int base, float* tokens, int Cb, int M, int n_ctx, int D, hipStream_t s);
+// feats [R, D]: the exemplar rows of the whole call (q.first_shot indexes it)
+int launch_agg_input(const float* cls_token, const half_t* feats, int R, float* x, const AggSeqs& q, int D, hipStream_t s);
+int launch_agg_output(const float* x, float* tokens, const AggSeqs& q, int D, hipStream_t s);
 int launch_assemble_prompts(const half_t* base, const int64_t* labels, const float* tokens, half_t* out,
                             int Cb, int Lctx, int n_ctx, int D, hipStream_t s);
 int launch_argmax_counts(const half_t* logits, int ld, const int* labels, int R, int C, int* tp, int* n_pred, hipStream_t s);

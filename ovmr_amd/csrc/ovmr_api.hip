@@ -334,24 +334,48 @@ int run_block_f16(ovmr_handle* h, const Block& k, half_t* x, half_t* y, half_t* 
     return 0;
 }
 
-// The sequences of a ragged aggregator pass: class c of the pass is n_ctx + shots[c] packed rows, M rows in all, the longest max_len.
-struct PackedSeqs { const int* offsets; int base, n_ctx, max_len, M; };
-
-// Same block in fp32 (ResidualAttentionBlockWithDropout in eval mode, clip/model.py:248-251): nseq sequences of L rows, or, with
-// `packed`, of their own lengths row after row -- only the attention launch knows the difference, every other step is per row.
-int run_block_f32(ovmr_handle* h, const Block& k, float* x, float* y, float* qkv, float* hid,
-                  int nseq, int L, int W, hipStream_t s, const PackedSeqs* packed = nullptr) {
-    const int M = packed ? packed->M : nseq * L, H = W / 64;
+// Same block in fp32 (ResidualAttentionBlockWithDropout in eval mode, clip/model.py:248-251) over the q.M packed rows of an aggregator
+// pass: only the attention launch reads the sequences, every other step is per row.
+int run_block_f32(ovmr_handle* h, const Block& k, float* x, float* y, float* qkv, float* hid, const AggSeqs& q, int W, hipStream_t s) {
+    const int M = q.M, H = W / 64;
     CK(launch_layernorm(x, y, k.ln1_g, k.ln1_b, M, W, W, 1, s));
     CK(launch_gemm_f32(gemm(y, W, k.in_w, W, qkv, 3 * W, M, 3 * W, W, EPI_BIAS, k.in_b), s));
-    if (packed)
-        CK(launch_attention_f32_varlen(qkv, y, packed->offsets, packed->base, nseq, packed->n_ctx, packed->max_len, M, H, s));
-    else
-        CK(launch_attention_f32(qkv, y, nseq, L, H, s));
+    CK(launch_attention_f32(qkv, y, q, H, s));
     CK(launch_gemm_f32(gemm(y, W, k.out_w, W, x, W, M, W, W, EPI_BIAS_RES, k.out_b, x, W), s));
     CK(launch_layernorm(x, y, k.ln2_g, k.ln2_b, M, W, W, 1, s));
     CK(launch_gemm_f32(gemm(y, W, k.fc_w, W, hid, 4 * W, M, 4 * W, W, EPI_BIAS_QGELU, k.fc_b), s));
     CK(launch_gemm_f32(gemm(hid, 4 * W, k.pj_w, 4 * W, x, W, M, W, 4 * W, EPI_BIAS_RES, k.pj_b, x, W), s));
+    return 0;
+}
+
+// The visual tokens of Cb classes, after the entry points' checks: class c has shots_host[c] exemplars (every class S where shots_host
+// is null: the uniform call, which has no device table either) and its rows of feats [R, D] start at the prefix sum of the shots.
+// Chunks are runs of whole classes whose packed rows fit agg_rows_cap, at least one class each -- on equal counts floor(agg_rows_cap / La)
+// classes, the uniform call's chunks; planned from the host's counts, indexed on the device through the table.
+int generate_tokens(ovmr_handle* h, const half_t* feats, const int32_t* shots_host, int S, const int32_t* offsets_dev, int Cb, int R,
+                    float* tokens_f32, hipStream_t s) {
+    const ovmr_model_desc& d = h->d;
+    const int D = d.embed_dim;
+    auto len = [&](int c) { return d.n_ctx + (int)(shots_host ? shots_host[c] : S); };
+    for (int c0 = 0, off0 = 0; c0 < Cb;) {
+        int c1 = c0, max_len = 0;
+        long rows = 0;
+        while (c1 < Cb && (c1 == c0 || rows + len(c1) <= h->agg_rows_cap)) {
+            rows += len(c1);
+            max_len = std::max(max_len, len(c1));
+            ++c1;
+        }
+        const AggWs ws(h, h->ws, (size_t)rows);
+        if (ws.bytes() > h->ws_bytes)
+            return fail(h, OVMR_E_SHAPE, "the %ld aggregator rows of class %d do not fit the workspace", rows, c0);
+        const int Cc = c1 - c0;
+        const AggSeqs q{offsets_dev ? offsets_dev + c0 : nullptr, off0, Cc, d.n_ctx, max_len, (int)rows};
+        CK(launch_agg_input(h->cls_token, feats, R, ws.x, q, D, s));
+        for (auto& k : h->agg) CK(run_block_f32(h, k, ws.x, ws.y, ws.qkv, ws.hid, q, D, s));
+        CK(launch_agg_output(ws.x, tokens_f32 + (size_t)c0 * d.n_ctx * D, q, D, s));
+        c0 = c1;
+        off0 += (int)(rows - (long)Cc * d.n_ctx);
+    }
     return 0;
 }
 
@@ -841,16 +865,7 @@ int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S, f
     const ovmr_model_desc& d = h->d;
     const int D = d.embed_dim, La = d.n_ctx + S;
     if (La > 128) return fail(h, OVMR_E_SHAPE, "n_ctx + shots = %d exceeds 128", La);
-    hipStream_t s = (hipStream_t)stream;
-    const int chunk = (int)std::max(1L, h->agg_rows_cap / La);
-    for (int c0 = 0; c0 < Cb; c0 += chunk) {
-        const int Cc = std::min(chunk, Cb - c0);
-        const AggWs ws(h, h->ws, (size_t)Cc * La);
-        CK(launch_agg_input(h->cls_token, (const half_t*)feats_f16 + (size_t)c0 * S * D, ws.x, Cc, S, d.n_ctx, D, s));
-        for (auto& k : h->agg) CK(run_block_f32(h, k, ws.x, ws.y, ws.qkv, ws.hid, Cc, La, D, s));
-        CK(launch_agg_output(ws.x, tokens_f32 + (size_t)c0 * d.n_ctx * D, Cc, La, d.n_ctx, D, s));
-    }
-    return 0;
+    return generate_tokens(h, (const half_t*)feats_f16, nullptr, S, nullptr, Cb, Cb * S, tokens_f32, (hipStream_t)stream);
 }
 
 int ovmr_generate_tokens_ragged(ovmr_handle* h, const void* feats_f16, const int32_t* shots_host, const int32_t* offsets_dev,
@@ -868,30 +883,7 @@ int ovmr_generate_tokens_ragged(ovmr_handle* h, const void* feats_f16, const int
         sum += shots_host[c];
     }
     if (sum != R) return fail(h, OVMR_E_SHAPE, "the shots add up to %ld rows, feats has %d", sum, R);
-    hipStream_t s = (hipStream_t)stream;
-    // chunks: runs of whole classes whose packed rows fit agg_rows_cap (at least one class each); planned from the host's shots, indexed
-    // on the device from offsets_dev
-    for (int c0 = 0, off0 = 0; c0 < Cb;) {
-        int c1 = c0, shots = 0, max_len = 0;
-        long rows = 0;
-        while (c1 < Cb && (c1 == c0 || rows + d.n_ctx + shots_host[c1] <= h->agg_rows_cap)) {
-            rows += d.n_ctx + shots_host[c1];
-            shots += shots_host[c1];
-            max_len = std::max(max_len, d.n_ctx + (int)shots_host[c1]);
-            ++c1;
-        }
-        const AggWs ws(h, h->ws, (size_t)rows);
-        if (ws.bytes() > h->ws_bytes)
-            return fail(h, OVMR_E_SHAPE, "the %ld aggregator rows of class %d do not fit the workspace", rows, c0);
-        const int Cc = c1 - c0, M = (int)rows;
-        const PackedSeqs seqs{offsets_dev + c0, off0, d.n_ctx, max_len, M};
-        CK(launch_agg_input_ragged(h->cls_token, (const half_t*)feats_f16, seqs.offsets, off0, ws.x, Cc, M, R, d.n_ctx, D, s));
-        for (auto& k : h->agg) CK(run_block_f32(h, k, ws.x, ws.y, ws.qkv, ws.hid, Cc, 0, D, s, &seqs));
-        CK(launch_agg_output_ragged(ws.x, seqs.offsets, off0, tokens_f32 + (size_t)c0 * d.n_ctx * D, Cc, M, d.n_ctx, D, s));
-        c0 = c1;
-        off0 += shots;
-    }
-    return 0;
+    return generate_tokens(h, (const half_t*)feats_f16, shots_host, 0, offsets_dev, Cb, R, tokens_f32, (hipStream_t)stream);
 }
 
 int ovmr_assemble_prompts(ovmr_handle* h, const void* base_f16, const int64_t* labels, const float* tokens_f32, int Cb,
@@ -1197,7 +1189,8 @@ int ovmr_debug_layernorm(int f32, const void* x, void* y, const float* g, const 
 
 int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B, int L, int H, int causal,
                          ovmr_stream stream) {
-    return f32 ? launch_attention_f32((const float*)qkv, (float*)out, B, L, H, (hipStream_t)stream)
+    // fp32: B equal sequences are the arithmetic mode of the aggregator's sequence table
+    return f32 ? launch_attention_f32((const float*)qkv, (float*)out, AggSeqs{nullptr, 0, B, 0, L, B * L}, H, (hipStream_t)stream)
                : launch_attention_f16((const half_t*)qkv, (half_t*)out, B, L, H, causal, variant, (hipStream_t)stream);
 }
 
@@ -1205,8 +1198,8 @@ int ovmr_debug_attention_f32_varlen(const void* qkv, void* out, const int32_t* o
                                     ovmr_stream stream) {
     if (nseq < 0 || n_ctx < 0 || H < 1 || max_len < 1) return OVMR_E_ARG;
     // (no row count in this signature: the clamp bound is the most rows nseq sequences of max_len can be)
-    return launch_attention_f32_varlen((const float*)qkv, (float*)out, offsets_dev, 0, nseq, n_ctx, max_len, nseq * max_len, H,
-                                       (hipStream_t)stream);
+    return launch_attention_f32((const float*)qkv, (float*)out, AggSeqs{offsets_dev, 0, nseq, n_ctx, max_len, nseq * max_len}, H,
+                                (hipStream_t)stream);
 }
 
 int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L, int Lq, int H, int causal,

@@ -222,63 +222,31 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(const half_t* __restri
     }
 }
 
-// PromptLearner.forward (trainers/mm_classifier_one_prompt.py:167-168): cat([cls_token, feats]) in fp32
-__global__ __launch_bounds__(256) void agg_input_kernel(const float* __restrict__ cls, const half_t* __restrict__ feats,
-                                                        float* __restrict__ x, int Cb, int S, int n_ctx, int D) {
+// PromptLearner.forward (trainers/mm_classifier_one_prompt.py:167-168): cat([cls_token, feats of the class]) in fp32 for every class of
+// an aggregator pass (AggSeqs, common.h), a wave per packed row.  TABLE: the row's class is found by a search over the clamped starts
+// and the feature row is clamped to the R rows of feats; uniform: a divide, nothing loaded from the table.
+template <bool TABLE>
+__global__ __launch_bounds__(256) void agg_input_kernel(const float* __restrict__ cls, const half_t* __restrict__ feats, int R,
+                                                        float* __restrict__ x, const AggSeqs q, int D) {
     const int lane = threadIdx.x & 63;
-    const int La = n_ctx + S;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (long)Cb * La) return;
-    const int c = (int)(row / La), t = (int)(row - (long)c * La);
-    for (int k = lane * 4; k < D; k += 256) {
-        float4_t v;
-        if (t < n_ctx) {
-            v = *(const float4_t*)(cls + (long)t * D + k);
-        } else {
-            half4_t h = *(const half4_t*)(feats + ((long)c * S + (t - n_ctx)) * D + k);
-            v = (float4_t){(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+    if (row >= q.M) return;
+    int c;
+    if (TABLE) {
+        int lo = 0, hi = q.nseq - 1;                      // the last class whose first row is at or before `row`
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (q.start<TABLE>(mid) <= row) lo = mid; else hi = mid - 1;
         }
-        *(float4_t*)(x + row * D + k) = v;
-    }
-}
-
-// aggregator(...)[0:n_ctx] (:169) -> tokens [Cb, n_ctx, D] fp32
-__global__ __launch_bounds__(256) void agg_output_kernel(const float* __restrict__ x, float* __restrict__ tokens,
-                                                         int Cb, int La, int n_ctx, int D) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (long)Cb * n_ctx) return;
-    const int c = (int)(row / n_ctx), t = (int)(row - (long)c * n_ctx);
-    for (int k = lane * 4; k < D; k += 256)
-        *(float4_t*)(tokens + row * D + k) = *(const float4_t*)(x + ((long)c * La + t) * D + k);
-}
-
-// ---- the same two steps for classes with their OWN exemplar counts (ovmr_generate_tokens_ragged) -------------------------------------
-// Class c of the launch owns the packed rows [start(c), start(c + 1)) of x [M, D], start(c) = offsets[c] - base + c * n_ctx: n_ctx
-// cls_token rows, then its shots[c] = offsets[c + 1] - offsets[c] feature rows offsets[c] ... of feats [R, D].  `offsets` is a DEVICE
-// array, so every index made from it is clamped to the launch's rows (M of x, R of feats): offsets that disagree with the host's plan
-// give wrong values, never an access outside the buffers.
-__device__ __forceinline__ long ragged_start(const int* __restrict__ offsets, int base, int c, int n_ctx, int M) {
-    return min(max((long)offsets[c] - base + (long)c * n_ctx, 0L), (long)M);
-}
-
-// cat([cls_token, feats of the class]) in fp32, promoted exactly as agg_input_kernel does
-__global__ __launch_bounds__(256) void agg_input_ragged(const float* __restrict__ cls, const half_t* __restrict__ feats,
-                                                        const int* __restrict__ offsets, int base, float* __restrict__ x,
-                                                        int Cb, int M, int R, int n_ctx, int D) {
-    const int lane = threadIdx.x & 63;
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= M) return;
-    int lo = 0, hi = Cb - 1;                              // the last class whose first row is at or before `row`
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (ragged_start(offsets, base, mid, n_ctx, M) <= row) lo = mid; else hi = mid - 1;
-    }
-    const long t = max(row - ragged_start(offsets, base, lo, n_ctx, M), 0L);
-    const long src = min(max((long)offsets[lo] + (t - n_ctx), 0L), (long)R - 1);
+        c = lo;
+    } else
+        c = (int)(row / q.len);
+    const long t = TABLE ? max(row - q.start<TABLE>(c), 0L) : row - q.start<TABLE>(c);
+    long src = q.first_shot<TABLE>(c) + (t - q.n_ctx);
+    if (TABLE) src = min(max(src, 0L), (long)R - 1);
     for (int k = lane * 4; k < D; k += 256) {
         float4_t v;
-        if (t < n_ctx) {
+        if (t < q.n_ctx) {
             v = *(const float4_t*)(cls + t * D + k);
         } else {
             half4_t h = *(const half4_t*)(feats + src * D + k);
@@ -288,14 +256,15 @@ __global__ __launch_bounds__(256) void agg_input_ragged(const float* __restrict_
     }
 }
 
-// the first n_ctx rows of every class -> tokens [Cb, n_ctx, D] fp32
-__global__ __launch_bounds__(256) void agg_output_ragged(const float* __restrict__ x, const int* __restrict__ offsets, int base,
-                                                         float* __restrict__ tokens, int Cb, int M, int n_ctx, int D) {
+// aggregator(...)[0:n_ctx] (:169): the first n_ctx rows of every class -> tokens [nseq, n_ctx, D] fp32
+template <bool TABLE>
+__global__ __launch_bounds__(256) void agg_output_kernel(const float* __restrict__ x, float* __restrict__ tokens, const AggSeqs q, int D) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= (long)Cb * n_ctx) return;
-    const int c = (int)(row / n_ctx), t = (int)(row - (long)c * n_ctx);
-    const long src = min(ragged_start(offsets, base, c, n_ctx, M) + t, (long)M - 1);
+    if (row >= (long)q.nseq * q.n_ctx) return;
+    const int c = (int)(row / q.n_ctx), t = (int)(row - (long)c * q.n_ctx);
+    long src = q.start<TABLE>(c) + t;
+    if (TABLE) src = min(src, (long)q.M - 1);
     for (int k = lane * 4; k < D; k += 256)
         *(float4_t*)(tokens + row * D + k) = *(const float4_t*)(x + src * D + k);
 }
@@ -448,28 +417,19 @@ int launch_unpack_rows(const half_t* gathered, int rows, int C, int D, int n_ctx
     hipLaunchKernelGGL(unpack_rows_kernel, dim3(rows), dim3(256), 0, s, gathered, C, D, n_ctx, mm, v, t, tokens, seen);
     return (int)hipGetLastError();
 }
-int launch_agg_input(const float* cls_token, const half_t* feats, float* x, int Cb, int S, int n_ctx, int D, hipStream_t s) {
-    const long rows = (long)Cb * (S + n_ctx);
-    if (rows <= 0) return 0;
-    hipLaunchKernelGGL(agg_input_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, cls_token, feats, x, Cb, S, n_ctx, D);
+int launch_agg_input(const float* cls_token, const half_t* feats, int R, float* x, const AggSeqs& q, int D, hipStream_t s) {
+    if (q.nseq <= 0 || q.M <= 0 || R <= 0) return 0;
+    const dim3 grid((unsigned)(((long)q.M + 3) / 4));
+    if (q.offsets) hipLaunchKernelGGL(agg_input_kernel<true>, grid, dim3(256), 0, s, cls_token, feats, R, x, q, D);
+    else hipLaunchKernelGGL(agg_input_kernel<false>, grid, dim3(256), 0, s, cls_token, feats, R, x, q, D);
     return (int)hipGetLastError();
 }
-int launch_agg_output(const float* x, float* tokens, int Cb, int La, int n_ctx, int D, hipStream_t s) {
-    const long rows = (long)Cb * n_ctx;
-    if (rows <= 0) return 0;
-    hipLaunchKernelGGL(agg_output_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, tokens, Cb, La, n_ctx, D);
-    return (int)hipGetLastError();
-}
-int launch_agg_input_ragged(const float* cls_token, const half_t* feats, const int* offsets, int base, float* x, int Cb, int M, int R,
-                            int n_ctx, int D, hipStream_t s) {
-    if (Cb <= 0 || M <= 0 || R <= 0) return 0;
-    hipLaunchKernelGGL(agg_input_ragged, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, cls_token, feats, offsets, base, x, Cb, M, R, n_ctx, D);
-    return (int)hipGetLastError();
-}
-int launch_agg_output_ragged(const float* x, const int* offsets, int base, float* tokens, int Cb, int M, int n_ctx, int D, hipStream_t s) {
-    const long rows = (long)Cb * n_ctx;
-    if (rows <= 0 || M <= 0) return 0;
-    hipLaunchKernelGGL(agg_output_ragged, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, offsets, base, tokens, Cb, M, n_ctx, D);
+int launch_agg_output(const float* x, float* tokens, const AggSeqs& q, int D, hipStream_t s) {
+    const long rows = (long)q.nseq * q.n_ctx;
+    if (rows <= 0 || q.M <= 0) return 0;
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (q.offsets) hipLaunchKernelGGL(agg_output_kernel<true>, grid, dim3(256), 0, s, x, tokens, q, D);
+    else hipLaunchKernelGGL(agg_output_kernel<false>, grid, dim3(256), 0, s, x, tokens, q, D);
     return (int)hipGetLastError();
 }
 int launch_assemble_prompts(const half_t* base, const int64_t* labels, const float* tokens, half_t* out,

@@ -574,40 +574,26 @@ class CustomCLIP(_TwoInFlight):
         self._text_streamed = streamed_text
         self._text_rows = torch.zeros((C, D), **f16) if streamed_text else self.zero_shot_classifier
 
-    def _generate_local(self, eval_set_loader: Iterable, rank: int = 0, world: int = 1) -> torch.Tensor:
-        """Hot loop A (:227-255) over the batches of `eval_set_loader` that belong to `rank` of `world`: exemplar features,
-        visual tokens, multimodal / vision (and streamed text) classifier rows written at their class labels into the buffers
-        of _reset_generation_state.  Returns the class labels this call produced, in order."""
-        e, pl, dev = self.engine, self.prompt_learner, self.device
-        S = self.test_num_ins
-        streamed_text, text_clf = self._text_streamed, self._text_rows
-        local_labels = []
+    def _exemplar_batches(self, eval_set_loader: Iterable, rank: int = 0, world: int = 1, gathered: bool = True):
+        """The walk over an eval-set loader (:227-247): for every batch that belongs to `rank` of `world` its exemplar features are
+        encoded and stored, and (feats, exemplar_label, shots) is handed out -- uniform mode: feats [num_cls, S, D], also written to
+        eval_feat4cls[exemplar_label], shots None; ragged mode (_RaggedRows): feats the packed [R, D] rows, shots a host list.  The
+        attributes of ragged mode are set when the walk ends.  gathered: the caller all-gathers per-batch blocks (forward_prompt)."""
+        e, dev, S = self.engine, self.device, self.test_num_ins
         presharded = bool(getattr(eval_set_loader, "presharded", False))
         cpb = max(1, self.cfg.DATALOADER.TEST.BATCH_SIZE // S)
         ragged = _RaggedRows(self, eval_set_loader, world)
         for batch_idx, batch in enumerate(eval_set_loader):
-            if ragged.takes(batch, batch_idx):                                      # every class uses exactly the images it has
-                if not presharded and batch_idx % world != rank:
-                    continue
-                feats, exemplar_label, shots = ragged.encode(batch)
-                mm_p, mm_l, v_p, v_l, tokens = pl(feats, exemplar_label, pl.eos_index[exemplar_label], shots=shots)
-                if streamed_text:
-                    mm, v, t = self.get_mm_v_feats(mm_p, mm_l, v_p, v_l, self.tokenized_prompts[exemplar_label])
-                    text_clf[exemplar_label] = t
-                else:
-                    mm, v = self.get_mm_v_feats(mm_p, mm_l, v_p, v_l)
-                self.mm_classifier[exemplar_label] = mm
-                self.visual_classifer[exemplar_label] = v
-                self.inference_text_initialized.index_fill_(0, exemplar_label, 1)
-                self.visual_tokens[exemplar_label] = tokens.half()
-                local_labels.append(exemplar_label)
-                continue
-            if world > 1 and not presharded and batch["label"].shape[0] // S > cpb:
+            takes = ragged.takes(batch, batch_idx)                                  # every class uses exactly the images it has
+            if not takes and gathered and world > 1 and not presharded and batch["label"].shape[0] // S > cpb:
                 # every rank iterates over every batch of a round-robin loader, so every rank raises HERE, before any of them
                 # has entered the all-gather whose block size assumes at most `cpb` classes per batch (shard.local_class_bound)
                 raise RuntimeError(f"eval-set batch {batch_idx} holds {batch['label'].shape[0] // S} classes, more than "
                                    f"TEST.BATCH_SIZE // NUM_SHOTS = {cpb}")
             if not presharded and batch_idx % world != rank:
+                continue
+            if takes:
+                yield ragged.encode(batch)
                 continue
             image = self._batch_images(batch, dev)
             label = batch["label"].to(dev, non_blocking=True)
@@ -615,7 +601,18 @@ class CustomCLIP(_TwoInFlight):
             exemplar_label = label.reshape(num_cls, S)[:, 0]                        # :240
             feats = e.encode_image(image, normalize=True).reshape(num_cls, S, -1)   # :243-245
             self.eval_feat4cls[exemplar_label] = feats                              # :247
-            mm_p, mm_l, v_p, v_l, tokens = pl(feats, exemplar_label, pl.eos_index[exemplar_label])   # :248
+            yield feats, exemplar_label, None
+        ragged.finish()
+
+    def _generate_local(self, eval_set_loader: Iterable, rank: int = 0, world: int = 1) -> torch.Tensor:
+        """Hot loop A (:227-255) over the batches of `eval_set_loader` that belong to `rank` of `world`: exemplar features,
+        visual tokens, multimodal / vision (and streamed text) classifier rows written at their class labels into the buffers
+        of _reset_generation_state.  Returns the class labels this call produced, in order."""
+        pl = self.prompt_learner
+        streamed_text, text_clf = self._text_streamed, self._text_rows
+        local_labels = []
+        for feats, exemplar_label, shots in self._exemplar_batches(eval_set_loader, rank, world):
+            mm_p, mm_l, v_p, v_l, tokens = pl(feats, exemplar_label, pl.eos_index[exemplar_label], shots=shots)   # :248
             if streamed_text:                                                       # :249 + the batch's own zero-shot rows (:118-126), one tower pass
                 mm, v, t = self.get_mm_v_feats(mm_p, mm_l, v_p, v_l, self.tokenized_prompts[exemplar_label])
                 text_clf[exemplar_label] = t
@@ -627,8 +624,7 @@ class CustomCLIP(_TwoInFlight):
                                                                                     #  a synchronisation in the middle of the head)
             self.visual_tokens[exemplar_label] = tokens.half()                      # :255
             local_labels.append(exemplar_label)
-        ragged.finish()
-        return torch.cat(local_labels) if local_labels else torch.zeros(0, dtype=torch.long, device=dev)
+        return torch.cat(local_labels) if local_labels else torch.zeros(0, dtype=torch.long, device=self.device)
 
     @torch.no_grad()
     def forward_prompt(self, eval_set_loader: Iterable, wait_files: bool = True):
@@ -816,22 +812,8 @@ class CustomCLIP(_TwoInFlight):
         rank, world = (dist.get_rank(), dist.get_world_size()) if dist else (0, 1)
         self.eval_feat4cls = torch.zeros((C, S, D), dtype=torch.float16, device=dev)
         self.eval_row_labels = self._ragged_n_label = None
-        presharded = bool(getattr(eval_set_loader, "presharded", False))
-        local_labels = []
-        ragged = _RaggedRows(self, eval_set_loader, world)
-        for batch_idx, batch in enumerate(eval_set_loader):
-            if ragged.takes(batch, batch_idx):
-                if presharded or batch_idx % world == rank:
-                    local_labels.append(ragged.encode(batch)[1])
-                continue
-            if not presharded and batch_idx % world != rank:
-                continue
-            image = self._batch_images(batch, dev)
-            label = batch["label"].to(dev, non_blocking=True)
-            exemplar_label = label.reshape(image.shape[0] // S, S)[:, 0]              # :261
-            self.eval_feat4cls[exemplar_label] = e.encode_image(image, normalize=True).reshape(-1, S, D)   # :263-267
-            local_labels.append(exemplar_label)
-        ragged.finish()
+        # (no all-gather of per-batch blocks here, so nothing bounds the classes of a round-robin batch)
+        local_labels = [label for _, label, _ in self._exemplar_batches(eval_set_loader, rank, world, gathered=False)]   # :261-267
         local = torch.cat(local_labels) if local_labels else torch.zeros(0, dtype=torch.long, device=dev)
         clfs = [c.to(device=dev, dtype=torch.float16).contiguous() for c in (mm_classifier, v_classifier, t_classifier)]
         self.fusion_weight = self._xval_fusion_weight(local, *clfs, 10.0)

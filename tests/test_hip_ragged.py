@@ -1,7 +1,9 @@
 """Ragged exemplar sets on the HIP path: every class uses exactly the images it has (ovmr_generate_tokens_ragged, PromptLearner.forward
 with shots=, CustomCLIP.forward_prompt on a loader whose batches carry "shots").  The contract (include/ovmr_hip.h): per class, the
 visual tokens are bit-identical to the uniform entry point run on that class alone with S = shots[c]; the reference's arithmetic is
-its own PromptLearner.forward at num_ins = shots[c] (trainers/mm_classifier_one_prompt.py:167-169).  Needs an MI355X: `pytest -m gpu`.
+its own PromptLearner.forward at num_ins = shots[c] (trainers/mm_classifier_one_prompt.py:167-169).  Both entry points end in one
+generator over one sequence table (AggSeqs, csrc/common.h): the uniform call is the table's arithmetic mode, and its chunks come from
+the same planner.  Needs an MI355X: `pytest -m gpu`.
 """
 import numpy as np
 import pytest
@@ -80,6 +82,31 @@ def test_ragged_chunks_do_not_change_a_bit(small_case):
     e3 = _engine("small", reserve=(64, 64, 3))
     got = e3.generate_tokens_ragged(feats, SHOTS)
     assert torch.equal(got.view(torch.int32), tokens.view(torch.int32))
+
+
+@pytest.fixture(scope="module")
+def one_class_engine():
+    """finalize(max_classes = 1): the aggregator's workspace holds 1 * (2 + 32) = 34 rows."""
+    return _engine("small", reserve=(64, 64, 1))
+
+
+@pytest.mark.parametrize("Cb,S", [(7, 3), (3, 32)])
+def test_uniform_chunks_do_not_change_a_bit(O, small_case, one_class_engine, Cb, S):
+    """The uniform call through the shared chunk planner, 34 aggregator rows: 7 classes x 3 shots run as 6 + 1 classes (floor(34 / 5)
+    per chunk), 3 classes x 32 shots one class per chunk (n_ctx + shots = the capacity).  Bit-equal to the default engine's one chunk;
+    class 0 against the reference's aggregator within the tolerances of test_ragged_tokens_vs_oracle."""
+    spec = synth.SPECS["small"]
+    feats = _feats(spec, [S] * Cb, 200 + S).cuda().view(Cb, S, -1)
+    got = one_class_engine.generate_tokens(feats)
+    one_chunk = small_case[0].generate_tokens(feats)
+    torch.cuda.synchronize()
+    assert got.shape == (Cb, 2, spec.embed_dim)
+    assert torch.equal(got.view(torch.int32), one_chunk.view(torch.int32))
+    pl = {k: torch.from_numpy(v) for k, v in synth.prompt_learner_state_dict(spec, 2, SEED, True).items()}
+    with torch.no_grad():
+        x = torch.cat([pl["cls_token"], feats[0].float().cpu()], dim=0).unsqueeze(0)
+        ref = O.transformer(x, pl, "aggregator.resblocks.", spec.embed_dim // 64, None)[:, :2]
+    np.testing.assert_allclose(got[0].cpu().numpy(), ref[0].numpy(), atol=5e-4, rtol=1e-3)
 
 
 @pytest.mark.parametrize("S", [1, 16, 33])

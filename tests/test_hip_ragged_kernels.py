@@ -1,7 +1,7 @@
-"""attn_f32_varlen (ovmr_amd/csrc/attention.hip) through ovmr_debug_attention_f32_varlen: fp32 attention over sequences of different
-lengths packed row after row, as ovmr_generate_tokens_ragged runs the aggregator.  Per sequence the result must be, bit for bit, what
-attn_f32_small gives on that sequence alone (both kernels run a query row through attn::f32_row), and must not depend on what else is
-in the launch.  Needs an MI355X: run with `pytest -m gpu`.
+"""attn_f32_small (ovmr_amd/csrc/attention.hip) in its table mode through ovmr_debug_attention_f32_varlen: fp32 attention over sequences
+of different lengths packed row after row, as ovmr_generate_tokens_ragged runs the aggregator.  Per sequence the result must be, bit
+for bit, what the kernel's uniform mode (ovmr_debug_attention, f32 = 1: the same body, the starts computed instead of loaded) gives on
+that sequence alone, and must not depend on what else is in the launch.  Needs an MI355X: run with `pytest -m gpu`.
 """
 import pytest
 import torch
@@ -53,7 +53,7 @@ def _run(lib, qd, offsets, nseq, n_ctx, max_len, H):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_varlen_attention(lib, case):
-    """1. bit-equal, sequence by sequence, to attn_f32_small on that sequence alone (B = 1, L = len); 2. within the tolerances of
+    """1. bit-equal, sequence by sequence, to the uniform mode on that sequence alone (B = 1, L = len); 2. within the tolerances of
     test_attention_f32_up_to_its_limit of the fp64 statement; 3. the sentinel rows behind M untouched; 4. isolation: with every row of
     every OTHER sequence NaN, a sequence's output keeps its bits; and the launch's max_len (the LDS size) does not change a bit either."""
     H, lens, n_ctx = CASES[case]
@@ -67,7 +67,7 @@ def test_varlen_attention(lib, case):
         assert lib.ovmr_debug_attention(1, 0, _p(seq), _p(alone), 1, n, H, 0, _s()) == 0
         torch.cuda.synchronize()
         mine = got[row0[b]:row0[b + 1]]
-        assert torch.equal(mine.view(torch.int32), alone.view(torch.int32)), f"sequence {b} (length {n}) != attn_f32_small alone"
+        assert torch.equal(mine.view(torch.int32), alone.view(torch.int32)), f"sequence {b} (length {n}) != the uniform mode alone"
         ref = _ref_attention(qkv[row0[b]:row0[b + 1]], 1, n, H, 0)
         torch.testing.assert_close(mine.cpu(), ref, atol=2e-5, rtol=1e-4)
     if max(lens) < 128:                                            # 64 KiB of LDS per workgroup: the same bits
@@ -95,6 +95,27 @@ def test_varlen_many_short_sequences(lib):
         assert lib.ovmr_debug_attention(1, 0, _p(seq), _p(alone), 1, n, H, 0, _s()) == 0
         torch.cuda.synchronize()
         assert torch.equal(got[row0[b]:row0[b + 1]].view(torch.int32), alone.view(torch.int32)), f"sequence {b} (length {n})"
+
+
+@pytest.mark.parametrize("L", [1, 64, 65, 128])
+def test_both_modes_on_equal_sequences(lib, L):
+    """Three sequences of L rows, two heads, through both modes of the kernel: the uniform launch (B = 3) and the table launch on three
+    equal lengths (n_ctx = 0) agree bit for bit, both are within the file's tolerances of the fp64 statement, and neither writes
+    behind the M = 3 L rows."""
+    H, B = 2, 3
+    qkv, _, offsets = _inputs(H, [L] * B, 0, seed=300 + L)
+    qd = qkv.cuda()
+    table = _run(lib, qd, offsets, B, 0, L, H)
+    out = torch.empty(B * L + PAD_ROWS, H * 64, device="cuda")
+    out.view(torch.int32).fill_(SENTINEL)
+    assert lib.ovmr_debug_attention(1, 0, _p(qd), _p(out), B, L, H, 0, _s()) == 0
+    torch.cuda.synchronize()
+    assert bool((out[B * L:].view(torch.int32) == SENTINEL).all()), "the uniform mode wrote behind the last row"
+    uniform = out[:B * L]
+    assert torch.equal(table.view(torch.int32), uniform.view(torch.int32)), "the two modes differ on equal sequences"
+    ref = _ref_attention(qkv, B, L, H, 0)
+    torch.testing.assert_close(uniform.cpu(), ref, atol=2e-5, rtol=1e-4)
+    torch.testing.assert_close(table.cpu(), ref, atol=2e-5, rtol=1e-4)
 
 
 def test_varlen_refuses_more_than_128_rows(lib):
