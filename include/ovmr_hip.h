@@ -363,6 +363,22 @@ int ovmr_debug_layernorm(int f32, const void* x, void* y, const float* g, const 
                          long in_stride, ovmr_stream stream);
 int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B, int L, int H, int causal,
                          ovmr_stream stream);
+/* The row kernels either side of the GEMMs, one launcher each (tests/rowops_exact.py states what each must give, bit for bit).
+ * OVMR_E_ARG for a NULL pointer, a negative count or a width the kernel's 8-byte accesses do not take (D % 4 != 0).
+ *   l2norm          x [rows, D] fp16, in place, x / h(||x||), applied `times` times (what normalize = 1 / 2 of the encoders runs)
+ *   text_ensemble   feats [T, rows, E] fp16 -> out [rows, E] fp16 (csrc/text_ensemble.hip); the pointers go to the launcher as they
+ *                   are: 16-byte aligned operands with E % 8 == 0 and E <= 1024 take the vector kernels, anything else (an `out`
+ *                   that is only 2-byte aligned, for one) the element-wise kernel
+ *   text_embed_ids  x[n * Lseq + l] = h(h(tok_emb[ids[n * ids_stride + l]]) + pos[l]) for l < Lseq, index[n] = the first maximum of
+ *                   ids[n * ids_stride + 0 .. Lctx); tok_emb fp32 [vocab, D], pos fp16 [>= Lseq, D], Lseq <= Lctx <= ids_stride
+ *   text_add_pos    x[n * Lseq + l] = h(prompts[n * Lctx + l] + pos[l]) for l < Lseq
+ *   gather_rows     out[n] = x[n * Lseq + clamp(index[n], 0, Lseq - 1)] */
+int ovmr_debug_l2norm(void* x_f16, int rows, int D, int times, ovmr_stream stream);
+int ovmr_debug_text_ensemble(const void* feats_f16, int T, int rows, int E, void* out_f16, ovmr_stream stream);
+int ovmr_debug_text_embed_ids(const int64_t* ids, int ids_stride, const float* tok_emb, const void* pos_f16, void* x_f16, int32_t* index,
+                              int N, int Lctx, int Lseq, int D, ovmr_stream stream);
+int ovmr_debug_text_add_pos(const void* prompts_f16, int Lctx, const void* pos_f16, void* x_f16, int N, int Lseq, int D, ovmr_stream stream);
+int ovmr_debug_gather_rows(const void* x_f16, const int32_t* index, void* out_f16, int N, int Lseq, int D, ovmr_stream stream);
 /* ovmr_debug_gemm (fp16 kernels) with explicit strides: A [M, lda], W [N, ldw], res [M, ldres], C [M, ldc] -- the sub-matrix
  * launches of the last vision block (CLS-row Q with A strided by a sequence, K/V written next to Q, out_proj reading the residual
  * of the CLS rows from the token rows).  For epi 6/7, W [N,K] and bias fp16 [N] are the RAW weight and bias: they are folded with

@@ -1187,6 +1187,36 @@ int ovmr_debug_layernorm(int f32, const void* x, void* y, const float* g, const 
     return launch_layernorm(x, y, g, b, rows, D, in_stride, f32, (hipStream_t)stream);
 }
 
+// The row kernels either side of the GEMMs (tests/test_hip_rowops_exact.py): argument checks and the launch, nothing else.
+int ovmr_debug_l2norm(void* x_f16, int rows, int D, int times, ovmr_stream stream) {
+    if (!x_f16 || rows < 0 || D < 4 || (D & 3) || times < 0) return OVMR_E_ARG;
+    int rc = 0;
+    for (int i = 0; i < times && !rc; ++i) rc = launch_l2norm_f16((half_t*)x_f16, rows, D, (hipStream_t)stream);
+    return rc;
+}
+
+int ovmr_debug_text_ensemble(const void* feats_f16, int T, int rows, int E, void* out_f16, ovmr_stream stream) {
+    if (!feats_f16 || !out_f16 || T < 1 || rows < 0 || E < 1 || ((uintptr_t)feats_f16 & 1) || ((uintptr_t)out_f16 & 1)) return OVMR_E_ARG;
+    return launch_text_ensemble((const half_t*)feats_f16, T, rows, E, (half_t*)out_f16, (hipStream_t)stream);
+}
+
+int ovmr_debug_text_embed_ids(const int64_t* ids, int ids_stride, const float* tok_emb, const void* pos_f16, void* x_f16, int32_t* index,
+                              int N, int Lctx, int Lseq, int D, ovmr_stream stream) {
+    if (!ids || !tok_emb || !pos_f16 || !x_f16 || !index || N < 0 || Lseq < 1 || Lseq > Lctx || ids_stride < Lctx || D < 4 || (D & 3))
+        return OVMR_E_ARG;
+    return launch_text_embed_ids(ids, ids_stride, tok_emb, (const half_t*)pos_f16, (half_t*)x_f16, index, N, Lctx, Lseq, D, (hipStream_t)stream);
+}
+
+int ovmr_debug_text_add_pos(const void* prompts_f16, int Lctx, const void* pos_f16, void* x_f16, int N, int Lseq, int D, ovmr_stream stream) {
+    if (!prompts_f16 || !pos_f16 || !x_f16 || N < 0 || Lseq < 1 || Lseq > Lctx || D < 4 || (D & 3)) return OVMR_E_ARG;
+    return launch_text_add_pos((const half_t*)prompts_f16, Lctx, (const half_t*)pos_f16, (half_t*)x_f16, N, Lseq, D, (hipStream_t)stream);
+}
+
+int ovmr_debug_gather_rows(const void* x_f16, const int32_t* index, void* out_f16, int N, int Lseq, int D, ovmr_stream stream) {
+    if (!x_f16 || !index || !out_f16 || N < 0 || Lseq < 1 || D < 4 || (D & 3)) return OVMR_E_ARG;
+    return launch_gather_rows_f16((const half_t*)x_f16, index, (half_t*)out_f16, N, Lseq, D, (hipStream_t)stream);
+}
+
 int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B, int L, int H, int causal,
                          ovmr_stream stream) {
     // fp32: B equal sequences are the arithmetic mode of the aggregator's sequence table

@@ -52,6 +52,9 @@ __global__ void fill_cls_kernel(half_t* __restrict__ x, const half_t* __restrict
 
 // x / x.norm(dim=-1, keepdim=True) on an fp16 tensor: the norm is accumulated in fp32, rounded to
 // fp16, and the quotient is rounded to fp16 (trainers/mm_classifier_one_prompt.py:204,244,307).
+// Two rows leave torch's arithmetic: an all-zero row stays all zero (the norm is clamped to 1e-12 before the division; torch divides
+// 0 by 0 and gives NaN), and a row whose norm overflows fp16 (sum of squares >= 65520^2) divides by +inf: signed zeros, as in torch.
+// D % 4 == 0 (8-byte accesses).  tests/rowops_exact.py holds every element to these roundings.
 __global__ __launch_bounds__(256) void l2norm_f16_kernel(half_t* __restrict__ x, int rows, int D) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);

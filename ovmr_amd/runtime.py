@@ -85,6 +85,11 @@ SIGNATURES = {
     "ovmr_debug_lnfold": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
     "ovmr_debug_layernorm": (c_i, [c_i, c_p, c_p, c_p, c_p, c_i, c_i, ctypes.c_long, c_p]),
     "ovmr_debug_attention": (c_i, [c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    "ovmr_debug_l2norm": (c_i, [c_p, c_i, c_i, c_i, c_p]),
+    "ovmr_debug_text_ensemble": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p]),
+    "ovmr_debug_text_embed_ids": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    "ovmr_debug_text_add_pos": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "ovmr_debug_gather_rows": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
     "ovmr_debug_gemm_strided": (c_i, [c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_p, c_p,
                                       c_i, c_p]),
     "ovmr_debug_attention_f32_varlen": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
