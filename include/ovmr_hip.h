@@ -379,6 +379,19 @@ int ovmr_debug_text_embed_ids(const int64_t* ids, int ids_stride, const float* t
                               int N, int Lctx, int Lseq, int D, ovmr_stream stream);
 int ovmr_debug_text_add_pos(const void* prompts_f16, int Lctx, const void* pos_f16, void* x_f16, int N, int Lseq, int D, ovmr_stream stream);
 int ovmr_debug_gather_rows(const void* x_f16, const int32_t* index, void* out_f16, int N, int Lseq, int D, ovmr_stream stream);
+/* The front of the image tower (tests/front_exact.py states what each must give, bit for bit).  OVMR_E_ARG for a NULL pointer, a
+ * negative count or a shape the kernel's accesses do not take.
+ *   im2col        image [B, 3, R, R] (fp16 or fp32, any element alignment) -> out [B * (R/P)^2, Kpad] fp16: row (b, gy, gx), column
+ *                 k = c * P * P + ky * P + kx, +0 from 3 * P * P on; Kpad % 8 == 0, R % P == 0, out 16-byte aligned
+ *   fill_cls      x [B * L, W] fp16: row b * L = cls_pos [W], every other row untouched; W % 4 == 0
+ *   gemm_patches  the patch-embedding GEMM gathering its rows from the fp16 images (16 x 16 patches, G = R / 16, K = 768):
+ *                 C [B * (G*G + 1), N], row b * (G*G + 1) + 1 + p = h(h(patch p of image b . W [N, 768]) + pos [G*G + 1, N] row 1 + p),
+ *                 the rows b * (G*G + 1) untouched.  Returns the launcher's rc: -2 for R % 16 != 0 or an image pointer that is not
+ *                 16-byte aligned, -4 for B * G*G < 256, N < 128 or images of 2^31 bytes or more (the 256-row kernel alone gathers). */
+int ovmr_debug_im2col(const void* image, int image_dtype, int B, int R, int P, int Kpad, void* out_f16, ovmr_stream stream);
+int ovmr_debug_fill_cls(void* x_f16, const void* cls_pos_f16, int B, int L, int W, ovmr_stream stream);
+int ovmr_debug_gemm_patches(int variant, const void* image_f16, int R, const void* W_f16, const void* pos_f16, void* C_f16, int B, int N,
+                            ovmr_stream stream);
 /* ovmr_debug_gemm (fp16 kernels) with explicit strides: A [M, lda], W [N, ldw], res [M, ldres], C [M, ldc] -- the sub-matrix
  * launches of the last vision block (CLS-row Q with A strided by a sequence, K/V written next to Q, out_proj reading the residual
  * of the CLS rows from the token rows).  For epi 6/7, W [N,K] and bias fp16 [N] are the RAW weight and bias: they are folded with

@@ -216,10 +216,13 @@ GemmPlan gemm_f16_route(const GemmArgs& a, int variant) {
                        (argmax ? a.argmax_out != nullptr
                                : !(a.N & 7) && !(a.ldc & 7) && aligned16(a.C) && (!res || (!(a.ldres & 7) && aligned16(a.res))));
     if ((tile_only || variant >= 1) && takes) {
-        if (a.im2col_R) {                                  // A = fp16 images [B, 3, R, R], 16 x 16 patches: K = 768, byte offsets in 32 bits
+        // A = fp16 images [B, 3, R, R], 16 x 16 patches: K = 768.  The images' bytes stay below 2^31 like every other operand's: an
+        // image is rows_in * 768 * 2 bytes, so for whole images `takes` (M * lda * 2 with lda = 768) holds that already and a higher
+        // bound here never admitted anything; this one counts a last, partly used image whole.
+        if (a.im2col_R) {
             const int G = a.im2col_R >> 4;
             if (a.epi != EPI_PATCH || a.K != 768 || (a.im2col_R & 15) || a.rows_in != G * G || !aligned16(a.A) ||
-                (long)((a.M + a.rows_in - 1) / a.rows_in) * 3 * a.im2col_R * a.im2col_R * 2 >= 0xffffffffL)
+                (long)((a.M + a.rows_in - 1) / a.rows_in) * 3 * a.im2col_R * a.im2col_R * 2 >= 0x7fffffffL)
                 return none(-2);
         }
         if (lnf && ((a.N & 63) || !a.ln_stats || a.ln_slots < 1 || !a.ln_g || !a.ln_b)) return none(-2);

@@ -238,6 +238,14 @@ GemmArgs gemm_stats(GemmArgs a, float* stats) {
     a.stats_out = stats;
     return a;
 }
+// The patch-embedding GEMM that gathers its rows from the fp16 images [B, 3, R, R] itself (gemm_f16_v5.hip, a.im2col_R): 16 x 16
+// patches, K = 768, G * G = (R / 16)^2 patch rows per image written behind the image's CLS row.  x [B * (G * G + 1), W].
+GemmArgs gemm_patches(const void* image, int R, const void* conv_w, const void* pos, void* x, int B, int W) {
+    const int G2 = (R >> 4) * (R >> 4);
+    GemmArgs a = gemm(image, 768, conv_w, 768, x, W, B * G2, W, 768, EPI_PATCH);
+    a.im2col_R = R; a.pos = pos; a.rows_in = G2; a.rows_out = G2 + 1;
+    return a;
+}
 
 // Scratch of the two LayerNorm-fold hooks, allocated per call: the statistics of `rows` rows and the folded form of a raw [N, K]
 // weight (rc: allocation or fold failure).  Leaving the hook waits for the stream and frees it.
@@ -740,13 +748,14 @@ int ovmr_encode_image(ovmr_handle* h, const void* image, int image_dtype, int B,
         // otherwise (fp32 images, other patch sizes, a handful of rows, the 128 x 128 kernel) an im2col pass writes them out first
         const bool fused_patches = h->fuse_im2col && image_dtype == OVMR_F16 && d.vision_patch_size == 16 && h->Kpad == 768 && (R & 15) == 0 &&
                                    Bc * G2 >= 256 && W >= 128 && h->gemm_variant >= 1 && ((uintptr_t)image & 15) == 0;
-        GemmArgs pe = gemm(col, h->Kpad, h->conv_w, h->Kpad, x, W, Bc * G2, W, h->Kpad, EPI_PATCH);
+        GemmArgs pe;
         if (fused_patches) {
-            pe.A = (const char*)image + (size_t)b0 * px;
-            pe.im2col_R = R;
-        } else
+            pe = gemm_patches((const char*)image + (size_t)b0 * px, R, h->conv_w, h->pos16_vis, x, Bc, W);
+        } else {
             CK(launch_im2col((const char*)image + (size_t)b0 * px, image_dtype == OVMR_F32, col, Bc, R, d.vision_patch_size, h->Kpad, s));
-        pe.pos = h->pos16_vis; pe.rows_in = G2; pe.rows_out = L;
+            pe = gemm(col, h->Kpad, h->conv_w, h->Kpad, x, W, Bc * G2, W, h->Kpad, EPI_PATCH);
+            pe.pos = h->pos16_vis; pe.rows_in = G2; pe.rows_out = L;
+        }
         CK(launch_gemm_f16(pe, h->gemm_variant, s));
         CK(launch_fill_cls(x, h->cls_pos16, Bc, L, W, s));
         CK(launch_layernorm(x, x, h->ln_pre_g, h->ln_pre_b, M, W, W, 0, s));
@@ -1215,6 +1224,29 @@ int ovmr_debug_text_add_pos(const void* prompts_f16, int Lctx, const void* pos_f
 int ovmr_debug_gather_rows(const void* x_f16, const int32_t* index, void* out_f16, int N, int Lseq, int D, ovmr_stream stream) {
     if (!x_f16 || !index || !out_f16 || N < 0 || Lseq < 1 || D < 4 || (D & 3)) return OVMR_E_ARG;
     return launch_gather_rows_f16((const half_t*)x_f16, index, (half_t*)out_f16, N, Lseq, D, (hipStream_t)stream);
+}
+
+// The front of the image tower (tests/test_hip_front_exact.py): argument checks and the launch, nothing else.
+int ovmr_debug_im2col(const void* image, int image_dtype, int B, int R, int P, int Kpad, void* out_f16, ovmr_stream stream) {
+    if (!image || !out_f16 || (image_dtype != OVMR_F16 && image_dtype != OVMR_F32) || B < 0 || R < 1 || P < 1 || R % P || Kpad < 3 * P * P ||
+        (Kpad & 7) || ((uintptr_t)out_f16 & 15))
+        return OVMR_E_ARG;
+    return launch_im2col(image, image_dtype == OVMR_F32, (half_t*)out_f16, B, R, P, Kpad, (hipStream_t)stream);
+}
+
+int ovmr_debug_fill_cls(void* x_f16, const void* cls_pos_f16, int B, int L, int W, ovmr_stream stream) {
+    if (!x_f16 || !cls_pos_f16 || B < 0 || L < 1 || W < 4 || (W & 3) || ((uintptr_t)x_f16 & 7) || ((uintptr_t)cls_pos_f16 & 7)) return OVMR_E_ARG;
+    if (B == 0) return 0;
+    return launch_fill_cls((half_t*)x_f16, (const half_t*)cls_pos_f16, B, L, W, (hipStream_t)stream);
+}
+
+// The fused launch of ovmr_encode_image: the same GemmArgs (gemm_patches) into the same launcher, whose rc comes back.  What the
+// launcher refuses (gemm_f16_route): -2 for R % 16 != 0 or an image pointer that is not 16-byte aligned -- the LDS-DMA reads 16-byte
+// chunks, so such a launch never starts; -4 for fewer than 256 patch rows, N < 128 or images of 2^31 bytes or more.
+int ovmr_debug_gemm_patches(int variant, const void* image_f16, int R, const void* W_f16, const void* pos_f16, void* C_f16, int B, int N,
+                            ovmr_stream stream) {
+    if (!image_f16 || !W_f16 || !pos_f16 || !C_f16 || B < 0 || N < 0 || R < 0) return OVMR_E_ARG;
+    return launch_gemm_f16(gemm_patches(image_f16, R, W_f16, pos_f16, C_f16, B, N), variant, (hipStream_t)stream);
 }
 
 int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B, int L, int H, int causal,

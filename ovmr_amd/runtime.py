@@ -90,6 +90,9 @@ SIGNATURES = {
     "ovmr_debug_text_embed_ids": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "ovmr_debug_text_add_pos": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_p]),
     "ovmr_debug_gather_rows": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p]),
+    "ovmr_debug_im2col": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
+    "ovmr_debug_fill_cls": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
+    "ovmr_debug_gemm_patches": (c_i, [c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p]),
     "ovmr_debug_gemm_strided": (c_i, [c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_p, c_p,
                                       c_i, c_p]),
     "ovmr_debug_attention_f32_varlen": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),

@@ -64,7 +64,7 @@ def _route_v5(loop, M, N, K, epi, ldc, ldres, stats=False, im2col=0):
         return None
     if im2col:                                                            # rows_in = (R / 16)^2 here
         rows_in = (im2col >> 4) ** 2
-        if epi != EPI_PATCH or K != 768 or (im2col & 15) or (M + rows_in - 1) // rows_in * 3 * im2col * im2col * 2 >= 0xffffffff:
+        if epi != EPI_PATCH or K != 768 or (im2col & 15) or (M + rows_in - 1) // rows_in * 3 * im2col * im2col * 2 >= 0x7fffffff:
             return _err(-2)
     lnf = epi in (EPI_LN_BIAS, EPI_LN_BIAS_QGELU)
     if lnf and (N & 63):

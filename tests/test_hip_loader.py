@@ -77,6 +77,17 @@ def _sizes(n, rng):
     return out[:n]
 
 
+def _content(rng, w, h, i):
+    """Frame i of a test: noise (every weight matters), noise with flat saturated quarters (clip8 at 0 / 255), or a smooth ramp."""
+    a = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    if i % 3 == 1:
+        a[: h // 2, : w // 2] = 255
+        a[h // 2:, w // 2:] = 0
+    elif i % 3 == 2:
+        a = ((np.arange(w)[None, :, None] * 3 + np.arange(h)[:, None, None] * 5 + np.arange(3)[None, None, :] * 40) % 256).astype(np.uint8)
+    return a
+
+
 @pytest.mark.parametrize("R,interpolation,n", [(224, "bicubic", 210), (336, "bicubic", 40), (224, "bilinear", 60), (64, "bicubic", 40)])
 def test_resize_crop_u8_bit_equal_to_pil(R, interpolation, n):
     """ovmr_resize_crop_u8 (PIL's two integer passes on the GPU over host-built tables, ovmr_amd/resize.py) against PIL itself --
@@ -86,15 +97,7 @@ def test_resize_crop_u8_bit_equal_to_pil(R, interpolation, n):
     from PIL import Image
     from ovmr_amd import _decode_worker, loader
     rng = np.random.default_rng(R + len(interpolation) + n)
-    frames = []
-    for i, (w, h) in enumerate(_sizes(n, rng)):
-        a = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-        if i % 3 == 1:
-            a[: h // 2, : w // 2] = 255
-            a[h // 2:, w // 2:] = 0
-        elif i % 3 == 2:
-            a = ((np.arange(w)[None, :, None] * 3 + np.arange(h)[:, None, None] * 5 + np.arange(3)[None, None, :] * 40) % 256).astype(np.uint8)
-        frames.append(a)
+    frames = [_content(rng, w, h, i) for i, (w, h) in enumerate(_sizes(n, rng))]
     want = np.stack([_decode_worker.load_u8(Image.fromarray(a), R, False, interpolation) for a in frames])
     for lo in range(0, n, 64):                                   # several launches, several sizes per launch
         got = loader.resize_crop_u8(frames[lo:lo + 64], R, interpolation).cpu().numpy()
@@ -102,6 +105,44 @@ def test_resize_crop_u8_bit_equal_to_pil(R, interpolation, n):
         for k in range(got.shape[0]):
             h, w = frames[lo + k].shape[:2]
             assert np.array_equal(got[k], want[lo + k]), f"{w} x {h} -> {R} ({interpolation}): {int((got[k] != want[lo + k]).sum())} bytes differ"
+
+
+# (R, interpolation, [(w, h)]): one launch each.  The horizontal pass stages a row segment in 12 KiB of LDS (csrc/resize_crop.hip, RS_SEG):
+# 4090 columns are the last that fit (seg_bytes + 16 = 12286, 768 chunks of 16 bytes fill the segment exactly), from 4091 on the rows are
+# read from global memory directly.  (xlo, columns, ksize_h, ksize_v) of the wide frame, from resize.plan, asserted below.
+WIDE = [
+    (224, "bicubic", [(4090, 4090)], (0, 4090, 75, 75)),                               # the last staged frame
+    (224, "bicubic", [(4091, 4091), (500, 375), (37, 100)], (0, 4091, 75, 75)),        # the first direct one, in front of staged frames
+    (224, "bicubic", [(4091, 4100)], (0, 4091, 75, 75)),                               # portrait: the window is the whole width
+    (224, "bicubic", [(375, 500), (223, 225), (6000, 4091)], (924, 4152, 75, 75)),     # landscape, xlo > 0; behind staged frames: the last frame
+                                                                                       # of the arena (frame_end), the grid sized by its ny
+    (224, "bilinear", [(4091, 4091)], (0, 4091, 39, 39)),
+    (64, "bicubic", [(4100, 4091)], (0, 4100, 259, 257)),                              # 64-fold reduction: 259 taps a column
+]
+
+
+@pytest.mark.parametrize("R,interpolation,sizes,plan", WIDE, ids=[f"{r}-{i}-" + "+".join(f"{w}x{h}" for w, h in s) for r, i, s, _ in WIDE])
+def test_resize_crop_u8_wide_frames_bit_equal_to_pil(R, interpolation, sizes, plan):
+    """Frames around the width at which resize_h_kernel leaves its LDS staging for direct reads, EVERY byte equal to PIL
+    (`_decode_worker.load_u8`), alone and in one launch with small staged frames on either side."""
+    import time
+    from PIL import Image
+    from ovmr_amd import _decode_worker, loader, resize
+    t0 = time.time()
+    w, h = max(sizes)
+    t = resize.plan(w, h, R, interpolation)
+    xlo, xhi = int(t["table"][0]), int(t["table"][2 * (R - 1)] + t["table"][2 * (R - 1) + 1])
+    assert (xlo, xhi - xlo, t["ksize_h"], t["ksize_v"]) == plan
+    assert ((xhi - xlo) * 3 + 16 <= 12 * 1024) == (w == 4090), "staged up to 4090 columns, direct from 4091 on"
+    rng = np.random.default_rng(w * 7 + h + R + len(interpolation))
+    kind = {(4090, 4090): 0, (4091, 4100): 2}                   # noise, a ramp; the other wide frames: noise with saturated quarters
+    frames = [_content(rng, fw, fh, kind.get((fw, fh), 1) if fw > 4000 else i) for i, (fw, fh) in enumerate(sizes)]
+    want = [_decode_worker.load_u8(Image.fromarray(a), R, False, interpolation) for a in frames]
+    got = loader.resize_crop_u8(frames, R, interpolation).cpu().numpy()
+    torch.cuda.synchronize()
+    for k, (fw, fh) in enumerate(sizes):
+        assert np.array_equal(got[k], want[k]), f"{fw} x {fh} -> {R} ({interpolation}): {int((got[k] != want[k]).sum())} bytes differ"
+    print(f"\n{sizes} -> {R} ({interpolation}): {time.time() - t0:.2f} s")
 
 
 def test_pipelined_loader_resizes_on_the_device_and_keeps_its_pool(tmp_path):

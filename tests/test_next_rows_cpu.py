@@ -461,6 +461,12 @@ def test_resize_tables_reproduce_pil_bit_for_bit():
             want = load_u8(Image.fromarray(img), R, False, interp)
             got = resize.resize_crop_reference(img, R, interp)
             assert np.array_equal(want, got), f"{w} x {h} -> {R} ({interp})"
+    # a frame whose row segment is wider than the horizontal pass stages (csrc/resize_crop.hip, RS_SEG = 12 KiB): 4090 columns are the
+    # last staged ones, 4091 the first on the direct path
+    seg = lambda w, h: (lambda t: (int(t[2 * 223]) + int(t[2 * 223 + 1]) - int(t[0])) * 3 + 16)(resize.plan(w, h, 224)["table"])
+    assert seg(4090, 4090) == 12286 and seg(4091, 4091) == 12289
+    img = rng.integers(0, 256, (4091, 4091, 3), dtype=np.uint8)
+    assert np.array_equal(load_u8(Image.fromarray(img), 224, False, "bicubic"), resize.resize_crop_reference(img, 224, "bicubic")), "4091 x 4091 -> 224"
     p = resize.plan(500, 375, 224)
     assert p["ksize_h"] == p["ksize_v"] == 9 and p["y0"] == 0 and p["ny"] == 375 and p["table"].dtype == np.int32
     assert resize.resized_size(500, 375, 224) == (298, 224) and resize.resized_size(375, 500, 224) == (224, 298)
