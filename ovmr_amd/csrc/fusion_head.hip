@@ -235,16 +235,12 @@ int launch_fusion_weights(const int* counts, const int* n_label, int C, float ta
 }
 
 int launch_fused_softmax(const half_t* l0, const half_t* l1, const half_t* l2, const float* w, int n_mod,
-                         float* out, int B, int C, hipStream_t s) {
+                         float* out, long plane_stride, int B, int C, hipStream_t s) {
     if (B <= 0) return 0;
-    hipLaunchKernelGGL(fused_softmax_kernel, dim3(B), dim3(256), 0, s, l0, l1, l2, w, n_mod, out, C);
-    return (int)hipGetLastError();
-}
-
-int launch_fused_softmax_all(const half_t* l0, const half_t* l1, const half_t* l2, const float* w, float* out, long plane_stride,
-                             int B, int C, hipStream_t s) {
-    if (B <= 0) return 0;
-    if (!l0 || !l1 || !l2 || !w || !out || plane_stride < (long)B * C) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(fused_softmax_all_kernel, dim3(B), dim3(256), 0, s, l0, l1, l2, w, out, C, plane_stride);
+    if (plane_stride > 0) {                                   // the all-modes form: four planes of `out`
+        if (!l0 || !l1 || !l2 || !w || !out || n_mod != 3 || plane_stride < (long)B * C) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(fused_softmax_all_kernel, dim3(B), dim3(256), 0, s, l0, l1, l2, w, out, C, plane_stride);
+    } else
+        hipLaunchKernelGGL(fused_softmax_kernel, dim3(B), dim3(256), 0, s, l0, l1, l2, w, n_mod, out, C);
     return (int)hipGetLastError();
 }

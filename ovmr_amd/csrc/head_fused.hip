@@ -33,6 +33,7 @@
 //     softmaxes p_mm, p_v, p_t of a tile when it writes their weighted sum -- the single modes ARE those p_m (:348-363) -- so it stores
 //     them too, into three further planes of the output (plane = OVMR_MODE_* value: fusion, text, vision, multimodal).  Everything
 //     before the stores is the fusion launch's; each plane is bit-equal to what the single-mode launch writes.
+#include "carver.h"
 #include "common.h"
 
 #include <algorithm>
@@ -433,14 +434,23 @@ int launch_one(const half_t* feats, int B, int D, float scale, const half_t* con
 
 size_t head_lds_bytes(int BM, int D) { return (size_t)BM * (D + 8) * 2 + (size_t)4 * 3 * BM * 2 * 4; }
 
+// Workspace of a softmax launch over B rows (padded to 64) and Tc class tiles: the tile pairs, the merged pairs, the recompute queue.
+// The two float arrays are multiples of 64 * 24 = 1536 bytes, hence of the carver's 256: `merged` starts where `partial` ends and the
+// queue where `merged` ends.  Only the queue is rounded up, so the total exceeds the sum of the three by less than 256 bytes.
+struct HeadFusedWs : Carver {
+    float *partial, *merged;
+    int* leftover;
+    HeadFusedWs(char* base, int B, int C) : Carver(base) {
+        const size_t Tc = (C + HF_BN - 1) / HF_BN, rows = (size_t)(B + 63) / 64 * 64;
+        partial = take<float>(3 * rows * Tc * 2);            // [3][rows][Tc][2]
+        merged = take<float>(3 * rows * 2);                  // [3][rows][2]
+        leftover = take<int>(rows / 32 * Tc);
+    }
+};
+
 }  // namespace
 
-// Workspace the launch needs for B rows: floats [3][rows padded to 64][Tc][2] (tile pairs), [3][rows][2] (merged), then ints
-// [rows / 32 x Tc] (the recompute queue).
-size_t head_fused_ws_bytes(int B, int C) {
-    const size_t Tc = (C + HF_BN - 1) / HF_BN, rows = (size_t)(B + 63) / 64 * 64;
-    return 3 * rows * (Tc + 1) * 2 * sizeof(float) + (rows / 32) * Tc * sizeof(int);
-}
+size_t head_fused_ws_bytes(int B, int C) { return HeadFusedWs(nullptr, B, C).bytes(); }
 int head_fused_sync_ints() { return HF_SYNC_INTS; }
 
 // -100: shape not taken (D not a multiple of 64, a feature row that does not fit LDS): the caller runs the five-launch path.
@@ -460,14 +470,11 @@ int launch_head_fused(const half_t* feats, int B, int D, float scale, const half
     if (head_lds_bytes(BM, D) > 160 * 1024) BM = 32;
     if (head_lds_bytes(BM, D) > 160 * 1024) return -100;
     const size_t lds = head_lds_bytes(BM, D);
-    const size_t rows = (size_t)(B + 63) / 64 * 64;
-    float* partial = (float*)ws;
-    float* merged = partial + 3 * rows * Tc * 2;
-    int* leftover = (int*)(merged + 3 * rows * 2);
+    const HeadFusedWs hw((char*)ws, B, C);
     if (raw) return BM == 32 ? launch_one<32, true>(feats, B, D, scale, clf, 1, C, nullptr, nullptr, 0, raw_out, nullptr, nullptr, nullptr, nullptr, Tc, lds, 0, s)
                              : launch_one<64, true>(feats, B, D, scale, clf, 1, C, nullptr, nullptr, 0, raw_out, nullptr, nullptr, nullptr, nullptr, Tc, lds, 0, s);
-    if (all) return BM == 32 ? launch_one<32, false, true>(feats, B, D, scale, clf, 3, C, w, out, plane_stride, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s)
-                             : launch_one<64, false, true>(feats, B, D, scale, clf, 3, C, w, out, plane_stride, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s);
-    return BM == 32 ? launch_one<32, false>(feats, B, D, scale, clf, n_mod, C, w, out, 0, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s)
-                    : launch_one<64, false>(feats, B, D, scale, clf, n_mod, C, w, out, 0, nullptr, partial, merged, leftover, sync, Tc, lds, max_grid, s);
+    if (all) return BM == 32 ? launch_one<32, false, true>(feats, B, D, scale, clf, 3, C, w, out, plane_stride, nullptr, hw.partial, hw.merged, hw.leftover, sync, Tc, lds, max_grid, s)
+                             : launch_one<64, false, true>(feats, B, D, scale, clf, 3, C, w, out, plane_stride, nullptr, hw.partial, hw.merged, hw.leftover, sync, Tc, lds, max_grid, s);
+    return BM == 32 ? launch_one<32, false>(feats, B, D, scale, clf, n_mod, C, w, out, 0, nullptr, hw.partial, hw.merged, hw.leftover, sync, Tc, lds, max_grid, s)
+                    : launch_one<64, false>(feats, B, D, scale, clf, n_mod, C, w, out, 0, nullptr, hw.partial, hw.merged, hw.leftover, sync, Tc, lds, max_grid, s);
 }

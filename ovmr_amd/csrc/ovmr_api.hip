@@ -2,9 +2,11 @@
 // sequences of the OVMR hot path.  No call in the compute entry points allocates, copies to the
 // host or synchronises, so every one of them can be captured into a hipGraph by the caller.
 #include "../../include/ovmr_hip.h"
+#include "carver.h"
 #include "gemm_route.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -13,13 +15,6 @@
 #include <map>
 #include <string>
 #include <vector>
-
-// text_ensemble.hip (declared here, not in common.h: that header's hash stamps the committed counter summaries, build.source_sha16)
-int launch_text_ensemble(const half_t* feats, int T, int rows, int E, half_t* out, hipStream_t s);
-int launch_topk_rows(const void* out, int out_is_f32, long ld, int B, int C, int k, float* values, int32_t* indices, const int64_t* labels,
-                     int* hits, hipStream_t s);   // topk.hip
-int launch_eval_detail(const void* out, int out_is_f32, long ld, const int64_t* labels, int B, int C, int k, int* counts, int* hits,
-                       int* class_hits, int* cmat, hipStream_t s);   // eval_detail.hip
 
 namespace {
 
@@ -64,6 +59,7 @@ struct ovmr_handle {
     std::vector<Block> vis, txt, agg;
     half_t *conv_w = nullptr, *pos16_vis = nullptr, *cls_pos16 = nullptr, *proj_t = nullptr;
     half_t *pos16_txt = nullptr, *textproj_t = nullptr;
+    void *conv1 = nullptr, *cls_emb = nullptr, *pos_vis = nullptr, *proj = nullptr, *pos_txt = nullptr, *textproj = nullptr;   // as set: the sources of those
     float *ln_pre_g = nullptr, *ln_pre_b = nullptr, *ln_post_g = nullptr, *ln_post_b = nullptr;
     float *ln_final_g = nullptr, *ln_final_b = nullptr, *tok_emb = nullptr, *cls_token = nullptr;
     int Kpad = 0, G = 0, L = 0;
@@ -102,17 +98,6 @@ bool ends_with(const std::string& s, const char* suf) {
     return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
 }
 
-// dtype policy of convert_weights() (clip/model.py:852-873); the aggregator is never halved.
-bool stored_as_f32(const std::string& name) {
-    if (name.rfind("prompt_learner.", 0) == 0) return true;
-    if (name.find(".ln_") != std::string::npos || name.rfind("ln_final", 0) == 0) return true;
-    if (name == "visual.class_embedding" || name == "visual.positional_embedding" ||
-        name == "positional_embedding" || name == "token_embedding.weight" || name == "logit_scale")
-        return true;
-    if (name.rfind("visual.ln_", 0) == 0) return true;
-    return false;   // conv1, proj, text_projection, attn.*, mlp.*
-}
-
 // Device allocation registered in `list`: h->owned (until ovmr_destroy) or h->derived (until the next ovmr_finalize)
 void* dev_alloc(std::vector<void*>& list, size_t bytes) {
     void* p = nullptr;
@@ -125,34 +110,50 @@ int need_finalized(ovmr_handle* h) {
     return h->finalized ? 0 : fail(h, OVMR_E_STATE, "ovmr_finalize() has not been called");
 }
 
-const Buf* find(ovmr_handle* h, const std::string& name, size_t elems) {
-    auto it = h->w.find(name);
-    if (it == h->w.end()) { fail(h, OVMR_E_STATE, "weight '%s' was never set", name.c_str()); return nullptr; }
-    if (it->second.elems != elems) {
-        fail(h, OVMR_E_SHAPE, "weight '%s' has %zu elements, expected %zu", name.c_str(), it->second.elems, elems);
-        return nullptr;
-    }
-    return &it->second;
+// The weights, each stated ONCE: name (block weights: the suffix behind "<prefix><layer>."), elements, stored dtype and where ovmr_finalize
+// binds it.  ovmr_set_weight reads the tables for "is this name known" and the dtype, ovmr_finalize for presence, size and binding, in
+// table order.  dtype policy of convert_weights() (clip/model.py:852-873): LayerNorm parameters and embeddings stay fp32.
+struct Weight { const char* name; size_t elems; bool f32; void** dst; };
+
+std::array<Weight, 12> block_weights(size_t w, Block& k) {
+    return {{{"attn.in_proj_weight", 3 * w * w, false, &k.in_w}, {"attn.in_proj_bias", 3 * w, false, &k.in_b},
+             {"attn.out_proj.weight", w * w, false, &k.out_w},   {"attn.out_proj.bias", w, false, &k.out_b},
+             {"mlp.c_fc.weight", 4 * w * w, false, &k.fc_w},     {"mlp.c_fc.bias", 4 * w, false, &k.fc_b},
+             {"mlp.c_proj.weight", 4 * w * w, false, &k.pj_w},   {"mlp.c_proj.bias", w, false, &k.pj_b},
+             {"ln_1.weight", w, true, (void**)&k.ln1_g},         {"ln_1.bias", w, true, (void**)&k.ln1_b},
+             {"ln_2.weight", w, true, (void**)&k.ln2_g},         {"ln_2.bias", w, true, (void**)&k.ln2_b}}};
 }
 
-int bind_blocks(ovmr_handle* h, const std::string& prefix, int layers, int W, std::vector<Block>& out) {
-    out.assign(layers, Block());
-    const size_t w = (size_t)W;
-    for (int i = 0; i < layers; ++i) {
-        const std::string p = prefix + std::to_string(i) + ".";
-        struct { const char* n; size_t e; void** dst; } items[] = {
-            {"attn.in_proj_weight", 3 * w * w, &out[i].in_w}, {"attn.in_proj_bias", 3 * w, &out[i].in_b},
-            {"attn.out_proj.weight", w * w, &out[i].out_w},   {"attn.out_proj.bias", w, &out[i].out_b},
-            {"mlp.c_fc.weight", 4 * w * w, &out[i].fc_w},     {"mlp.c_fc.bias", 4 * w, &out[i].fc_b},
-            {"mlp.c_proj.weight", 4 * w * w, &out[i].pj_w},   {"mlp.c_proj.bias", w, &out[i].pj_b},
-            {"ln_1.weight", w, (void**)&out[i].ln1_g},        {"ln_1.bias", w, (void**)&out[i].ln1_b},
-            {"ln_2.weight", w, (void**)&out[i].ln2_g},        {"ln_2.bias", w, (void**)&out[i].ln2_b}};
-        for (auto& it : items) {
-            const Buf* b = find(h, p + it.n, it.e);
-            if (!b) return OVMR_E_STATE;
-            *it.dst = b->p;
-        }
-    }
+struct Tower { const char* prefix; int layers, width; std::vector<Block>* blocks; bool f32; };
+std::array<Tower, 3> towers(ovmr_handle* h) {
+    const ovmr_model_desc& d = h->d;
+    return {{{"visual.transformer.resblocks.", d.vision_layers, d.vision_width, &h->vis, false},
+             {"transformer.resblocks.", d.transformer_layers, d.transformer_width, &h->txt, false},
+             {"prompt_learner.aggregator.resblocks.", d.agg_layers, d.embed_dim, &h->agg, true}}};   // the aggregator is never halved
+}
+
+std::array<Weight, 14> single_weights(ovmr_handle* h) {   // (logit_scale is none of them: read to the host, never stored)
+    const ovmr_model_desc& d = h->d;
+    const size_t W = d.vision_width, T = d.transformer_width, E = d.embed_dim, P = d.vision_patch_size;
+    return {{{"visual.conv1.weight", W * 3 * P * P, false, &h->conv1},
+             {"visual.class_embedding", W, true, &h->cls_emb},
+             {"visual.positional_embedding", (size_t)h->L * W, true, &h->pos_vis},
+             {"visual.proj", W * E, false, &h->proj},
+             {"positional_embedding", (size_t)d.context_length * T, true, &h->pos_txt},
+             {"text_projection", T * E, false, &h->textproj},
+             {"visual.ln_pre.weight", W, true, (void**)&h->ln_pre_g},   {"visual.ln_pre.bias", W, true, (void**)&h->ln_pre_b},
+             {"visual.ln_post.weight", W, true, (void**)&h->ln_post_g}, {"visual.ln_post.bias", W, true, (void**)&h->ln_post_b},
+             {"ln_final.weight", T, true, (void**)&h->ln_final_g},      {"ln_final.bias", T, true, (void**)&h->ln_final_b},
+             {"token_embedding.weight", (size_t)d.vocab_size * T, true, (void**)&h->tok_emb},
+             {"prompt_learner.cls_token", (size_t)d.n_ctx * E, true, (void**)&h->cls_token}}};
+}
+
+int bind_weight(ovmr_handle* h, const std::string& name, const Weight& wt) {
+    auto it = h->w.find(name);
+    if (it == h->w.end()) return fail(h, OVMR_E_STATE, "weight '%s' was never set", name.c_str());
+    if (it->second.elems != wt.elems)
+        return fail(h, OVMR_E_STATE, "weight '%s' has %zu elements, expected %zu", name.c_str(), it->second.elems, wt.elems);
+    *wt.dst = it->second.p;
     return 0;
 }
 
@@ -164,18 +165,6 @@ GemmArgs gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, 
     a.M = M; a.N = N; a.K = K; a.epi = epi; a.bias = bias; a.res = res; a.ldres = ldres; a.scale = 1.f;
     return a;
 }
-
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-// The workspace is one arena that every pass carves anew (calls on one handle are stream ordered).  Each pass states its buffers ONCE,
-// as a Carver whose constructor takes them in order: on a null base that only measures (ovmr_finalize sizes the arena with bytes()),
-// on h->ws it hands out the pointers the entry point uses -- so a buffer cannot be sized without being carved, or the reverse.
-struct Carver {
-    char* base; size_t off = 0;
-    explicit Carver(char* b) : base(b) {}
-    template <typename T> T* take(size_t n) { T* p = base ? (T*)(base + off) : nullptr; off = align_up(off + n * sizeof(T)); return p; }
-    size_t bytes() const { return off; }
-};
 
 // One pass of an fp16 tower over M token rows of N sequences.  Image tower (image_ws): the patch rows `col` come first and `rows` are
 // the CLS rows; text tower (text_ws): `rows` are the read-out rows and `index` their positions.  A buffer of 0 elements takes no room.
@@ -214,7 +203,7 @@ struct AggWs : Carver {         // the fp32 aggregator over `rows` token rows
 };
 
 // The classifier head's GEMM path: `n_logits` buffers of logit_elems_cap fp16 logits, then 65536 rows of scaled features.
-// ovmr_fused_logits takes three (ovmr_finalize sizes for that), ovmr_xval_counts one, ovmr_zeroshot_logits none.
+// A probability call takes one per classifier (ovmr_finalize sizes for three), ovmr_xval_counts one, a raw call (zero-shot) none.
 struct HeadWs : Carver {
     half_t *l[3] = {nullptr, nullptr, nullptr}, *sf;
     HeadWs(const ovmr_handle* h, char* base, int n_logits) : Carver(base) {
@@ -461,6 +450,41 @@ bool head_takes_one_launch(const ovmr_handle* h, int B, int C) {
     return h->fused_head && (B <= 256 || (B <= 512 && C <= 2048) || h->fused_head == 2) && head_fused_ws_bytes(B, C) <= h->ws_bytes;
 }
 
+// One call of the classifier head: the probabilities of n_mod classifiers [C, D] weighted by w [C, 3] (null: one classifier, weight 1)
+// into fp32 `out` [B, C] (plane_stride > 0: the four planes of the all-modes form), or the fp16 logits of ONE classifier into raw_out.
+struct HeadCall {
+    const half_t* feats; int B;
+    const half_t* clf[3]; int n_mod;
+    const float* w;
+    int C;
+    float* out; long plane_stride;
+    half_t* raw_out;
+};
+
+// The one-launch head (head_fused.hip) where the call takes it -- raw calls whenever fused_head is set, at any size (one pass, no workspace,
+// no counters); the others under head_takes_one_launch -- and the launcher takes the shape; else scale + GEMMs + softmax over row chunks.
+int run_head(ovmr_handle* h, const HeadCall& c, hipStream_t s) {
+    const int D = h->d.embed_dim, C = c.C;
+    const bool raw = c.raw_out != nullptr;
+    if (raw ? h->fused_head != 0 : head_takes_one_launch(h, c.B, C)) {
+        // one launch: scaled features staged once, the (up to) three products, both rounding points, softmax and weighted sum
+        const int rc = launch_head_fused(c.feats, c.B, D, h->logit_scale_exp, c.clf, c.n_mod, C, c.w, c.out, c.plane_stride, c.raw_out,
+                                         h->ws, h->head_sync, h->n_cu, h->head_max_grid, s);
+        if (rc != -100) { CK(rc); return 0; }
+    }
+    const HeadWs ws(h, h->ws, raw ? 0 : c.n_mod);            // raw logits go straight to raw_out: no logits buffer bounds the chunk
+    const int chunk = raw ? 65536 : (int)std::min<long>(std::max<long>(1, h->logit_elems_cap / C), 65536);
+    for (int b0 = 0; b0 < c.B; b0 += chunk) {
+        const int Bc = std::min(chunk, c.B - b0);
+        // (logit_scale * image_features) is rounded to fp16 before the matmul (:358-360)
+        CK(launch_scale_f16(c.feats + (size_t)b0 * D, ws.sf, h->logit_scale_exp, (long)Bc * D, s));
+        for (int m = 0; m < c.n_mod; ++m)
+            CK(launch_gemm_f16(gemm(ws.sf, D, c.clf[m], D, raw ? c.raw_out + (size_t)b0 * C : ws.l[m], C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
+        if (!raw) CK(launch_fused_softmax(ws.l[0], ws.l[1], ws.l[2], c.w, c.n_mod, c.out + (size_t)b0 * C, c.plane_stride, Bc, C, s));   // every plane advances by b0 * C
+    }
+    return 0;
+}
+
 int check_text_call(ovmr_handle* h, int seq_len, int normalize) {
     if (normalize < 0 || normalize > 2) return OVMR_E_ARG;
     if (int rc = need_finalized(h)) return rc;
@@ -592,20 +616,6 @@ int ovmr_set_weight(ovmr_handle* h, const char* name_c, const void* data, int dt
     const std::string name(name_c);
     size_t elems = 1;
     for (int i = 0; i < ndim; ++i) elems *= (size_t)shape[i];
-    static const char* suffixes[] = {"attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias",
-                                     "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias",
-                                     "ln_1.weight", "ln_1.bias", "ln_2.weight", "ln_2.bias"};
-    bool known = false;
-    if (name.rfind("visual.transformer.resblocks.", 0) == 0 || name.rfind("transformer.resblocks.", 0) == 0 ||
-        name.rfind("prompt_learner.aggregator.resblocks.", 0) == 0)
-        for (const char* sf : suffixes) known |= ends_with(name, sf);
-    static const char* singles[] = {"visual.class_embedding", "visual.positional_embedding", "visual.proj", "visual.conv1.weight",
-                                    "visual.ln_pre.weight", "visual.ln_pre.bias", "visual.ln_post.weight", "visual.ln_post.bias",
-                                    "token_embedding.weight", "positional_embedding", "ln_final.weight", "ln_final.bias",
-                                    "text_projection", "logit_scale", "prompt_learner.cls_token"};
-    for (const char* sn : singles) known |= (name == sn);
-    if (!known) return fail(h, OVMR_E_NAME, "unknown weight name '%s'", name_c);
-
     if (name == "logit_scale") {
         if (elems != 1) return fail(h, OVMR_E_SHAPE, "logit_scale must be a scalar");
         float v = 0.f;
@@ -622,8 +632,17 @@ int ovmr_set_weight(ovmr_handle* h, const char* name_c, const void* data, int dt
         h->have_logit_scale = true;
         return 0;
     }
+    int f32 = -1;                         // the stored dtype, from the tables; -1: no table has the name
+    Block none;
+    for (const Tower& t : towers(h))
+        if (name.rfind(t.prefix, 0) == 0)
+            for (const Weight& wt : block_weights(0, none))
+                if (ends_with(name, wt.name)) f32 = wt.f32 || t.f32;
+    for (const Weight& wt : single_weights(h))
+        if (name == wt.name) f32 = wt.f32;
+    if (f32 < 0) return fail(h, OVMR_E_NAME, "unknown weight name '%s'", name_c);
     Buf& b = h->w[name];
-    b.f32 = stored_as_f32(name) ? 1 : 0;
+    b.f32 = f32;
     if (!b.p || b.elems != elems) {
         b.p = dev_alloc(h->owned, elems * (b.f32 ? 4 : 2));
         if (!b.p) return fail(h, OVMR_E_NOMEM, "hipMalloc failed for '%s'", name_c);
@@ -641,24 +660,14 @@ int ovmr_finalize(ovmr_handle* h, int max_images, int max_prompts, int max_class
     const size_t W = d.vision_width, T = d.transformer_width, E = d.embed_dim, P = d.vision_patch_size;
     if (!h->have_logit_scale) return fail(h, OVMR_E_STATE, "weight 'logit_scale' was never set");
 
-    if (int rc = bind_blocks(h, "visual.transformer.resblocks.", d.vision_layers, (int)W, h->vis)) return rc;
-    if (int rc = bind_blocks(h, "transformer.resblocks.", d.transformer_layers, (int)T, h->txt)) return rc;
-    if (int rc = bind_blocks(h, "prompt_learner.aggregator.resblocks.", d.agg_layers, (int)E, h->agg)) return rc;
-
-    const Buf *conv, *cls, *pos, *proj, *tpos, *tproj, *b;
-    if (!(conv = find(h, "visual.conv1.weight", W * 3 * P * P))) return OVMR_E_STATE;
-    if (!(cls = find(h, "visual.class_embedding", W))) return OVMR_E_STATE;
-    if (!(pos = find(h, "visual.positional_embedding", (size_t)h->L * W))) return OVMR_E_STATE;
-    if (!(proj = find(h, "visual.proj", W * E))) return OVMR_E_STATE;
-    if (!(tpos = find(h, "positional_embedding", (size_t)d.context_length * T))) return OVMR_E_STATE;
-    if (!(tproj = find(h, "text_projection", T * E))) return OVMR_E_STATE;
-#define BINDF(field, nm, n) if (!(b = find(h, nm, n))) return OVMR_E_STATE; h->field = (float*)b->p;
-    BINDF(ln_pre_g, "visual.ln_pre.weight", W) BINDF(ln_pre_b, "visual.ln_pre.bias", W)
-    BINDF(ln_post_g, "visual.ln_post.weight", W) BINDF(ln_post_b, "visual.ln_post.bias", W)
-    BINDF(ln_final_g, "ln_final.weight", T) BINDF(ln_final_b, "ln_final.bias", T)
-    BINDF(tok_emb, "token_embedding.weight", (size_t)d.vocab_size * T)
-    BINDF(cls_token, "prompt_learner.cls_token", (size_t)d.n_ctx * E)
-#undef BINDF
+    for (const Tower& t : towers(h)) {
+        t.blocks->assign(t.layers, Block());
+        for (int i = 0; i < t.layers; ++i)
+            for (const Weight& wt : block_weights(t.width, (*t.blocks)[i]))
+                if (int rc = bind_weight(h, t.prefix + std::to_string(i) + "." + wt.name, wt)) return rc;
+    }
+    for (const Weight& wt : single_weights(h))
+        if (int rc = bind_weight(h, wt.name, wt)) return rc;
 
     // derived layouts of a previous finalize are dropped first (the stream is idle: every finalize ends with a sync)
     HIP_CHECK_RET(hipStreamSynchronize(s));
@@ -674,13 +683,13 @@ int ovmr_finalize(ovmr_handle* h, int max_images, int max_prompts, int max_class
     half_t* cls16 = (half_t*)dalloc(W * 2);
     if (!h->conv_w || !h->pos16_vis || !h->cls_pos16 || !h->proj_t || !h->pos16_txt || !h->textproj_t || !cls16)
         return fail(h, OVMR_E_NOMEM, "hipMalloc failed for derived weights");
-    CK(launch_pad_rows_f16((const half_t*)conv->p, h->conv_w, (int)W, (int)(3 * P * P), h->Kpad, s));
-    CK(launch_cast(pos->p, 1, h->pos16_vis, 0, (long)h->L * W, s));            // positional_embedding.to(fp16), clip/model.py:416
-    CK(launch_cast(cls->p, 1, cls16, 0, (long)W, s));                          // class_embedding.to(fp16), :415
+    CK(launch_pad_rows_f16((const half_t*)h->conv1, h->conv_w, (int)W, (int)(3 * P * P), h->Kpad, s));
+    CK(launch_cast(h->pos_vis, 1, h->pos16_vis, 0, (long)h->L * W, s));        // positional_embedding.to(fp16), clip/model.py:416
+    CK(launch_cast(h->cls_emb, 1, cls16, 0, (long)W, s));                      // class_embedding.to(fp16), :415
     CK(launch_add_f16(cls16, h->pos16_vis, h->cls_pos16, (long)W, s));
-    CK(launch_transpose_to_f16(proj->p, 0, h->proj_t, (int)W, (int)E, s));     // x @ proj == x * proj^T^T
-    CK(launch_cast(tpos->p, 1, h->pos16_txt, 0, (long)d.context_length * T, s));
-    CK(launch_transpose_to_f16(tproj->p, 0, h->textproj_t, (int)T, (int)E, s));
+    CK(launch_transpose_to_f16(h->proj, 0, h->proj_t, (int)W, (int)E, s));     // x @ proj == x * proj^T^T
+    CK(launch_cast(h->pos_txt, 1, h->pos16_txt, 0, (long)d.context_length * T, s));
+    CK(launch_transpose_to_f16(h->textproj, 0, h->textproj_t, (int)T, (int)E, s));
 
     // LayerNorm folded into in_proj / c_fc of the two fp16 towers (common.h EPI_LN_BIAS)
     for (auto* tower : {&h->vis, &h->txt}) {
@@ -1001,37 +1010,17 @@ int ovmr_fused_logits(ovmr_handle* h, const void* feats_f16, int B, const void* 
     if (h && B == 0) return 0;
     if (!h || !feats_f16 || !out_f32 || B < 0 || C < 1) return OVMR_E_ARG;
     if (int rc = need_finalized(h)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int D = h->d.embed_dim;
-    const void* clf[3];
-    int n_mod;
+    const half_t *cm = (const half_t*)mm, *cv = (const half_t*)v, *ct = (const half_t*)t;
+    HeadCall c = {(const half_t*)feats_f16, B, {nullptr, nullptr, nullptr}, 1, nullptr, C, out_f32, 0, nullptr};
     switch (mode) {
-        case OVMR_MODE_FUSION: clf[0] = mm; clf[1] = v; clf[2] = t; n_mod = 3; if (!w) return OVMR_E_ARG; break;   // column order mm, v, t (:361)
-        case OVMR_MODE_TEXT: clf[0] = t; n_mod = 1; break;
-        case OVMR_MODE_VISION: clf[0] = v; n_mod = 1; break;
-        case OVMR_MODE_MULTIMODAL: clf[0] = mm; n_mod = 1; break;
+        case OVMR_MODE_FUSION: c.clf[0] = cm; c.clf[1] = cv; c.clf[2] = ct; c.n_mod = 3; c.w = w; if (!w) return OVMR_E_ARG; break;   // column order mm, v, t (:361)
+        case OVMR_MODE_TEXT: c.clf[0] = ct; break;
+        case OVMR_MODE_VISION: c.clf[0] = cv; break;
+        case OVMR_MODE_MULTIMODAL: c.clf[0] = cm; break;
         default: return fail(h, OVMR_E_ARG, "unknown eval mode %d", mode);
     }
-    for (int m = 0; m < n_mod; ++m) if (!clf[m]) return fail(h, OVMR_E_ARG, "classifier %d is NULL for mode %d", m, mode);
-    if (head_takes_one_launch(h, B, C)) {
-        // one launch: scaled features staged once, the (up to) three products, both rounding points, softmax and weighted sum (head_fused.hip)
-        const half_t* cl[3] = {(const half_t*)clf[0], n_mod > 1 ? (const half_t*)clf[1] : nullptr, n_mod > 2 ? (const half_t*)clf[2] : nullptr};
-        const int rc = launch_head_fused((const half_t*)feats_f16, B, D, h->logit_scale_exp, cl, n_mod, C, mode == OVMR_MODE_FUSION ? w : nullptr,
-                                         out_f32, 0, nullptr, h->ws, h->head_sync, h->n_cu, h->head_max_grid, s);
-        if (rc != -100) { CK(rc); return 0; }
-    }
-    const int chunk = (int)std::min<long>(std::max<long>(1, h->logit_elems_cap / C), 65536);
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int Bc = std::min(chunk, B - b0);
-        const HeadWs ws(h, h->ws, 3);
-        // (logit_scale * image_features) is rounded to fp16 before the matmul (:358-360)
-        CK(launch_scale_f16((const half_t*)feats_f16 + (size_t)b0 * D, ws.sf, h->logit_scale_exp, (long)Bc * D, s));
-        for (int m = 0; m < n_mod; ++m)
-            CK(launch_gemm_f16(gemm(ws.sf, D, clf[m], D, ws.l[m], C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
-        CK(launch_fused_softmax(ws.l[0], n_mod > 1 ? ws.l[1] : nullptr, n_mod > 2 ? ws.l[2] : nullptr,
-                                mode == OVMR_MODE_FUSION ? w : nullptr, n_mod, out_f32 + (size_t)b0 * C, Bc, C, s));
-    }
-    return 0;
+    for (int m = 0; m < c.n_mod; ++m) if (!c.clf[m]) return fail(h, OVMR_E_ARG, "classifier %d is NULL for mode %d", m, mode);
+    return run_head(h, c, (hipStream_t)stream);
 }
 
 // The four eval modes of one batch from one pass over the head (EVAL_MODE all): the route, the options and the workspace of
@@ -1041,24 +1030,8 @@ int ovmr_fused_logits_all(ovmr_handle* h, const void* feats_f16, int B, const vo
     if (h && B == 0) return 0;
     if (!h || !feats_f16 || !mm || !v || !t || !w || !out_f32 || B < 0 || C < 1 || plane_stride < (long)B * C) return OVMR_E_ARG;
     if (int rc = need_finalized(h)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int D = h->d.embed_dim;
-    const half_t* cl[3] = {(const half_t*)mm, (const half_t*)v, (const half_t*)t};           // column order mm, v, t (:361)
-    if (head_takes_one_launch(h, B, C)) {
-        const int rc = launch_head_fused((const half_t*)feats_f16, B, D, h->logit_scale_exp, cl, 3, C, w, out_f32, plane_stride, nullptr,
-                                         h->ws, h->head_sync, h->n_cu, h->head_max_grid, s);
-        if (rc != -100) { CK(rc); return 0; }
-    }
-    const int chunk = (int)std::min<long>(std::max<long>(1, h->logit_elems_cap / C), 65536);
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int Bc = std::min(chunk, B - b0);
-        const HeadWs ws(h, h->ws, 3);
-        CK(launch_scale_f16((const half_t*)feats_f16 + (size_t)b0 * D, ws.sf, h->logit_scale_exp, (long)Bc * D, s));
-        for (int m = 0; m < 3; ++m)
-            CK(launch_gemm_f16(gemm(ws.sf, D, cl[m], D, ws.l[m], C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
-        CK(launch_fused_softmax_all(ws.l[0], ws.l[1], ws.l[2], w, out_f32 + (size_t)b0 * C, plane_stride, Bc, C, s));   // every plane advances by b0 * C
-    }
-    return 0;
+    const HeadCall c = {(const half_t*)feats_f16, B, {(const half_t*)mm, (const half_t*)v, (const half_t*)t}, 3, w, C, out_f32, plane_stride, nullptr};   // column order mm, v, t (:361)
+    return run_head(h, c, (hipStream_t)stream);
 }
 
 int ovmr_zeroshot_logits(ovmr_handle* h, const void* feats_f16, int B, const void* text_f16, int C, void* out_f16,
@@ -1066,21 +1039,8 @@ int ovmr_zeroshot_logits(ovmr_handle* h, const void* feats_f16, int B, const voi
     if (h && B == 0) return 0;
     if (!h || !feats_f16 || !text_f16 || !out_f16 || B < 0 || C < 1) return OVMR_E_ARG;
     if (int rc = need_finalized(h)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    const int D = h->d.embed_dim;
-    if (h->fused_head) {                           // scale, product and the fp16 rounding of the logits in one launch
-        const half_t* cl[3] = {(const half_t*)text_f16, nullptr, nullptr};
-        const int rc = launch_head_fused((const half_t*)feats_f16, B, D, h->logit_scale_exp, cl, 1, C, nullptr, nullptr, 0, (half_t*)out_f16,
-                                         nullptr, nullptr, h->n_cu, 0, s);
-        if (rc != -100) { CK(rc); return 0; }
-    }
-    for (int b0 = 0; b0 < B; b0 += 65536) {
-        const int Bc = std::min(65536, B - b0);
-        half_t* sf = HeadWs(h, h->ws, 0).sf;
-        CK(launch_scale_f16((const half_t*)feats_f16 + (size_t)b0 * D, sf, h->logit_scale_exp, (long)Bc * D, s));
-        CK(launch_gemm_f16(gemm(sf, D, text_f16, D, (half_t*)out_f16 + (size_t)b0 * C, C, Bc, C, D, EPI_NONE), h->gemm_variant, s));
-    }
-    return 0;
+    const HeadCall c = {(const half_t*)feats_f16, B, {(const half_t*)text_f16, nullptr, nullptr}, 1, nullptr, C, nullptr, 0, (half_t*)out_f16};
+    return run_head(h, c, (hipStream_t)stream);
 }
 
 // Closed-form FLOPs (2*MAC), SURVEY.md section 2.3: per layer 24*L*W^2 (QKV 6, out 2, MLP 16) + 4*L^2*W

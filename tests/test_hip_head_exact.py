@@ -3,6 +3,7 @@ partial sum of every dot product is exact in fp32 (head_exact.py: the method, th
 logits are then ONE number in any summation order, so
 
   * zero-shot logits are compared bit for bit with the expected fp16 logits, one-launch kernel and scale + GEMM path, every GEMM variant;
+    test_zeroshot_row_chunks does so over 65536 + 33 rows, where the scale + GEMM path runs two row chunks;
   * probabilities (fusion / text / vision / multimodal) with the fp64 softmax of the expected logits weighted by w:
     |got - ref| <= 1e-4 * ref + tiny, row sums within 1e-4 -- for the one-launch head at its full grid, capped at 1, 3 and Tc + 1
     workgroups (recompute queue), as the entry rule decides, and for the five-launch path under GEMM variants 0, 6, 8, 9;
@@ -172,6 +173,29 @@ def test_head_exact(shape):
                 torch.cuda.synchronize()
                 msg = H.counts_mismatch(counts[0], counts[1], xl, labels)
                 assert msg is None, f"xval_counts, {tag}, classifier {m}, {where}: {msg}"
+    finally:
+        _reset(e)
+
+
+def test_zeroshot_row_chunks():
+    """ovmr_zeroshot_logits over more than 65536 rows: the scale + GEMM path runs two row chunks, the second one 33 rows (a partial
+    tile) behind b0 * C logits; C = 5 is an odd ldc (rows that are not 16-byte aligned, the scalar store arm).  Bit-equal logits from
+    GEMM variants 0 and 8 and from the one-launch kernel, which takes a raw call at any size."""
+    B, C, D = 65536 + 33, 5, 128
+    e = _engine(D)
+    _reset(e)
+    feats, clfs, _, logits = H.exact_head_case(B, C, D, 1, e.logit_scale, B + C)
+    fd, cd, ld = feats.cuda(), clfs[0].cuda(), logits[0].cuda()
+    try:
+        for tag, fused, gv in (("scale + GEMM, gemm 0", 0, 0), ("scale + GEMM, gemm 8", 0, 8), ("one launch", 1, 8)):
+            e.set_option("fused_head", fused)
+            e.set_option("gemm", gv)
+            flat, out = _sentinel_out(B, C, torch.float16)
+            z = e.zeroshot_logits(fd, cd, out=out)
+            torch.cuda.synchronize()
+            msg = H.logits_mismatch(z, ld)
+            assert msg is None, f"zero-shot logits, {tag}, B={B} C={C} D={D}: {msg}"
+            assert _tail_untouched(flat, B, C), f"zero-shot logits, {tag}: wrote behind row {B}"
     finally:
         _reset(e)
 
