@@ -64,7 +64,7 @@ void ovmr_destroy(ovmr_handle* h);
 const char* ovmr_last_error(const ovmr_handle* h);
 const char* ovmr_version(void);
 
-/* Kernel-variant switch used by tests/bench to A/B implementations: key in {"gemm","attn","ln_fold","xval_fused","gelu_exact","fuse_im2col","enc_chunk","last_q_cls","fused_head","head_max_grid"}.
+/* Kernel-variant switch used by tests/bench to A/B implementations: key in {"gemm","attn","ln_fold","xval_fused","gelu_exact","fuse_im2col","enc_chunk","last_q_cls","fused_head","head_max_grid","agg_max_len"}.
  * "gemm" (default 8): which fp16 GEMM kernel a launch runs, and with which K loop, tile height and cache hints (gemm_f16_route in
  *   csrc/gemm_f16.hip, exported as ovmr_debug_gemm_route):
  *   8 = 256-row LDS-DMA tiles with the ping-pong K loop (half-tile staging, counted waits) and, for latency-bound shapes
@@ -97,7 +97,13 @@ const char* ovmr_version(void);
  *   sum) for up to 256 query rows, or up to 512 rows x 2048 classes; larger calls run scale + GEMMs + softmax as separate launches.
  *   2 = one launch at any size; 0 = never.  The two implementations sum K in different orders: a logit may land on the neighbouring fp16
  *   value (tests/test_hip_parity.py:test_fusion_head_vs_oracle holds both to the oracle).
- * "head_max_grid" (default 0 = one workgroup per tile): caps the one-launch head's grid (tests: workgroups then take several tiles). */
+ * "head_max_grid" (default 0 = one workgroup per tile): caps the one-launch head's grid (tests: workgroups then take several tiles).
+ * "agg_max_len" (default 128): the most aggregator rows, n_ctx + shots, one class may bring to ovmr_generate_tokens /
+ *   ovmr_generate_tokens_ragged.  128 .. OVMR_AGG_MAX_LEN_CEILING; any other value returns OVMR_E_ARG and leaves the option as it was.  A
+ *   chunk whose longest class has at most 128 rows runs attn_f32_small whatever the option says; a longer one runs attn_f32_long (csrc/attention.hip)
+ *   for all its classes, each to the same bits.  Set before ovmr_finalize, the aggregator's workspace holds at least one class of that
+ *   length; raised afterwards, a class that does not fit the workspace is refused (OVMR_E_SHAPE) before anything launches. */
+#define OVMR_AGG_MAX_LEN_CEILING 4096   /* rows per class: keeps a launch's row arithmetic in int and its grid (classes x heads x 32 query tiles) small */
 int ovmr_set_option(ovmr_handle* h, const char* key, int value);
 
 /* Weight ingestion -- replaces build_model()/convert_weights()/load_state_dict
@@ -173,7 +179,9 @@ int ovmr_embed_tokens(ovmr_handle* h, const int64_t* ids, int N, int L, void* ou
 /* PromptLearner.forward, visual-token generator part (trainers/mm_classifier_one_prompt.py:167-169):
  * feats [Cb, S, embed_dim] fp16 -> tokens [Cb, n_ctx, embed_dim] fp32 (aggregator in fp32).  The arithmetic mode of the sequence
  * table ovmr_generate_tokens_ragged reads (AggSeqs, csrc/common.h): the same generator, the same kernels (agg_input_kernel,
- * attn_f32_small, agg_output_kernel), class c's rows at c * (n_ctx + S) computed, no device array loaded. */
+ * attn_f32_small or, beyond 128 rows per class, attn_f32_long; agg_output_kernel), class c's rows at c * (n_ctx + S) computed, no device
+ * array loaded.  OVMR_E_SHAPE before any launch when n_ctx + S exceeds option "agg_max_len" (default 128, at most
+ * OVMR_AGG_MAX_LEN_CEILING), or when a chunk's rows do not fit the workspace. */
 int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S,
                          float* tokens_f32, ovmr_stream stream);
 
@@ -187,7 +195,8 @@ int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S,
  * two views that disagree give wrong values, never an access outside the buffers).  Asynchronous, allocation-free, capturable.
  * THE CONTRACT: tokens[c] is bit-identical to what ovmr_generate_tokens returns for class c alone with S = shots[c] on the same
  * handle, whatever else shares the call and wherever the chunk boundaries fall; a call whose counts are all S equals the uniform call.
- * OVMR_E_SHAPE before any launch, naming the class: a count < 1, n_ctx + shots[c] > 128; also when the shots do not add up to R.
+ * OVMR_E_SHAPE before any launch, naming the class: a count < 1, n_ctx + shots[c] above option "agg_max_len" (default 128, at most
+ * OVMR_AGG_MAX_LEN_CEILING), a class whose rows do not fit the workspace; also when the shots do not add up to R.
  * Cb == 0 returns 0. */
 int ovmr_generate_tokens_ragged(ovmr_handle* h, const void* feats_f16, const int32_t* shots_host, const int32_t* offsets_dev,
                                 int Cb, int R, float* tokens_f32, ovmr_stream stream);
@@ -407,6 +416,13 @@ int ovmr_debug_gemm_strided(int variant, const void* A, int lda, const void* W, 
  * mode: row by row the same arithmetic.  -2 for max_len > 128. */
 int ovmr_debug_attention_f32_varlen(const void* qkv, void* out, const int32_t* offsets_dev, int nseq, int n_ctx, int max_len, int H,
                                     ovmr_stream stream);
+
+/* attn_f32_long, the kernel the generator runs for a chunk whose longest class has more than 128 rows, launched directly at ANY max_len
+ * (short launches included): 128-row query tiles, the keys walked in order in 64-key LDS blocks.  offsets_dev as above, or NULL for the
+ * uniform mode: nseq sequences of max_len rows each, n_ctx unused.  Per sequence bit-equal to attn_f32_small up to 128 rows and to
+ * this launch on the sequence alone beyond; max_len only sizes the grid.  -2 for max_len > OVMR_AGG_MAX_LEN_CEILING, before any launch. */
+int ovmr_debug_attention_f32_long(const void* qkv, void* out, const int32_t* offsets_dev, int nseq, int n_ctx, int max_len, int H,
+                                  ovmr_stream stream);
 /* fp16 attention for the first Lq <= L queries of every sequence (the last vision block runs Lq = 1, the CLS query):
  * out [B*Lq, H*64], row b*Lq + q.  Lq > L returns OVMR_E_SHAPE. */
 int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L, int Lq, int H, int causal,

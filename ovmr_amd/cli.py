@@ -496,7 +496,8 @@ def main(argv=None) -> Dict[str, float]:
         if shots < 1:
             raise SystemExit("DATASET.NUM_SHOTS must be >= 1: the eval-set loader draws NUM_SHOTS rows per class (data_manager.py:157-170)")
         if batch < shots:
-            raise SystemExit(f"DATALOADER.TEST.BATCH_SIZE {batch} is smaller than DATASET.NUM_SHOTS {shots}: RandomClassSampler needs one class per batch")
+            raise SystemExit(f"DATALOADER.TEST.BATCH_SIZE {batch} is smaller than DATASET.NUM_SHOTS {shots}: a loader batch holds whole classes "
+                             f"(RandomClassSampler needs one class per batch), raise TEST.BATCH_SIZE to at least {shots}")
         if cfg.DATALOADER.K_TRANSFORMS != 1:
             raise SystemExit("DATALOADER.K_TRANSFORMS > 1 only applies to training transforms; the test transform has one view")
 

@@ -133,9 +133,9 @@ __global__ __launch_bounds__(256) void attn_f16_v0(const half_t* __restrict__ qk
 }
 
 // fp32, sequences of at most 128 rows packed row after row (AggSeqs, common.h): one workgroup per (sequence, head), K and V in LDS sized
-// by the launch's longest sequence (q.len rows each), a thread per query row through attn::f32_row, single-pass online softmax.  A
-// row's bits depend on its own sequence alone.  TABLE: the starts come from the device prefix sum, clamped, and a workgroup takes at
-// most q.len rows; uniform: sequence b is the rows [b * q.len, (b + 1) * q.len), nothing loaded.
+// by the launch's longest sequence (q.len rows each), a thread per query row through the three steps of attn::F32Row, single-pass online
+// softmax.  A row's bits depend on its own sequence alone.  TABLE: the starts come from the device prefix sum, clamped, and a workgroup
+// takes at most q.len rows; uniform: sequence b is the rows [b * q.len, (b + 1) * q.len), nothing loaded.
 template <bool TABLE>
 __global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ qkv, float* __restrict__ out, const AggSeqs q,
                                                       int H, float scale) {
@@ -155,7 +155,51 @@ __global__ __launch_bounds__(128) void attn_f32_small(const float* __restrict__ 
     }
     __syncthreads();
     if (tid >= L) return;
-    attn::f32_row(base + (long)tid * ld, sK, sV, L, scale, out + (r0 + tid) * D + h * 64);
+    attn::F32Row r;
+    attn::f32_row_begin(r, base + (long)tid * ld);
+    attn::f32_row_keys(r, sK, sV, 0, L, scale);
+    attn::f32_row_end(r, out + (r0 + tid) * D + h * 64);
+}
+
+// The same attention over sequences of any length up to q.len, in the same two modes: a workgroup is the 128-row query tile `tile` of one
+// (sequence, head), a thread per query row, and walks the sequence's keys IN ORDER in blocks of attn::F32_KEYS keys staged in LDS --
+// stage, barrier, every live row advances over the block's keys, barrier, next block.  The rows go through the same three steps as
+// attn_f32_small's, the keys in the same order: a sequence of at most 128 rows gets the bits that kernel gives it, a longer one the
+// bits of this kernel on it alone, and q.len, which only sizes the grid (nT = ceil(q.len / 128) tiles per (sequence, head)), changes
+// nothing.
+// Barriers: L and `tile` are the same for every thread of a workgroup, so the return of a tile that starts at or behind the sequence's
+// end is taken by all of them or by none, in front of the first barrier, and the block loop has the same trip count for all.  A
+// thread whose row lies behind the end (the last tile) stages and meets every barrier; it only skips the steps of its row.
+template <bool TABLE>
+__global__ __launch_bounds__(128) void attn_f32_long(const float* __restrict__ qkv, float* __restrict__ out, const AggSeqs q, int H,
+                                                     int nT, float scale) {
+    constexpr int TILE = attn::F32_TILE, KEYS = attn::F32_KEYS;
+    __shared__ __attribute__((aligned(16))) float sK[KEYS * 64], sV[KEYS * 64];
+    const int tid = threadIdx.x;
+    const int tile = blockIdx.x % nT, bh = blockIdx.x / nT;
+    const int h = bh % H, b = bh / H;
+    const int D = H * 64, ld = 3 * D;
+    const long r0 = q.start<TABLE>(b);
+    const int L = TABLE ? (int)min(max(q.start<TABLE>(b + 1) - r0, 0L), (long)q.len) : q.len;
+    if (tile * TILE >= L) return;                            // workgroup-uniform, before any barrier
+    const int row = tile * TILE + tid;
+    const bool live = row < L;
+    const float* base = qkv + r0 * ld + h * 64;
+    attn::F32Row r;
+    if (live) attn::f32_row_begin(r, base + (long)row * ld);
+    for (int k0 = 0; k0 < L; k0 += KEYS) {
+        const int n = min(KEYS, L - k0);
+        const float* kb = base + (long)k0 * ld;
+        for (int i = tid; i < n * 16; i += TILE) {
+            const int kr = i >> 4, c = i & 15;
+            *(float4_t*)(sK + kr * 64 + c * 4) = *(const float4_t*)(kb + D + (long)kr * ld + c * 4);
+            *(float4_t*)(sV + kr * 64 + c * 4) = *(const float4_t*)(kb + 2 * D + (long)kr * ld + c * 4);
+        }
+        __syncthreads();
+        if (live) attn::f32_row_keys(r, sK, sV, 0, n, scale);
+        __syncthreads();                                     // the block is read before the next one overwrites it
+    }
+    if (live) attn::f32_row_end(r, out + (r0 + row) * D + h * 64);
 }
 
 // Which kernel a launch of `variant` runs: 0 attn_f16_v0, 1 attn_f16_v1, 2 attn_f16_short, 3 attn_f16_v3, 5 attn_f16_v5
@@ -170,6 +214,16 @@ Kernel route(int variant, int L, int Lq, int causal) {
     if ((variant == 3 || variant == 5) && attn::v5_takes(L, Lq, causal)) return K_V5;
     if ((variant == 1 || variant == 3 || variant == 5) && attn::v1_wanted(L)) return K_V1;
     return K_V0;
+}
+
+// Which fp32 kernel a launch whose longest sequence has `len` rows runs.  `cap` is the largest length the caller lets through: 128 from
+// the debug hooks of attn_f32_small, option "agg_max_len" from the generator, OVMR_AGG_MAX_LEN_CEILING at the most.  Up to 128 rows the
+// launch is attn_f32_small's, as it always was; a longer one runs attn_f32_long for ALL its sequences, the short ones to the same bits.
+enum F32Kernel { F32_REFUSED, F32_SMALL, F32_LONG };
+
+F32Kernel route_f32(int len, int cap) {
+    if (len < 1 || len > cap || len > OVMR_AGG_MAX_LEN_CEILING) return F32_REFUSED;
+    return len <= attn::F32_SMALL_MAX ? F32_SMALL : F32_LONG;
 }
 
 }  // namespace
@@ -202,12 +256,34 @@ int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq,
     return (int)hipGetLastError();
 }
 
-int launch_attention_f32(const float* qkv, float* out, const AggSeqs& q, int H, hipStream_t s) {
+int launch_attention_f32(const float* qkv, float* out, const AggSeqs& q, int H, int max_len, hipStream_t s) {
     if (q.nseq <= 0 || q.M <= 0) return 0;
-    if (q.len < 1 || q.len > 128) return -2;
-    const size_t lds = (size_t)2 * q.len * 64 * sizeof(float);
-    const dim3 grid((unsigned)q.nseq * H);
-    if (q.offsets) hipLaunchKernelGGL(attn_f32_small<true>, grid, dim3(128), lds, s, qkv, out, q, H, 0.125f);
-    else hipLaunchKernelGGL(attn_f32_small<false>, grid, dim3(128), lds, s, qkv, out, q, H, 0.125f);
+    switch (route_f32(q.len, max_len)) {
+    case F32_REFUSED: return -2;
+    case F32_SMALL: {
+        const size_t lds = (size_t)2 * q.len * 64 * sizeof(float);
+        const dim3 grid((unsigned)q.nseq * H);
+        if (q.offsets) hipLaunchKernelGGL(attn_f32_small<true>, grid, dim3(128), lds, s, qkv, out, q, H, 0.125f);
+        else hipLaunchKernelGGL(attn_f32_small<false>, grid, dim3(128), lds, s, qkv, out, q, H, 0.125f);
+        return (int)hipGetLastError();
+    }
+    case F32_LONG: break;
+    }
+    return launch_attention_f32_long(qkv, out, q, H, s);
+}
+
+// attn_f32_long at any q.len up to the ceiling (the generator comes here through launch_attention_f32; ovmr_debug_attention_f32_long
+// directly, short launches included).  One workgroup per (sequence, head, 128-row query tile of the LONGEST sequence): the tiles of a
+// shorter one that start behind its end leave at once, so a 500-row class among a thousand short ones adds its own four tiles per
+// head and three empty ones per other (class, head), and nothing waits for it.
+int launch_attention_f32_long(const float* qkv, float* out, const AggSeqs& q, int H, hipStream_t s) {
+    if (q.nseq <= 0 || q.M <= 0) return 0;
+    if (q.len < 1 || q.len > OVMR_AGG_MAX_LEN_CEILING) return -2;
+    const int nT = (q.len + attn::F32_TILE - 1) / attn::F32_TILE;
+    const long wgs = (long)q.nseq * H * nT;
+    if (wgs > 0x7fffffffL) return -2;
+    const dim3 grid((unsigned)wgs), block(attn::F32_TILE);
+    if (q.offsets) hipLaunchKernelGGL(attn_f32_long<true>, grid, block, 0, s, qkv, out, q, H, nT, 0.125f);
+    else hipLaunchKernelGGL(attn_f32_long<false>, grid, block, 0, s, qkv, out, q, H, nT, 0.125f);
     return (int)hipGetLastError();
 }

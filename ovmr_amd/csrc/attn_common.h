@@ -142,38 +142,57 @@ __device__ __forceinline__ void store_row4(half_t* op, const float4_t (&o)[4], f
     }
 }
 
-// ---- the fp32 kernels (attention.hip: attn_f32_small, both modes) ---------------------------------------------------------
-// One query row against the L keys of its own (sequence, head), K and V in LDS as [key][64] fp32: keys in increasing order, s summed
-// over d in increasing order and then scaled, the online maximum, __expf, l and o updated in this order, one reciprocal at the end.
-// Both kernels go through this one function, and the library is built with -ffp-contract=off and without fast-math: a row's bits do
-// not depend on which kernel ran it, on L of any other sequence, or on where the row sits in the launch.
-__device__ __forceinline__ void f32_row(const float* __restrict__ qrow, const float* sK, const float* sV, int L, float scale,
-                                        float* __restrict__ orow) {
-    float qv[64], o[64];
+// ---- the fp32 kernels (attention.hip: attn_f32_small and attn_f32_long, both modes of each) -------------------------------------
+// One query row against the keys of its own (sequence, head), K and V of a key block in LDS as [key][64] fp32: keys in increasing
+// order, s summed over d in increasing order and then scaled, the online maximum, __expf, l and o updated in this order, one
+// reciprocal at the end.  The row is three steps over one state -- begin, keys (once per staged block, the blocks in key order), end
+// -- and every kernel goes through these three functions.  The library is built with -ffp-contract=off and without fast-math, so a row
+// walked over its keys 0 .. L - 1 gives the same bits whether the keys were staged in one block or in several: a row's bits do not
+// depend on which kernel ran it, on L of any other sequence, or on where the row sits in the launch.
+struct F32Row {
+    float qv[64], o[64], m, l;
+};
+__device__ __forceinline__ void f32_row_begin(F32Row& r, const float* __restrict__ qrow) {
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
         float4_t t = *(const float4_t*)(qrow + c * 4);
-        qv[c * 4] = t[0]; qv[c * 4 + 1] = t[1]; qv[c * 4 + 2] = t[2]; qv[c * 4 + 3] = t[3];
+        r.qv[c * 4] = t[0]; r.qv[c * 4 + 1] = t[1]; r.qv[c * 4 + 2] = t[2]; r.qv[c * 4 + 3] = t[3];
     }
 #pragma unroll
-    for (int d = 0; d < 64; ++d) o[d] = 0.f;
-    float m = -INFINITY, l = 0.f;
-    for (int key = 0; key < L; ++key) {
+    for (int d = 0; d < 64; ++d) r.o[d] = 0.f;
+    r.m = -INFINITY;
+    r.l = 0.f;
+}
+// the keys [k0, k1) of the block staged at sK / sV (m and l in locals over the loop: attn_f32_small then compiles to the
+// instructions it had when the row was one function)
+__device__ __forceinline__ void f32_row_keys(F32Row& r, const float* sK, const float* sV, int k0, int k1, float scale) {
+    float m = r.m, l = r.l;
+    for (int key = k0; key < k1; ++key) {
         float s = 0.f;
 #pragma unroll
-        for (int d = 0; d < 64; ++d) s += qv[d] * sK[key * 64 + d];
+        for (int d = 0; d < 64; ++d) s += r.qv[d] * sK[key * 64 + d];
         s *= scale;
         const float mn = fmaxf(m, s);
         const float alpha = __expf(m - mn), p = __expf(s - mn);
         l = l * alpha + p;
 #pragma unroll
-        for (int d = 0; d < 64; ++d) o[d] = o[d] * alpha + p * sV[key * 64 + d];
+        for (int d = 0; d < 64; ++d) r.o[d] = r.o[d] * alpha + p * sV[key * 64 + d];
         m = mn;
     }
-    const float inv = 1.0f / l;
+    r.m = m;
+    r.l = l;
+}
+__device__ __forceinline__ void f32_row_end(const F32Row& r, float* __restrict__ orow) {
+    const float inv = 1.0f / r.l;
 #pragma unroll
     for (int c = 0; c < 16; ++c)
-        *(float4_t*)(orow + c * 4) = (float4_t){o[c * 4] * inv, o[c * 4 + 1] * inv, o[c * 4 + 2] * inv, o[c * 4 + 3] * inv};
+        *(float4_t*)(orow + c * 4) = (float4_t){r.o[c * 4] * inv, r.o[c * 4 + 1] * inv, r.o[c * 4 + 2] * inv, r.o[c * 4 + 3] * inv};
 }
+
+// The shapes of the two kernels.  attn_f32_small holds a whole sequence's K and V in LDS: 128 rows are its 64 KiB.  attn_f32_long takes
+// 128 query rows per workgroup (a thread each) and stages 64 keys per block, 32 KiB: with a thousand short classes beside one long one
+// most workgroups of a launch are short or leave at once, and at 64 KiB two of them fill a CU's LDS (measured with 128-key blocks:
+// 10.8 against 8.7 ms).  The block size changes no bit: the keys are walked in the same order.
+constexpr int F32_SMALL_MAX = 128, F32_TILE = 128, F32_KEYS = 64;
 
 }  // namespace attn

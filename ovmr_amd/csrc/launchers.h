@@ -14,7 +14,9 @@ int launch_attention_f16_q(const half_t* qkv, half_t* out, int B, int L, int Lq,
 // up to 4 groups of sequences of at most 32 tokens in one launch (attention_short.hip); -100: not taken
 int launch_attention_f16_short(const half_t* qkv, half_t* out, int n_groups, const int* nseq, const int* L, const long* row0, int H,
                                int causal, hipStream_t s);
-int launch_attention_f32(const float* qkv, float* out, const AggSeqs& q, int H, hipStream_t s);   // attention.hip, attn_f32_small
+// attention.hip: attn_f32_small for q.len <= 128, attn_f32_long up to max_len (route_f32 there), -2 above it before any launch
+int launch_attention_f32(const float* qkv, float* out, const AggSeqs& q, int H, int max_len, hipStream_t s);
+int launch_attention_f32_long(const float* qkv, float* out, const AggSeqs& q, int H, hipStream_t s);   // attn_f32_long at any q.len
 int launch_im2col(const void* img, int img_is_f32, half_t* out, int B, int R, int P, int Kpad, hipStream_t s);
 int launch_fill_cls(half_t* x, const half_t* cls_pos, int B, int L, int W, hipStream_t s);
 int launch_l2norm_f16(half_t* x, int rows, int D, hipStream_t s);

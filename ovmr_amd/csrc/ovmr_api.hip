@@ -73,6 +73,7 @@ struct ovmr_handle {
     int enc_fold = 0;             // a remainder of at most this many images (one round of the narrowest GEMM grid) joins the last full sequence
     int img_cap = 0;              // images the workspace holds: max_images + enc_fold
     long agg_rows_cap = 0, logit_elems_cap = 0;
+    int agg_max_len = 128;             // option "agg_max_len": the most rows (n_ctx + shots) of one class
 };
 
 namespace {
@@ -337,7 +338,7 @@ int run_block_f32(ovmr_handle* h, const Block& k, float* x, float* y, float* qkv
     const int M = q.M, H = W / 64;
     CK(launch_layernorm(x, y, k.ln1_g, k.ln1_b, M, W, W, 1, s));
     CK(launch_gemm_f32(gemm(y, W, k.in_w, W, qkv, 3 * W, M, 3 * W, W, EPI_BIAS, k.in_b), s));
-    CK(launch_attention_f32(qkv, y, q, H, s));
+    CK(launch_attention_f32(qkv, y, q, H, h->agg_max_len, s));
     CK(launch_gemm_f32(gemm(y, W, k.out_w, W, x, W, M, W, W, EPI_BIAS_RES, k.out_b, x, W), s));
     CK(launch_layernorm(x, y, k.ln2_g, k.ln2_b, M, W, W, 1, s));
     CK(launch_gemm_f32(gemm(y, W, k.fc_w, W, hid, 4 * W, M, 4 * W, W, EPI_BIAS_QGELU, k.fc_b), s));
@@ -354,25 +355,30 @@ int generate_tokens(ovmr_handle* h, const half_t* feats, const int32_t* shots_ho
     const ovmr_model_desc& d = h->d;
     const int D = d.embed_dim;
     auto len = [&](int c) { return d.n_ctx + (int)(shots_host ? shots_host[c] : S); };
-    for (int c0 = 0, off0 = 0; c0 < Cb;) {
-        int c1 = c0, max_len = 0;
-        long rows = 0;
-        while (c1 < Cb && (c1 == c0 || rows + len(c1) <= h->agg_rows_cap)) {
-            rows += len(c1);
-            max_len = std::max(max_len, len(c1));
-            ++c1;
+    // two walks over the same plan: the first only checks that every chunk fits (a class longer than finalize sized the workspace
+    // for -- option "agg_max_len" raised afterwards -- is refused before anything of the call has launched), the second launches
+    for (int launch = 0; launch < 2; ++launch)
+        for (int c0 = 0, off0 = 0; c0 < Cb;) {
+            int c1 = c0, max_len = 0;
+            long rows = 0;
+            while (c1 < Cb && (c1 == c0 || rows + len(c1) <= h->agg_rows_cap)) {
+                rows += len(c1);
+                max_len = std::max(max_len, len(c1));
+                ++c1;
+            }
+            const AggWs ws(h, h->ws, (size_t)rows);
+            if (ws.bytes() > h->ws_bytes)
+                return fail(h, OVMR_E_SHAPE, "the %ld aggregator rows of class %d do not fit the workspace", rows, c0);
+            const int Cc = c1 - c0;
+            if (launch) {
+                const AggSeqs q{offsets_dev ? offsets_dev + c0 : nullptr, off0, Cc, d.n_ctx, max_len, (int)rows};
+                CK(launch_agg_input(h->cls_token, feats, R, ws.x, q, D, s));
+                for (auto& k : h->agg) CK(run_block_f32(h, k, ws.x, ws.y, ws.qkv, ws.hid, q, D, s));
+                CK(launch_agg_output(ws.x, tokens_f32 + (size_t)c0 * d.n_ctx * D, q, D, s));
+            }
+            c0 = c1;
+            off0 += (int)(rows - (long)Cc * d.n_ctx);
         }
-        const AggWs ws(h, h->ws, (size_t)rows);
-        if (ws.bytes() > h->ws_bytes)
-            return fail(h, OVMR_E_SHAPE, "the %ld aggregator rows of class %d do not fit the workspace", rows, c0);
-        const int Cc = c1 - c0;
-        const AggSeqs q{offsets_dev ? offsets_dev + c0 : nullptr, off0, Cc, d.n_ctx, max_len, (int)rows};
-        CK(launch_agg_input(h->cls_token, feats, R, ws.x, q, D, s));
-        for (auto& k : h->agg) CK(run_block_f32(h, k, ws.x, ws.y, ws.qkv, ws.hid, q, D, s));
-        CK(launch_agg_output(ws.x, tokens_f32 + (size_t)c0 * d.n_ctx * D, q, D, s));
-        c0 = c1;
-        off0 += (int)(rows - (long)Cc * d.n_ctx);
-    }
     return 0;
 }
 
@@ -589,6 +595,11 @@ int ovmr_set_option(ovmr_handle* h, const char* key, int value) {
     else if (!strcmp(key, "fused_head")) h->fused_head = value;
     else if (!strcmp(key, "head_max_grid")) h->head_max_grid = value;
     else if (!strcmp(key, "gelu_exact")) h->gelu_exact = value;
+    else if (!strcmp(key, "agg_max_len")) {
+        if (value < 128 || value > OVMR_AGG_MAX_LEN_CEILING)
+            return fail(h, OVMR_E_ARG, "agg_max_len %d outside [128,%d]", value, OVMR_AGG_MAX_LEN_CEILING);
+        h->agg_max_len = value;
+    }
     else return fail(h, OVMR_E_NAME, "unknown option '%s'", key);
     return 0;
 }
@@ -720,7 +731,8 @@ int ovmr_finalize(ovmr_handle* h, int max_images, int max_prompts, int max_class
         h->enc_fold = big ? (int)std::min<long>(round_images, max_images / 4) : 0;
         h->img_cap = max_images + h->enc_fold;
     }
-    h->agg_rows_cap = (long)max_classes * (d.n_ctx + 32);
+    // (the longest class the option lets through fits a chunk of its own; at the option's default the capacity is what it always was)
+    h->agg_rows_cap = std::max((long)max_classes * (d.n_ctx + 32), h->agg_max_len > 128 ? (long)h->agg_max_len : 0L);
     h->logit_elems_cap = 32L << 20;
     const size_t need = std::max({image_ws(h, nullptr, h->img_cap).bytes(), text_ws(h, nullptr, (size_t)max_prompts * d.context_length, max_prompts).bytes(),
                                   AggWs(h, nullptr, h->agg_rows_cap).bytes(), HeadWs(h, nullptr, 3).bytes()});
@@ -882,7 +894,7 @@ int ovmr_generate_tokens(ovmr_handle* h, const void* feats_f16, int Cb, int S, f
     if (int rc = need_finalized(h)) return rc;
     const ovmr_model_desc& d = h->d;
     const int D = d.embed_dim, La = d.n_ctx + S;
-    if (La > 128) return fail(h, OVMR_E_SHAPE, "n_ctx + shots = %d exceeds 128", La);
+    if (La > h->agg_max_len) return fail(h, OVMR_E_SHAPE, "n_ctx + shots = %d exceeds %d", La, h->agg_max_len);
     return generate_tokens(h, (const half_t*)feats_f16, nullptr, S, nullptr, Cb, Cb * S, tokens_f32, (hipStream_t)stream);
 }
 
@@ -896,8 +908,8 @@ int ovmr_generate_tokens_ragged(ovmr_handle* h, const void* feats_f16, const int
     long sum = 0;
     for (int c = 0; c < Cb; ++c) {
         if (shots_host[c] < 1) return fail(h, OVMR_E_SHAPE, "class %d of the call has %d exemplars, at least 1 is needed", c, (int)shots_host[c]);
-        if (d.n_ctx + (long)shots_host[c] > 128)
-            return fail(h, OVMR_E_SHAPE, "class %d of the call: n_ctx + shots = %ld exceeds 128", c, d.n_ctx + (long)shots_host[c]);
+        if (d.n_ctx + (long)shots_host[c] > h->agg_max_len)
+            return fail(h, OVMR_E_SHAPE, "class %d of the call: n_ctx + shots = %ld exceeds %d", c, d.n_ctx + (long)shots_host[c], h->agg_max_len);
         sum += shots_host[c];
     }
     if (sum != R) return fail(h, OVMR_E_SHAPE, "the shots add up to %ld rows, feats has %d", sum, R);
@@ -1212,7 +1224,7 @@ int ovmr_debug_gemm_patches(int variant, const void* image_f16, int R, const voi
 int ovmr_debug_attention(int f32, int variant, const void* qkv, void* out, int B, int L, int H, int causal,
                          ovmr_stream stream) {
     // fp32: B equal sequences are the arithmetic mode of the aggregator's sequence table
-    return f32 ? launch_attention_f32((const float*)qkv, (float*)out, AggSeqs{nullptr, 0, B, 0, L, B * L}, H, (hipStream_t)stream)
+    return f32 ? launch_attention_f32((const float*)qkv, (float*)out, AggSeqs{nullptr, 0, B, 0, L, B * L}, H, 128, (hipStream_t)stream)
                : launch_attention_f16((const half_t*)qkv, (half_t*)out, B, L, H, causal, variant, (hipStream_t)stream);
 }
 
@@ -1221,7 +1233,16 @@ int ovmr_debug_attention_f32_varlen(const void* qkv, void* out, const int32_t* o
     if (nseq < 0 || n_ctx < 0 || H < 1 || max_len < 1) return OVMR_E_ARG;
     // (no row count in this signature: the clamp bound is the most rows nseq sequences of max_len can be)
     return launch_attention_f32((const float*)qkv, (float*)out, AggSeqs{offsets_dev, 0, nseq, n_ctx, max_len, nseq * max_len}, H,
-                                (hipStream_t)stream);
+                                128, (hipStream_t)stream);
+}
+
+int ovmr_debug_attention_f32_long(const void* qkv, void* out, const int32_t* offsets_dev, int nseq, int n_ctx, int max_len, int H,
+                                  ovmr_stream stream) {
+    if (nseq < 0 || n_ctx < 0 || H < 1 || max_len < 1) return OVMR_E_ARG;
+    if (max_len > OVMR_AGG_MAX_LEN_CEILING || (long)nseq * max_len > 0x7fffffffL) return -2;
+    // uniform (offsets_dev == NULL): nseq sequences of max_len rows, n_ctx unused; table: the clamp bound as in the hook above
+    return launch_attention_f32_long((const float*)qkv, (float*)out, AggSeqs{offsets_dev, 0, nseq, n_ctx, max_len, nseq * max_len}, H,
+                                     (hipStream_t)stream);
 }
 
 int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L, int Lq, int H, int causal,

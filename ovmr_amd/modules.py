@@ -486,6 +486,9 @@ class _RaggedRows:
         m._ragged_n_label = n_label
 
 
+AGG_MAX_LEN_CEILING = 4096      # OVMR_AGG_MAX_LEN_CEILING (include/ovmr_hip.h): aggregator rows, n_ctx + shots, of one class
+
+
 class CustomCLIP(_TwoInFlight):
     """trainers/mm_classifier_one_prompt.py:179-364 (evaluation / classifier-generation branch)."""
 
@@ -508,6 +511,17 @@ class CustomCLIP(_TwoInFlight):
         self._dist = dist if distributed else None
         if reserve is None:
             reserve = (cfg.DATALOADER.TEST.BATCH_SIZE if hasattr(cfg.DATALOADER, "TEST") else 256, 256, 1024)
+        # NUM_SHOTS is the per-class ceiling in both layouts (what --ragged-shots caps a class at).  Beyond 128 aggregator rows per class
+        # the engine is told so BEFORE PromptLearner finalises it, so that its workspace holds such a class; up to 128 nothing is set and
+        # the engine is what it always was.
+        rows = cfg.TRAINER.COCOOP.N_CTX + int(cfg.DATASET.NUM_SHOTS)
+        if rows > AGG_MAX_LEN_CEILING:
+            raise ValueError(f"DATASET.NUM_SHOTS {cfg.DATASET.NUM_SHOTS}: n_ctx + NUM_SHOTS = {rows} aggregator rows per class, the engine "
+                             f"takes at most {AGG_MAX_LEN_CEILING} (NUM_SHOTS <= {AGG_MAX_LEN_CEILING - cfg.TRAINER.COCOOP.N_CTX})")
+        if rows > 128:
+            e = clip_model.engine(cfg.TRAINER.COCOOP.N_CTX)
+            if e._options.get("agg_max_len", 128) < rows:
+                e.set_option("agg_max_len", rows)
         self.prompt_learner = PromptLearner(cfg, classnames, clip_model, tokenizer, prompt_learner_state,
                                             compute_zero_shot=self._dist is None and not stream_text, reserve=reserve)
         self._text_streamed = bool(stream_text) or self._dist is not None

@@ -96,6 +96,7 @@ SIGNATURES = {
     "ovmr_debug_gemm_strided": (c_i, [c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_p, c_p,
                                       c_i, c_p]),
     "ovmr_debug_attention_f32_varlen": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
+    "ovmr_debug_attention_f32_long": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "ovmr_debug_attention_q": (c_i, [c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "ovmr_debug_attention_route": (c_i, [c_i, c_i, c_i, c_i]),
     "ovmr_debug_gemm_route": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i)]),
