@@ -29,7 +29,11 @@ trainers ignore EVAL_MODE.
 adds the reference's `=> per-class result` block (and `perclass_accuracy` in the results) and OUTPUT_DIR/cmat.pt, the row-normalised
 confusion matrix, to the test pass of any of the three trainers.  These two FLAGS are the switch: the reference's keys
 `TEST.PER_CLASS_RESULT` / `TEST.COMPUTE_CMAT` stay accepted and ignored.  They do not go with `--predict`.  Either way `main` is train.py's evaluation path,
-`trainer.build_trainer(cfg, dm, ...)` and `.test()` (ovmr_amd/trainer.py), on loaders of this runner's own.  It
+`trainer.build_trainer(cfg, dm, ...)` and `.test()` (ovmr_amd/trainer.py), on loaders of this runner's own.  Under
+`python -m torch.distributed.run --nproc-per-node N -m ovmr_amd.cli ...` (any of the three trainers; not `--predict`) the runner opens the process
+group, shards the classes over the ranks for the generation and the BATCHES of the test set for the test pass: every rank evaluates its own
+contiguous range of the one-process pass's batches, the evaluator's counters are summed over the ranks, rank 0 prints and writes -- the figures and
+files of the one-process job byte for byte -- and every rank returns the results plus `test_shard` (its rank, world, batch range, images).  It
 takes the command line of `scripts/mm_cls/generate_classifier.sh:30-44` / `train.py:183-255` as it is: `--dataset-config-file` and
 `--config-file` (YAML, read with PyYAML), the flags `reset_cfg` copies (`--root --output-dir --seed --trainer --backbone --init_weight
 --n_ctx --eval_mode --eval_tau`) and the trailing `KEY VALUE` opts, merged in train.py's order by `ovmr_amd.config.setup_cfg` with the
@@ -107,10 +111,16 @@ class FolderLoader:
 
     With world > 1 the loader is class-sharded: a rank keeps only the items whose class lies in its contiguous
     `shard_range` of the `num_classes` classes, so it opens and decodes only its own images; `presharded = True` then tells
-    CustomCLIP.forward_prompt that every batch it receives is its own."""
+    CustomCLIP.forward_prompt that every batch it receives is its own.
+
+    batch_shard=(rank, world) shards a TEST pass instead, independently of the above: the loader keeps the items of its contiguous range
+    of the one-process loader's batches (shard.shard_test_batches: same item order, same batch boundaries) and publishes `.batch_shard`
+    and `.batch_range` = [first, end) of those batches; `_EvalTrainer.test()` then sums the evaluator state over the ranks.  A rank whose
+    range is empty has a loader of zero batches."""
 
     def __init__(self, items: Sequence[Tuple[str, int]], batch_size: int, size: int, rank: int = 0, world: int = 1,
-                 num_classes: int = 0, interpolation: str = "bicubic", mean=PIXEL_MEAN, std=PIXEL_STD, ragged: bool = False):
+                 num_classes: int = 0, interpolation: str = "bicubic", mean=PIXEL_MEAN, std=PIXEL_STD, ragged: bool = False,
+                 batch_shard=None):
         """ragged: `items` is a ragged exemplar set (layout_exemplars_ragged).  A batch then holds whole classes, at most
         `batch_size` rows, and carries "shots" (host int64 [n_cls]); `.shots` is int32 [C], the rows of every class of the vocabulary."""
         self.bs, self.size = batch_size, size
@@ -124,7 +134,8 @@ class FolderLoader:
             from .shard import shard_range
             lo, hi = shard_range(num_classes or (1 + max(l for _, l in items)), rank, world)
             items = [it for it in items if lo <= it[1] < hi]
-        self.items = list(items)
+        from .shard import keep_batch_shard
+        self.items, self.batch_shard, self.batch_range = keep_batch_shard(list(items), int(batch_size), batch_shard, ragged)
         if ragged:
             from .shard import ragged_batches
             self.spans = ragged_batches(self.items, self.bs)
@@ -240,6 +251,7 @@ def read_exemplar_list(path: str, num_classes: int, shots: int) -> List[Tuple[st
 
 
 IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".gif", ".ppm", ".pgm", ".tif", ".tiff", ".webp")
+PREDICT_ONE_PROCESS = "--predict runs in one process: sharding the prediction pass over ranks is not implemented"
 MAX_TOPK = 32                 # ovmr_topk_rows (include/ovmr_hip.h)
 
 
@@ -398,21 +410,27 @@ def _check_model_matches_cfg(spec, cfg) -> None:
 
 
 def _init_process_group(args) -> bool:
-    """Launched by torch.distributed.run (scripts/generate_classifier.sh with several GPUs): one rank per GPU, process group nccl = RCCL;
-    forward_prompt then shards the classes over the ranks (two collectives) and rank 0 evaluates and writes.
+    """Launched by torch.distributed.run (scripts/generate_classifier.sh / eval_ovmr.sh with several GPUs): one rank per GPU, process group
+    nccl = RCCL; forward_prompt then shards the classes over the ranks (two collectives), every rank evaluates its own
+    batches of the test set, the evaluator state is summed over the ranks and rank 0 reports and writes.
     True when the group was opened here (and is this runner's to close); `args.device` becomes the rank's own GPU."""
     import torch
     import torch.distributed as dist
     own_group = False
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not dist.is_initialized():
+        if "RANK" not in os.environ:
+            raise SystemExit(f"WORLD_SIZE is {os.environ['WORLD_SIZE']} but RANK is not set: a job over several ranks is one process per GPU, "
+                             "each with its own RANK (torch.distributed.run sets them: scripts/eval_ovmr.sh)")
         local = int(os.environ.get("LOCAL_RANK", "0"))
         backend = os.environ.get("OVMR_DIST_BACKEND", "nccl")
         if backend == "nccl":
             args.device = f"cuda:{local}"
         torch.cuda.set_device(torch.device(args.device))
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        # ranks > 0 wait in the closing barrier while rank 0 evaluates the whole test set alone: the collective timeout has to cover a test
-        # pass, not a collective (the backend's default of 10 minutes would abort the waiting ranks, and the launcher then rank 0)
+        # a rank reaches the sum of the evaluator state, and the closing barrier, when ITS batches of the test pass are done, and waits there
+        # for the slowest rank: the collective timeout has to cover the skew between ranks over a test pass (a slower GPU, a cold page cache,
+        # one batch more), which nobody has measured -- it stays sized for a whole pass, not for a collective (the backend's default of 10
+        # minutes would abort the waiting ranks, and the launcher then the others)
         import datetime
         to = datetime.timedelta(seconds=float(os.environ.get("OVMR_DIST_TIMEOUT", 6 * 3600)))
         if backend == "nccl":
@@ -424,13 +442,16 @@ def _init_process_group(args) -> bool:
 
 
 def _loader_factory(args, cfg, size: int, tfm: dict):
-    """loader(items, batch, rank, world, n_classes): the pipelined loader, or with no decode workers the in-thread FolderLoader."""
+    """loader(items, batch, rank, world, n_classes, ragged=, batch_shard=): the pipelined loader, or with no decode workers the in-thread
+    FolderLoader."""
     workers = cfg.DATALOADER.NUM_WORKERS if args.workers is None else args.workers
     if workers <= 0:
-        return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False: FolderLoader(items, batch, size, rank, world, n_classes, ragged=ragged, **tfm)
+        return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False, batch_shard=None: FolderLoader(
+            items, batch, size, rank, world, n_classes, ragged=ragged, batch_shard=batch_shard, **tfm)
     from .loader import PipelinedFolderLoader
     kw = dict(workers=workers, prefetch=args.prefetch, device=args.device, fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
-    return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False: PipelinedFolderLoader(items, batch, size, rank, world, n_classes, ragged=ragged, **kw)
+    return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False, batch_shard=None: PipelinedFolderLoader(
+        items, batch, size, rank, world, n_classes, ragged=ragged, batch_shard=batch_shard, **kw)
 
 
 def _report_pipeline(results: dict, name: str, loader) -> None:
@@ -465,7 +486,7 @@ def main(argv=None) -> Dict[str, float]:
             if on:
                 raise SystemExit(f"{flag} belongs to the test pass: --predict ranks unlabelled images, there is nothing to count")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise SystemExit("--predict runs in one process: sharding the prediction pass over ranks is not implemented")
+            raise SystemExit(PREDICT_ONE_PROCESS)
         k = 5 if args.topk is None else args.topk
         if not 1 <= k <= MAX_TOPK:
             raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, number of classes)]")
@@ -482,8 +503,6 @@ def main(argv=None) -> Dict[str, float]:
         split_cfg = copy.deepcopy(cfg)
         split_cfg.DATASET.NUM_SHOTS = max(1, shots)       # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set)
     if zeroshot:
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise SystemExit(f"--trainer {cfg.TRAINER.NAME} runs in one process: sharding the zero-shot test pass over ranks is not implemented")
         try:
             templates.check_dataset(cfg.DATASET.NAME)
         except KeyError as e:
@@ -506,7 +525,10 @@ def main(argv=None) -> Dict[str, float]:
     from types import SimpleNamespace
     from . import checkpoint, modules, trainer
     from .tokenizer import BPETokenizer
-    own_group = not zeroshot and _init_process_group(args)
+    own_group = _init_process_group(args)
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
+    if predict and world > 1:                                 # (a group the caller opened: WORLD_SIZE > 1 was refused above)
+        raise SystemExit(PREDICT_ONE_PROCESS)
     if seed >= 0:
         print(f"Setting fixed seed: {seed}")                  # train.py:157-159
         torch.manual_seed(seed)
@@ -535,7 +557,6 @@ def main(argv=None) -> Dict[str, float]:
         else:
             print("Note that load_model() is skipped as no pretrained model is given")       # :464-466
         kw["prompt_learner_state"] = pl_state
-    rank, world = (dist.get_rank(), dist.get_world_size()) if not zeroshot and dist.is_available() and dist.is_initialized() else (0, 1)
     loader = _loader_factory(args, cfg, spec.image_resolution, tfm)
     if zeroshot or load_classifiers:
         eval_loader = None
@@ -548,10 +569,11 @@ def main(argv=None) -> Dict[str, float]:
         print(f"ragged exemplar set: {int(n.sum()):,} images of {len(n):,} classes, shots per class min {int(n[0])} / median {float(np.median(n)):g} / max {int(n[-1])}")
     else:
         eval_loader = loader(exemplars, batch // shots * shots, rank, world, len(classnames))
-    test_loader = loader(test_items, batch)
-    # the decode workers start while the engine takes the weights; on rank 0 one ring (sized for the larger batch) serves both loaders,
-    # ranks > 0 never touch the test set: theirs is sized for the exemplar batches alone
-    first = eval_loader if eval_loader is not None and (rank > 0 or eval_loader.bs > test_loader.bs) else test_loader
+    # the test pass is sharded by batches: every rank evaluates its contiguous range of the one-process pass's batches (shard.shard_test_batches)
+    test_loader = loader(test_items, batch, batch_shard=(rank, world) if world > 1 else None)
+    # the decode workers start while the engine takes the weights; one ring, sized for the larger batch, serves both loaders of a rank
+    # (a rank whose share of the test batches is empty decodes exemplars alone: its ring is sized for those)
+    first = eval_loader if eval_loader is not None and (len(test_loader) == 0 or eval_loader.bs > test_loader.bs) else test_loader
     if hasattr(first, "warm"):
         first.warm()
     dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
@@ -562,13 +584,9 @@ def main(argv=None) -> Dict[str, float]:
         tr.model.load_classifiers(args.classifiers)
     elif not zeroshot:
         # the reference does this inside the first forward (:341-342); up front it keeps the two loaders' statistics apart.  Rank 0's two
-        # files are written by a worker thread while the test set runs (CustomCLIP._write_files), joined at the end of test()
+        # files are written by a worker thread while the test set runs (CustomCLIP._write_files), joined at the end of test().  The
+        # classifiers are complete on every rank: each goes on to its own batches of the test set
         tr.model.forward_prompt(eval_loader, wait_files=False)
-        if rank > 0:                         # the classifiers are complete on every rank; rank 0 evaluates the test set and reports
-            if own_group:
-                dist.barrier()
-                dist.destroy_process_group()
-            return {}
     if predict:
         values, indices = tr.predict(test_loader, k)
         results = {"predictions": ranked_predictions(images, values, indices, classnames)}
@@ -582,7 +600,9 @@ def main(argv=None) -> Dict[str, float]:
         _report_pipeline(results, "exemplar set", eval_loader)
     _report_pipeline(results, "predict set" if predict else "test set", test_loader)
     results["classnames"] = classnames
-    if own_group:
+    if test_loader.batch_shard is not None:
+        results["test_shard"] = {"rank": rank, "world": world, "batches": list(test_loader.batch_range), "images": len(test_loader.items)}
+    if own_group:                                # (a rank that raised inside the pass never gets here: its peers end at the group's timeout)
         dist.barrier()
         dist.destroy_process_group()
     return results

@@ -36,12 +36,47 @@ class Classification:
     def reset(self):
         # int32 [3][C] = tp, n_pred, n_label, + one slot counting rows whose label is outside [0, C) (include/ovmr_hip.h: ovmr_eval_counts)
         self._counts = torch.zeros(3 * self.num_classes + 1, dtype=torch.int32, device=self.device)
-        self._topk = None                            # the `topk` of this pass, set by its first process()
+        self._topk = None                            # the `topk` of this pass, set by begin() or by its first process()
         self._hits = None                            # int32 [1], topk > 1: rows whose label is among their k best columns
-        # detail mode, allocated by the first process() of the pass (the matches depend on its topk)
+        # detail mode, allocated by begin() / the first process() of the pass (the matches depend on its topk)
         self._class_hits = None                      # int32 [C], per_class and topk > 1: such rows per label (at topk == 1 that is tp)
         self._cmat = None                            # int32 [C, C], confusion: rows per (label, top-1 prediction)
         self.confusion_counts = None                 # int64 [C, C] on the host, set by evaluate()
+
+    def begin(self, topk: int = 1):
+        """Allocates the state of a pass that uses `topk`, without a batch: what the first process() of a pass does by itself.  A pass
+        sharded over ranks calls it up front on every rank (trainer._EvalTrainer.test), so that a rank without a single batch enters
+        `all_reduce` with the tensors its peers hold."""
+        C = self.num_classes
+        topk = int(topk)
+        if not 1 <= topk <= min(32, C):
+            raise ValueError(f"topk {topk} outside [1, min(32, {C} classes)]")
+        if self._topk is not None:
+            raise ValueError(f"begin(topk={topk}) in a pass that began already (topk={self._topk}): reset() starts the next")
+        self._topk = topk
+        if topk > 1:
+            self._hits = torch.zeros(1, dtype=torch.int32, device=self.device)
+            if self.per_class:
+                self._class_hits = torch.zeros(C, dtype=torch.int32, device=self.device)
+        if self.confusion:
+            self._cmat = torch.zeros((C, C), dtype=torch.int32, device=self.device)
+
+    @staticmethod
+    def all_reduce(evaluators: Sequence["Classification"], dist) -> None:
+        """Sums the state of the evaluators of ONE pass over the process group `dist` (torch.distributed), in place: afterwards every rank
+        holds the job's counters.  The small counters of all of them travel in one all-reduce, each confusion matrix in one of its own
+        (shard.all_reduce_eval_state).  Every evaluator has begun its pass (begin(), or a first process()), with the same topk and the
+        same flags on every rank: the collectives' shapes then do not depend on what a rank counted."""
+        from .shard import all_reduce_eval_state
+        small, cmats = [], []
+        for ev in evaluators:
+            if ev._topk is None:
+                raise RuntimeError("Classification.all_reduce before begin(): a rank without a batch would enter the collective with fewer "
+                                   "tensors than its peers")
+            small += [t for t in (ev._counts, ev._hits, ev._class_hits) if t is not None]
+            if ev._cmat is not None:
+                cmats.append(ev._cmat)
+        all_reduce_eval_state(small, cmats, dist)
 
     @torch.no_grad()
     def process(self, mo: torch.Tensor, gt: torch.Tensor, topk: int = 1):
@@ -53,19 +88,11 @@ class Classification:
         C = self.num_classes
         if mo.dim() != 2 or mo.shape[1] != C or gt.shape[0] != mo.shape[0]:
             raise ValueError(f"outputs {tuple(mo.shape)} / labels {tuple(gt.shape)} do not fit {C} classes")
-        topk = int(topk)
-        if not 1 <= topk <= min(32, C):
-            raise ValueError(f"topk {topk} outside [1, min(32, {C} classes)]")
         if self._topk is None:
-            self._topk = topk
-            if topk > 1:
-                self._hits = torch.zeros(1, dtype=torch.int32, device=self.device)
-                if self.per_class:
-                    self._class_hits = torch.zeros(C, dtype=torch.int32, device=self.device)
-            if self.confusion:
-                self._cmat = torch.zeros((C, C), dtype=torch.int32, device=self.device)
-        elif topk != self._topk:
+            self.begin(topk)
+        elif int(topk) != self._topk:
             raise ValueError(f"process(topk={topk}) in a pass that began with topk={self._topk}: one pass uses one topk (reset() starts the next)")
+        topk = self._topk
         if self.device.type == "cpu":
             pred, ok = self._process_host(mo, gt)
             gt = gt.long()
@@ -121,7 +148,12 @@ class Classification:
             raise ValueError(f"{int(c[3 * C])} test label(s) outside [0, {C})")
         return c[:C], c[C:2 * C], c[2 * C:3 * C]
 
-    def evaluate(self, output_dir: Optional[str] = None) -> "OrderedDict[str, float]":
+    def evaluate(self, output_dir: Optional[str] = None, report: bool = True) -> "OrderedDict[str, float]":
+        """report=False: the figures alone -- nothing is printed and no file is written (ranks > 0 of a sharded pass, which hold the
+        job's counters after all_reduce and leave the reporting to rank 0)."""
+        say = print if report else (lambda *a, **k: None)
+        if not report:
+            output_dir = None
         tp_i, n_pred_i, n_label_i = self.counts()
         tp, n_pred, n_label = tp_i.double(), n_pred_i.double(), n_label_i.double()
         total = float(n_label.sum())
@@ -136,7 +168,7 @@ class Classification:
         res = OrderedDict(accuracy=acc, error_rate=100.0 - acc, macro_f1=macro_f1)
         self.per_class_accuracy = (100.0 * recall).tolist()
         self.per_class_f1 = (100.0 * f1).tolist()
-        print("=> result\n"
+        say("=> result\n"
               f"* total: {int(total):,}\n* correct: {correct:,}\n* accuracy: {acc:.1f}%\n"
               f"* error: {100.0 - acc:.1f}%\n* macro_f1: {macro_f1:.1f}%")       # the format parse_test_res.py greps for
         if output_dir:                                                    # evaluator.py:84-113 (csv module formats)
@@ -156,7 +188,7 @@ class Classification:
         if self.per_class:                                                # evaluator.py:140-163, its format byte for byte
             import numpy as np
             matches = tp_i if self._class_hits is None else self._class_hits.cpu().long()      # top-k matches when topk > 1 (:56-58, 69-73)
-            print("=> per-class result")
+            say("=> per-class result")
             accs = []
             for label in range(self.num_classes):
                 total_c, correct_c = int(n_label_i[label]), int(matches[label])
@@ -164,9 +196,9 @@ class Classification:
                     continue
                 acc_c = 100.0 * correct_c / total_c
                 accs.append(acc_c)
-                print(f"* class: {label} ({self.classnames[label]})\ttotal: {total_c:,}\tcorrect: {correct_c:,}\tacc: {acc_c:.1f}%")
+                say(f"* class: {label} ({self.classnames[label]})\ttotal: {total_c:,}\tcorrect: {correct_c:,}\tacc: {acc_c:.1f}%")
             mean_acc = float(np.mean(accs)) if accs else 0.0
-            print(f"* average: {mean_acc:.1f}%")
+            say(f"* average: {mean_acc:.1f}%")
             res["perclass_accuracy"] = mean_acc
         if self.confusion:                                                # evaluator.py:165-171
             C = self.num_classes

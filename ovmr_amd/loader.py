@@ -225,7 +225,9 @@ def _get_pool(key) -> _Pool:
 class PipelinedFolderLoader:
     """Iterable of {"img", "label"} dict batches over (path, label) items; see the module docstring.
 
-    With world > 1 the loader is class-sharded like cli.FolderLoader (`presharded = True`).  `stats` after an iteration:
+    With world > 1 the loader is class-sharded like cli.FolderLoader (`presharded = True`); batch_shard=(rank, world) keeps this rank's
+    contiguous range of the one-process loader's batches, as cli.FolderLoader does (`.batch_shard`, `.batch_range`; a loader of zero
+    batches iterates, warms and reports without starting a decode pool).  `stats` after an iteration:
     images, batches, wall_s, decode_wait_s (the caller blocked on the workers), decode_bound_fraction = decode_wait_s / wall_s (the
     share of the job the host spent waiting for JPEG decode: robust whatever streams the consumer uses), consumer_gpu_s (device time
     on the caller's CURRENT stream between a batch becoming available and the caller asking for the next one) and
@@ -239,7 +241,7 @@ class PipelinedFolderLoader:
     def __init__(self, items: Sequence[Tuple[str, int]], batch_size: int, size: int, rank: int = 0, world: int = 1,
                  num_classes: int = 0, workers: int = 8, prefetch: int = 3, device: str = "cuda:0", chunk: int = 8,
                  fast_decode: bool = False, interpolation: str = "bicubic", mean=PIXEL_MEAN, std=PIXEL_STD,
-                 device_resize: bool = True, raw_cap_bytes: int = 768 * 1024, ragged: bool = False):
+                 device_resize: bool = True, raw_cap_bytes: int = 768 * 1024, ragged: bool = False, batch_shard=None):
         """ragged: `items` is a ragged exemplar set (cli.layout_exemplars_ragged).  A batch then holds whole classes, at most
         `batch_size` rows, and carries "shots" (host int64 [n_cls]); `.shots` is int32 [C], the rows of every class of the vocabulary."""
         self.bs, self.size = int(batch_size), int(size)
@@ -253,7 +255,8 @@ class PipelinedFolderLoader:
             from .shard import shard_range
             lo, hi = shard_range(num_classes or (1 + max(l for _, l in items)), rank, world)
             items = [it for it in items if lo <= it[1] < hi]
-        self.items = list(items)
+        from .shard import keep_batch_shard
+        self.items, self.batch_shard, self.batch_range = keep_batch_shard(list(items), int(batch_size), batch_shard, ragged)
         if ragged:
             from .shard import ragged_batches
             self.spans = ragged_batches(self.items, self.bs)

@@ -11,6 +11,12 @@ independent until the cross-validation step:
     precedes it;
   * every rank runs the argmax counting for its own exemplar rows against all classes and ONE
     all-reduce sums the int32 [3,2,C] counters (n_pred[c] receives votes from other ranks' rows).
+
+The test pass shards by BATCHES (`shard_test_batches`): rank r evaluates a contiguous range of the batches of the one-process pass --
+same item order, same batch boundaries, so every output row is the one-process row bit for bit (a batch's size selects kernels and
+the head's implementation; an item split would move the boundaries) -- and counts them into its own evaluator state, integer
+counters whose sum over the ranks is the job's (`all_reduce_eval_state`: ONE all-reduce for the small counters of every evaluator
+of the pass, one per confusion matrix).
 """
 from __future__ import annotations
 
@@ -24,6 +30,30 @@ def shard_range(n: int, rank: int, world: int) -> Tuple[int, int]:
     base, rem = divmod(n, world)
     start = rank * base + min(rank, rem)
     return start, start + base + (1 if rank < rem else 0)
+
+
+def shard_test_batches(n_items: int, batch_size: int, rank: int, world: int) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+    """The split of a test pass: `n_items` items in batches of `batch_size` (the last one ragged), as one process walks them ->
+    ((first item, end item), (first batch, end batch)) of `rank`: the contiguous `shard_range` of the BATCHES, and the items those
+    batches hold.  A rank beyond the number of batches gets an empty range of both."""
+    n_batches = -(-n_items // batch_size)
+    first, end = shard_range(n_batches, rank, world)
+    return (min(first * batch_size, n_items), min(end * batch_size, n_items)), (first, end)
+
+
+def keep_batch_shard(items: list, batch_size: int, batch_shard, ragged: bool = False):
+    """What a loader's `batch_shard=(rank, world)` keeps of `items` -> (items of the rank's batches, (rank, world), [first, end) of its
+    batches); batch_shard None: (items, None, None).  Refused with a ragged exemplar set, whose batches hold whole classes and are
+    sharded by class."""
+    if batch_shard is None:
+        return items, None, None
+    if ragged:
+        raise ValueError("batch_shard= shards a test pass by batches: not with ragged=True (an exemplar set is sharded by class: rank=, world=)")
+    rank, world = (int(v) for v in batch_shard)
+    if not 0 <= rank < world:
+        raise ValueError(f"batch_shard=({rank}, {world}): the rank lies in [0, world)")
+    (a, b), span = shard_test_batches(len(items), batch_size, rank, world)
+    return items[a:b], (rank, world), span
 
 
 def shard_batches(num_batches: int, rank: int, world: int) -> List[int]:
@@ -121,3 +151,20 @@ def all_reduce_counts(counts: torch.Tensor, dist) -> torch.Tensor:
     c = _staged(counts, dist)
     dist.all_reduce(c)
     return c.to(counts.device)
+
+
+def all_reduce_eval_state(small: List[torch.Tensor], cmats: List[torch.Tensor], dist) -> None:
+    """Sums the evaluator state of a test pass over the ranks, IN PLACE.  `small`: the int32 counter vectors of every evaluator of the
+    pass (evaluator.Classification: _counts, _hits, _class_hits), concatenated into ONE all-reduce and split back; `cmats`: the int32
+    [C, C] confusion counts, one all-reduce each (a matrix is not copied into a concatenation).  Every rank passes the same number of
+    tensors with the same shapes, whatever it counted (Classification.begin); int32 sums over ranks are the one-process int32 sums."""
+    if small:
+        flat = _staged(torch.cat([t.reshape(-1) for t in small]), dist)
+        dist.all_reduce(flat)
+        for t, part in zip(small, flat.split([t.numel() for t in small])):
+            t.copy_(part.reshape(t.shape))
+    for m in cmats:
+        c = _staged(m, dist)
+        dist.all_reduce(c)
+        if c is not m:
+            m.copy_(c)

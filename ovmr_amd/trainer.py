@@ -109,6 +109,28 @@ class _EvalTrainer:
     def after_test(self):
         """What a trainer still owes once the last output has been counted."""
 
+    def output_modes(self):
+        """What `outputs` yields, known from the configuration before the first batch: ALL_MODES for [4, B, C] outputs (EVAL_MODE all: one
+        evaluator per mode), None for [B, C] outputs (one evaluator).  A pass sharded over ranks decides its evaluators from this -- a rank
+        without a batch has no output to look at."""
+        return ALL_MODES if getattr(self.cfg, "EVAL_MODE", None) == "all" else None
+
+    def _pass_group(self, data_loader):
+        """The process group a pass over `data_loader` is sharded over: torch.distributed when the loader carries `batch_shard` with more
+        than one rank, else None (every rank evaluates everything and nothing is reduced, as without a group).  A sharded loader without
+        the matching group is refused here, before the first batch: the figures would be those of a part of the test set."""
+        shard = getattr(data_loader, "batch_shard", None)
+        if shard is None or shard[1] <= 1:
+            return None
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError(f"the test loader holds the batches of rank {shard[0]} of {shard[1]} (batch_shard), but no torch.distributed "
+                               "process group is initialised: the result would cover a part of the test set")
+        if (dist.get_rank(), dist.get_world_size()) != tuple(shard):
+            raise RuntimeError(f"the test loader holds the batches of rank {shard[0]} of {shard[1]} (batch_shard), this process is rank "
+                               f"{dist.get_rank()} of {dist.get_world_size()}")
+        return dist
+
     # trainer.py:460-482 (DATASET.REGION_AUG False)
     @torch.no_grad()
     def test(self, split=None):
@@ -121,6 +143,7 @@ class _EvalTrainer:
             split = "test"
             data_loader = self.test_loader
         print(f"Evaluate on the *{split}* set")
+        dist = self._pass_group(data_loader)
         labels = collections.deque()                 # an output is handed over after later batches have been fetched (two in flight)
 
         def inputs():
@@ -132,8 +155,21 @@ class _EvalTrainer:
         topk = int(getattr(getattr(self.cfg, "TEST", None), "TOPK", 1))          # evaluator.process(mo, gt, topk), evaluator.py:50
         kw = {"topk": topk} if topk != 1 else {}
         per_mode = False
+        if dist is not None:
+            # sharded over ranks: the evaluators and their state exist before the loop, from the configuration, so that every rank calls the
+            # same collectives with the same shapes whatever it received -- also a rank with no batch at all
+            per_mode = self.output_modes() is not None
+            if per_mode and self.mode_evaluators is None:
+                self.mode_evaluators = [self._new_evaluator() for _ in ALL_MODES]
+            evaluators = self.mode_evaluators if per_mode else [self.evaluator]
+            for ev in evaluators:
+                ev.reset()
+                ev.begin(topk)
         for output in self.outputs(inputs()):
             label = labels.popleft()
+            if dist is not None and (output.dim() == 3) != per_mode:
+                raise RuntimeError(f"{type(self).__name__}.outputs yields {output.dim()}-dimensional outputs, output_modes() announced "
+                                   f"{'[4, B, C]' if per_mode else '[B, C]'}: the ranks of a sharded pass agree on their evaluators up front")
             if output.dim() == 3:                    # [4, B, C] (EVAL_MODE all): plane p is mode ALL_MODES[p]'s output, counted by evaluator p
                 if not per_mode:
                     per_mode = True
@@ -145,17 +181,23 @@ class _EvalTrainer:
                     ev.process(plane, label, **kw)
             else:
                 self.evaluator.process(output, label, **kw)
+        report = True
+        if dist is not None:
+            # each rank counted its own batches: after the sum every rank holds the job's counters (hence the same results); rank 0 reports
+            Classification.all_reduce(evaluators, dist)
+            report = dist.get_rank() == 0
         self.after_test()
         if not per_mode:
-            self.results = self.evaluator.evaluate(self.output_dir or None)
+            self.results = self.evaluator.evaluate(self.output_dir or None, report=report)
             return list(self.results.values())[0]
         # one result block and one set of files (OUTPUT_DIR/<mode>/) per mode, every key prefixed "<mode>/"; then the table's four rows
         self.results = OrderedDict()
         for mode, ev in zip(ALL_MODES, self.mode_evaluators):
-            print(f"=> eval mode: {mode}")
-            res = ev.evaluate(os.path.join(self.output_dir, mode) if self.output_dir else None)
+            if report:
+                print(f"=> eval mode: {mode}")
+            res = ev.evaluate(os.path.join(self.output_dir, mode) if self.output_dir else None, report=report)
             self.results.update((f"{mode}/{k}", v) for k, v in res.items())
-        for mode in ALL_MODES:
+        for mode in ALL_MODES if report else ():
             r = self.results
             print(f"=> {mode}: accuracy {r[mode + '/accuracy']:.1f}%, error {r[mode + '/error_rate']:.1f}%, macro_f1 {r[mode + '/macro_f1']:.1f}%")
         return list(self.results.values())[0]
@@ -269,6 +311,9 @@ class ZeroshotCLIP(_EvalTrainer):
 
     def outputs(self, inputs):
         return self.model.inference_batches(inputs)
+
+    def output_modes(self):
+        return None                                  # (the zero-shot trainers ignore EVAL_MODE: [B, C] logits whatever it says)
 
     def ranked(self, inputs, k):
         return self.model.predict_topk_batches(inputs, k)

@@ -10,7 +10,9 @@
 # RAGGED=1 passes --ragged-shots: every class uses exactly the exemplars it has, up to SHOTS, and none twice.
 # DRY_RUN=1 prints the command line instead of running it.
 # GPU_ID selects the device with HIP_VISIBLE_DEVICES; a comma-separated list starts one rank per GPU (torch.distributed.run, RCCL):
-# the classes are sharded over the ranks.
+# the classes are sharded over the ranks for the generation, and the batches of the test set for the test pass -- every rank evaluates its
+# own batches, the evaluator's counters are summed over the ranks, rank 0 reports and writes; figures and files are those of the one-GPU
+# run byte for byte.
 set -e
 if [ $# -lt 7 ]; then
     echo "usage: $0 DATASET SEED SUB_CLASSES N_CTX EVAL_MODE EVAL_TAU GPU_ID" >&2
