@@ -87,7 +87,8 @@ class Classification:
         One pass uses one topk."""
         C = self.num_classes
         if mo.dim() != 2 or mo.shape[1] != C or gt.shape[0] != mo.shape[0]:
-            raise ValueError(f"outputs {tuple(mo.shape)} / labels {tuple(gt.shape)} do not fit {C} classes")
+            raise ValueError(f"Classification.process: mo must be [B, {C}] ({C} classes) and gt [B], got mo {list(mo.shape)} and "
+                             f"gt {list(gt.shape)}")
         if self._topk is None:
             self.begin(topk)
         elif int(topk) != self._topk:

@@ -28,19 +28,26 @@ PIXEL_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 def preprocess_u8(u8: torch.Tensor, out: torch.Tensor = None, stream=None, mean=PIXEL_MEAN, std=PIXEL_STD) -> torch.Tensor:
-    """uint8 [B, R, R, 3] on the device -> normalised fp16 [B, 3, R, R] (ovmr_preprocess_u8).  mean=None: ToTensor only (no Normalize)."""
+    """uint8 [B, R, R, 3] on the device -> normalised fp16 [B, 3, R, R] (ovmr_preprocess_u8).  mean=None: ToTensor only (no Normalize).
+    Both tensors go to the library as they are: u8 contiguous uint8 on the GPU with square frames and R % 8 == 0; out, when given, fp16
+    [B, 3, R, R], contiguous, on the same device.  Anything else is a ValueError before the launch."""
     if mean is None:
         mean, std = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
     from . import runtime
-    lib = runtime.load_library()
-    assert u8.is_cuda and u8.dtype == torch.uint8 and u8.dim() == 4 and u8.shape[3] == 3 and u8.is_contiguous()
+    side = u8.shape[1] if isinstance(u8, torch.Tensor) and u8.dim() == 4 else None
+    runtime._want("preprocess_u8", "u8", u8, (None, side, side, 3))
     B, R = int(u8.shape[0]), int(u8.shape[1])
+    if R % 8:
+        runtime._refuse("preprocess_u8", "u8", "frames of a side that is a multiple of 8", f"{list(u8.shape)}")
+    runtime._want("preprocess_u8", "u8", u8, None, torch.uint8, "cuda", dense=True)
+    if out is not None:
+        runtime._want("preprocess_u8", "out", out, (B, 3, R, R), torch.float16, u8.device, dense=True)
+    lib = runtime.load_library()
     if out is None:
         out = torch.empty((B, 3, R, R), dtype=torch.float16, device=u8.device)
     mean, std = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
     s = stream if stream is not None else torch.cuda.current_stream(u8.device)
-    rc = lib.ovmr_preprocess_u8(ctypes.c_void_p(u8.data_ptr()), B, R, mean, std, ctypes.c_void_p(out.data_ptr()),
-                                ctypes.c_void_p(s.cuda_stream))
+    rc = lib.ovmr_preprocess_u8(runtime._ptr(u8), B, R, mean, std, runtime._ptr(out), ctypes.c_void_p(s.cuda_stream))
     if rc != 0:
         raise runtime.OvmrError(f"ovmr_preprocess_u8 failed with {rc}")
     return out

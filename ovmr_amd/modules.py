@@ -368,6 +368,7 @@ class _TwoInFlight:
         pending = collections.deque()                    # (output, event on its stream), oldest first: at most n - 1 while the next is enqueued
         k = 0
         for image in batches:
+            self.engine.check_image(image)               # refused before it is copied, staged or given a stream
             image = self.engine._dev(image)
             use = overlap if overlap is not None else image.shape[0] <= cap
             if not use or image.shape[0] > cap:
@@ -879,6 +880,7 @@ class CustomCLIP(_TwoInFlight):
         return min(self.OVERLAP_MAX_BATCH, 2 * getattr(self.engine, "_reserve", (256,))[0])
 
     def _forward_split(self, image):
+        self.engine.check_image(image)                       # refused before the batch is copied or the side stream is touched
         image = self.engine._dev(image)
         B, C = image.shape[0], len(self.tokenized_prompts)
         half = (B + 1) // 2

@@ -126,6 +126,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
 
 
 def _ptr(t: Optional[torch.Tensor]):
+    """The ONE place a tensor becomes an address for the library (the struct fields of encode_text_groups included; loader.preprocess_u8
+    and evaluator.Classification go through it too): tests/test_boundary_cpu.py patches it to learn which tensor stands behind an address."""
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
@@ -137,25 +139,76 @@ class OvmrError(RuntimeError):
     pass
 
 
+def _refuse(where: str, name: str, want: str, got: str):
+    raise ValueError(f"{where}: {name} must be {want}, got {got}")
+
+
+def _same_device(a: torch.device, b) -> bool:
+    if isinstance(b, str) and ":" not in b:                       # "cuda": any GPU
+        return a.type == b
+    b = torch.device(b)
+    return a.type == b.type and (a.index == b.index or a.index is None or b.index is None)
+
+
+def _want(where: str, name: str, t, shape=None, dtype=None, device=None, dense: bool = False, at_least: Optional[int] = None):
+    """The operand check of every wrapper, stated once: the library sees an address and a few integers, never a shape (include/ovmr_hip.h),
+    so what the integers promise is compared with the tensor here, before anything is copied, allocated or enqueued.  Metadata only --
+    shape, dtype, device, strides: no device memory is read and nothing synchronises.  shape: one entry per dimension, None = any extent;
+    at_least: the fewest elements.  dtype (one or a tuple), device and dense are for operands the library takes as they are (outputs,
+    accumulators, the evaluator's inputs); what Engine._dev repairs (host or numpy input, another dtype, a strided view) is left to it.
+    Raises ValueError naming the wrapper, the argument, what it must be and what it is."""
+    if not isinstance(t, (torch.Tensor, np.ndarray)):
+        _refuse(where, name, "a torch.Tensor or a numpy array", type(t).__name__)
+    got = tuple(t.shape)
+    if shape is not None and (len(got) != len(shape) or any(w is not None and int(w) != g for w, g in zip(shape, got))):
+        _refuse(where, name, "of shape [" + ", ".join("*" if w is None else str(int(w)) for w in shape) + "]", f"{list(got)}")
+    if at_least is not None and int(np.prod(got, dtype=np.int64)) < at_least:
+        _refuse(where, name, f"of at least {at_least} elements", f"{list(got)}")
+    if dtype is None and device is None and not dense:
+        return
+    if not isinstance(t, torch.Tensor):
+        _refuse(where, name, "a torch.Tensor (the library takes it as it is)", "a numpy array")
+    if dtype is not None and t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)):
+        _refuse(where, name, " / ".join(str(d) for d in (dtype if isinstance(dtype, tuple) else (dtype,))), str(t.dtype))
+    if device is not None and not _same_device(t.device, device):
+        _refuse(where, name, f"on {device}", f"a tensor on {t.device}")
+    if dense and not t.is_contiguous():
+        _refuse(where, name, "contiguous", f"strides {tuple(t.stride())} for shape {list(got)}")
+
+
+def _want_range(where: str, name: str, t, lo: int, hi: int, what: str):
+    """Values are checked on HOST operands only (as the EOT checks below): a device tensor would need a read-back, and stays the caller's
+    contract."""
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t)
+    if t.is_cuda or not t.numel() or t.is_floating_point():
+        return
+    mn, mx = (int(x) for x in torch.aminmax(t))
+    if mn < lo or mx >= hi:
+        _refuse(where, name, f"{what} in [{lo}, {hi})", f"values from {mn} to {mx}")
+
+
+def _want_rows(where: str, name: str, mo):
+    """outputs [B, C] of the evaluator's entry points: fp16 / fp32 on the GPU, taken as it is."""
+    _want(where, name, mo, (None, None), (torch.float16, torch.float32), "cuda")
+
+
 def topk_rows(mo: torch.Tensor, k: int, labels: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None):
     """ovmr_topk_rows on the current stream: mo [B, C] fp16 / fp32 on the GPU (rows may be strided: stride(1) == 1, stride(0) >= C, no
     copy) -> (values fp32 [B, k], indices int32 [B, k]), best first in the library's total order (include/ovmr_hip.h).  labels int64 [B]
     and hits int32 [1] (both on the GPU, together or not at all): hits[0] += rows whose label is among their k columns."""
-    lib = load_library()
-    if mo.dim() != 2 or not mo.is_cuda or mo.dtype not in (torch.float16, torch.float32):
-        raise ValueError(f"topk_rows takes a [B, C] fp16 / fp32 device tensor, got {tuple(mo.shape)} {mo.dtype} on {mo.device}")
+    _want_rows("topk_rows", "mo", mo)
     B, C = mo.shape
+    if (labels is None) != (hits is None):
+        raise ValueError("topk_rows takes labels and hits together or not at all")
+    if labels is not None:
+        _want("topk_rows", "labels", labels, (B,), torch.int64, mo.device, dense=True)
+        _want("topk_rows", "hits", hits, None, torch.int32, mo.device, at_least=1)
+    lib = load_library()
     if B > 1 and mo.stride(1) == 1 and mo.stride(0) < C:
         mo = mo.contiguous()                         # (an expanded row: not a row view of a matrix)
     elif C > 1 and mo.stride(1) != 1:
         mo = mo.contiguous()
-    if (labels is None) != (hits is None):
-        raise ValueError("topk_rows takes labels and hits together or not at all")
-    if labels is not None:
-        if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (B,)):
-            raise ValueError("labels must be a contiguous int64 [B] device tensor")
-        if not (hits.is_cuda and hits.dtype == torch.int32 and hits.numel() >= 1):
-            raise ValueError("hits must be an int32 device tensor")
     with torch.cuda.device(mo.device):
         values = torch.empty((B, int(k)), dtype=torch.float32, device=mo.device)
         indices = torch.empty((B, int(k)), dtype=torch.int32, device=mo.device)
@@ -172,18 +225,19 @@ def eval_detail(mo: torch.Tensor, labels: torch.Tensor, k: int, counts: torch.Te
     """ovmr_eval_detail on the current stream: mo [B, C] fp16 / fp32 on the GPU (stride(1) == 1, stride(0) >= C), labels int64 [B];
     counts int32 [3C + 1], hits int32 [1], class_hits int32 [C], cmat int32 [C, C] (the last three optional) accumulate
     (include/ovmr_hip.h)."""
-    lib = load_library()
-    if mo.dim() != 2 or not mo.is_cuda or mo.dtype not in (torch.float16, torch.float32) or (mo.shape[1] > 1 and mo.stride(1) != 1):
-        raise ValueError(f"eval_detail takes a [B, C] fp16 / fp32 device tensor with unit column stride, got {tuple(mo.shape)} {mo.dtype} "
-                         f"on {mo.device}")
+    _want_rows("eval_detail", "mo", mo)
     B, C = mo.shape
-    if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == (B,)):
-        raise ValueError("labels must be a contiguous int64 [B] device tensor")
-    for name, t, n in (("counts", counts, 3 * C + 1), ("hits", hits, 1), ("class_hits", class_hits, C), ("cmat", cmat, C * C)):
-        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
-            raise ValueError(f"{name} must be a contiguous int32 device tensor of {n} elements")
+    if C > 1 and mo.stride(1) != 1 or B > 1 and mo.stride(0) < C:
+        _refuse("eval_detail", "mo", f"rows of unit column stride, at least {C} elements apart", f"strides {tuple(mo.stride())}")
+    _want("eval_detail", "labels", labels, (B,), torch.int64, mo.device, dense=True)
     if counts is None:
         raise ValueError("eval_detail needs counts")
+    for name, t, n in (("counts", counts, 3 * C + 1), ("hits", hits, 1), ("class_hits", class_hits, C), ("cmat", cmat, C * C)):
+        if t is not None:
+            _want("eval_detail", name, t, None, torch.int32, mo.device, dense=True)
+            if t.numel() != n:
+                _refuse("eval_detail", name, f"of {n} elements", f"{list(t.shape)}")
+    lib = load_library()
     with torch.cuda.device(mo.device):
         ld = mo.stride(0) if B > 1 else max(C, mo.stride(0))
         rc = lib.ovmr_eval_detail(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, _ptr(labels), B, C, int(k), _ptr(counts),
@@ -245,6 +299,10 @@ class Engine:
 
     # ------------------------------------------------------------------ weights
     def set_weight(self, name: str, tensor):
+        """tensor: a real-valued torch.Tensor or numpy array of the weight's own shape (fp16 and fp32 go as they are, anything else as fp32)."""
+        _want(f"set_weight({name})", "tensor", tensor)
+        if (torch.from_numpy(tensor) if isinstance(tensor, np.ndarray) else tensor).is_complex():
+            _refuse(f"set_weight({name})", "tensor", "real-valued", str(tensor.dtype))
         t = self._dev(tensor)
         if t.dtype not in (torch.float16, torch.float32):
             t = t.float()
@@ -304,19 +362,43 @@ class Engine:
         return float(self.lib.ovmr_flops_per_prompt(self.h, seq_len))
 
     # ------------------------------------------------------------------ compute
+    # Every wrapper below checks its operands against the handle's geometry FIRST (_want: shapes, and dtype / device / strides of what the
+    # library takes as it is), then repairs layouts (_dev), allocates and launches: a refused call has copied and enqueued nothing.
+    def check_image(self, image, where: str = "encode_image"):
+        """image must be [B, 3, R, R] with R = spec.image_resolution (any dtype or layout; numpy and host tensors too).  For callers that
+        slice or stage a batch before they encode it (modules._TwoInFlight, CustomCLIP._forward_split)."""
+        R = self.spec.image_resolution
+        _want(where, "image", image, (None, 3, R, R))
+
+    def _want_ids(self, where: str, name: str, ids, shape):
+        _want(where, name, ids, shape)
+        _want_range(where, name, ids, 0, self.spec.vocab_size, "token ids")
+
     def encode_image(self, image: torch.Tensor, normalize: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """image [B, 3, R, R] (fp16 / fp32 go as they are, any other dtype as fp32) -> [B, embed_dim] fp16; out, when given: that tensor,
+        fp16, contiguous, on the engine's device."""
+        self.check_image(image)
+        B = int(image.shape[0])
+        if out is not None:
+            _want("encode_image", "out", out, (B, self.spec.embed_dim), torch.float16, self.device, dense=True)
         image = self._dev(image)
         if image.dtype not in (torch.float16, torch.float32):
             image = image.float()
-        B = image.shape[0]
         if out is None:
             out = torch.empty((B, self.spec.embed_dim), dtype=torch.float16, device=self.device)
         self._ck(self.lib.ovmr_encode_image(self.h, _ptr(image), F16 if image.dtype == torch.float16 else F32, B,
                                             _ptr(out), int(normalize), _stream()), "ovmr_encode_image")
         return out
 
+    def _want_prompts(self, where: str, prompts, index):
+        sp = self.spec
+        _want(where, "prompts", prompts, (None, sp.context_length, sp.transformer_width))
+        _want(where, "index", index, (prompts.shape[0],))
+
     def encode_text_embedded(self, prompts: torch.Tensor, index: torch.Tensor, seq_len: Optional[int] = None,
                              normalize: int = 0) -> torch.Tensor:
+        """prompts [N, context_length, transformer_width], index [N] (the read-out rows) -> [N, embed_dim] fp16."""
+        self._want_prompts("encode_text_embedded", prompts, index)
         sl_req = int(seq_len) if seq_len is not None else self.spec.context_length
         if isinstance(index, torch.Tensor) and not index.is_cuda and index.numel() and int(index.max()) >= sl_req:
             raise ValueError(f"seq_len {sl_req} does not reach the largest read-out index {int(index.max())}")
@@ -330,6 +412,8 @@ class Engine:
         return out
 
     def encode_text_ids(self, ids: torch.Tensor, seq_len: Optional[int] = None, normalize: int = 0) -> torch.Tensor:
+        """ids [N, context_length] (any integer dtype; host ids are held to [0, vocab_size)) -> [N, embed_dim] fp16."""
+        self._want_ids("encode_text_ids", "ids", ids, (None, self.spec.context_length))
         if seq_len is not None and isinstance(ids, torch.Tensor) and not ids.is_cuda and ids.numel():
             eot = int(ids.argmax(dim=-1).max())                 # EOT has the largest id (clip/model.py:831)
             if eot >= int(seq_len):
@@ -346,6 +430,12 @@ class Engine:
         """Several prompt families in ONE pass of the text tower (ovmr_encode_text_groups).  Each group is a dict with either
         `prompts` [N, context_length, W] + `index` [N] or `ids` [N, context_length], and `seq_len`, `normalize` as the
         single-group calls.  Returns one [N, embed_dim] fp16 tensor per group."""
+        for k, g in enumerate(groups):                       # every group is checked before the first one is copied
+            where = f"encode_text_groups (group {k})"
+            if g.get("ids") is not None:
+                self._want_ids(where, "ids", g["ids"], (None, self.spec.context_length))
+            else:
+                self._want_prompts(where, g.get("prompts"), g.get("index"))
         arr = (TextGroup * len(groups))()
         keep, outs = [], []
         for a, g in zip(arr, groups):
@@ -359,13 +449,13 @@ class Engine:
             if g.get("ids") is not None:
                 ids = self._dev(g["ids"], torch.int64)
                 keep.append(ids)
-                a.prompts_f16, a.ids, a.index, n = None, ids.data_ptr(), None, ids.shape[0]
+                a.prompts_f16, a.ids, a.index, n = None, _ptr(ids).value, None, ids.shape[0]
             else:
                 pr, ix = self._dev(g["prompts"], torch.float16), self._dev(g["index"], torch.int32)
                 keep += [pr, ix]
-                a.prompts_f16, a.ids, a.index, n = pr.data_ptr(), None, ix.data_ptr(), pr.shape[0]
+                a.prompts_f16, a.ids, a.index, n = _ptr(pr).value, None, _ptr(ix).value, pr.shape[0]
             out = torch.empty((n, self.spec.embed_dim), dtype=torch.float16, device=self.device)
-            a.n, a.seq_len, a.normalize, a.out_f16 = n, sl, int(g.get("normalize", 0)), out.data_ptr()
+            a.n, a.seq_len, a.normalize, a.out_f16 = n, sl, int(g.get("normalize", 0)), _ptr(out).value
             outs.append(out)
         self._ck(self.lib.ovmr_encode_text_groups(self.h, arr, len(groups), _stream()), "ovmr_encode_text_groups")
         return outs
@@ -374,25 +464,29 @@ class Engine:
         """The prompt-ensembled text classifier of ZeroshotCLIP2 (ovmr_encode_text_ensemble): ids [T, C, context_length], template-major
         -> [C, embed_dim] fp16.  seq_lens: T template lengths; None = each template's exact length (max EOT position + 1) when `ids` is a
         host tensor, the full context otherwise (no device read-back here)."""
+        self._want_ids("encode_text_ensemble", "ids", ids, (None, None, self.spec.context_length))
+        if isinstance(ids, np.ndarray):
+            ids = torch.from_numpy(ids)
         T, C = int(ids.shape[0]), int(ids.shape[1])
-        host = isinstance(ids, np.ndarray) or not ids.is_cuda
-        if host and ids.numel():
-            eot = torch.as_tensor(ids).argmax(dim=-1).amax(dim=1)          # EOT has the largest id (clip/model.py:831)
+        if seq_lens is not None and len(seq_lens) != T:
+            _refuse("encode_text_ensemble", "seq_lens", f"{T} lengths, one for each of the templates in ids {list(ids.shape)}", f"{len(seq_lens)}")
+        if not ids.is_cuda and ids.numel():
+            eot = ids.argmax(dim=-1).amax(dim=1)          # EOT has the largest id (clip/model.py:831)
             if seq_lens is None:
                 seq_lens = (eot + 1).tolist()
             elif any(int(e) >= int(s) for e, s in zip(eot.tolist(), seq_lens)):
                 raise ValueError(f"seq_lens {list(seq_lens)} do not reach the EOT tokens at {eot.tolist()}")
         sl = None
         if seq_lens is not None:
-            if len(seq_lens) != T:
-                raise ValueError(f"{len(seq_lens)} seq_lens for {T} templates")
-            sl = (ctypes.c_int32 * T)(*[int(s) for s in seq_lens])
+            sl = (ctypes.c_int32 * max(1, T))(*[int(s) for s in seq_lens])
         ids = self._dev(ids, torch.int64)
         out = torch.empty((C, self.spec.embed_dim), dtype=torch.float16, device=self.device)
         self._ck(self.lib.ovmr_encode_text_ensemble(self.h, _ptr(ids), T, C, sl, _ptr(out), _stream()), "ovmr_encode_text_ensemble")
         return out
 
     def embed_tokens(self, ids: torch.Tensor) -> torch.Tensor:
+        """ids [N, L] (host ids are held to [0, vocab_size)) -> [N, L, transformer_width] fp16."""
+        self._want_ids("embed_tokens", "ids", ids, (None, None))
         ids = self._dev(ids, torch.int64)
         N, L = ids.shape
         out = torch.empty((N, L, self.spec.transformer_width), dtype=torch.float16, device=self.device)
@@ -400,6 +494,8 @@ class Engine:
         return out
 
     def generate_tokens(self, feats: torch.Tensor) -> torch.Tensor:
+        """feats [Cb, S, embed_dim] -> tokens [Cb, n_ctx, embed_dim] fp32."""
+        _want("generate_tokens", "feats", feats, (None, None, self.spec.embed_dim))
         feats = self._dev(feats, torch.float16)
         Cb, S, D = feats.shape
         out = torch.empty((Cb, self.n_ctx, D), dtype=torch.float32, device=self.device)
@@ -407,7 +503,7 @@ class Engine:
         return out
 
     def generate_tokens_ragged(self, feats: torch.Tensor, shots) -> torch.Tensor:
-        """ovmr_generate_tokens_ragged: feats [R, D], class after class, class c owning shots[c] rows -> tokens [Cb, n_ctx, D] fp32, each
+        """ovmr_generate_tokens_ragged: feats [R, embed_dim], class after class, class c owning shots[c] rows -> tokens [Cb, n_ctx, D] fp32, each
         class bit-identical to generate_tokens on its rows alone.  `shots` is a HOST sequence (list, numpy array or CPU tensor): the
         library's host array and the kernels' device prefix sum are both built here from this ONE list, so they cannot disagree."""
         if isinstance(shots, torch.Tensor):
@@ -415,9 +511,8 @@ class Engine:
                 raise ValueError("shots must live on the host: the library plans its launches from them")
             shots = shots.tolist()
         shots = [int(n) for n in shots]
+        _want("generate_tokens_ragged", "feats", feats, (None, self.spec.embed_dim))
         feats = self._dev(feats, torch.float16)
-        if feats.dim() != 2:
-            raise ValueError(f"generate_tokens_ragged takes packed [R, D] features, got {tuple(feats.shape)}")
         Cb, (R, D) = len(shots), feats.shape
         host = (ctypes.c_int32 * max(1, Cb))(*shots)
         offsets = self._dev(np.concatenate([[0], np.cumsum(np.asarray(shots, dtype=np.int64))]).astype(np.int32))
@@ -427,6 +522,14 @@ class Engine:
         return out
 
     def assemble_prompts(self, base: torch.Tensor, labels: Optional[torch.Tensor], tokens: torch.Tensor) -> torch.Tensor:
+        """base [rows, context_length, transformer_width], tokens [Cb, n_ctx, transformer_width], labels [Cb] (the row of base each class
+        takes; host labels are held to base's rows) or None (row 0 for every class) -> [Cb, context_length, transformer_width] fp16."""
+        sp = self.spec
+        _want("assemble_prompts", "tokens", tokens, (None, self.n_ctx, sp.transformer_width))
+        _want("assemble_prompts", "base", base, (None, sp.context_length, sp.transformer_width), at_least=1)
+        if labels is not None:
+            _want("assemble_prompts", "labels", labels, (tokens.shape[0],))
+            _want_range("assemble_prompts", "labels", labels, 0, int(base.shape[0]), "rows of base")
         base = self._dev(base, torch.float16)
         tokens = self._dev(tokens, torch.float32)
         labels = None if labels is None else self._dev(labels, torch.int64)
@@ -438,14 +541,24 @@ class Engine:
 
     def xval_counts(self, feats: torch.Tensor, labels: torch.Tensor, clf: torch.Tensor,
                     tp: torch.Tensor, n_pred: torch.Tensor):
+        """feats [R, embed_dim], labels [R], clf [C, embed_dim]; tp and n_pred accumulate in place: int32, contiguous, on the engine's
+        device, at least C elements each."""
+        D = self.spec.embed_dim
+        _want("xval_counts", "feats", feats, (None, D))
+        _want("xval_counts", "labels", labels, (feats.shape[0],))
+        _want("xval_counts", "clf", clf, (None, D))
+        for name, x in (("tp", tp), ("n_pred", n_pred)):
+            _want("xval_counts", name, x, None, torch.int32, self.device, dense=True, at_least=int(clf.shape[0]))
         feats = self._dev(feats, torch.float16)
         labels = self._dev(labels, torch.int32)
         clf = self._dev(clf, torch.float16)
-        assert tp.dtype == torch.int32 and n_pred.dtype == torch.int32 and tp.is_contiguous() and n_pred.is_contiguous()
         self._ck(self.lib.ovmr_xval_counts(self.h, _ptr(feats), _ptr(labels), feats.shape[0], _ptr(clf), clf.shape[0],
                                            _ptr(tp), _ptr(n_pred), _stream()), "ovmr_xval_counts")
 
     def fusion_weights(self, counts: torch.Tensor, n_label: torch.Tensor, tau: float) -> torch.Tensor:
+        """counts [3, 2, C], n_label [C] -> [C, 3] fp32."""
+        _want("fusion_weights", "n_label", n_label, (None,))
+        _want("fusion_weights", "counts", counts, (3, 2, n_label.shape[0]))
         counts = self._dev(counts, torch.int32)
         n_label = self._dev(n_label, torch.int32)
         C = n_label.shape[0]
@@ -456,13 +569,19 @@ class Engine:
 
     def pack_rows(self, mm, v, t, tokens, labels, bound: int) -> torch.Tensor:
         """One rank's block of the sharded job's all-gather (ovmr_amd/shard.py pack_block, one launch): rows `labels` of the class-indexed
-        fp16 buffers mm / v / t [C, D] and tokens [C, n_ctx, D] + the label bits, [bound, 3 D + n_ctx D + 2] fp16."""
+        fp16 buffers mm / v / t [C, D] and tokens [C, n_ctx, D] + the label bits, [bound, 3 D + n_ctx D + 2] fp16.  The four buffers go to
+        the library as they are: fp16, contiguous, on the engine's device; labels [n], n <= bound."""
+        _want("pack_rows", "mm", mm, (None, None))
+        _want("pack_rows", "tokens", tokens, (mm.shape[0], None, mm.shape[1]))
+        _want("pack_rows", "labels", labels, (None,))
         n, (C, D), n_ctx = int(labels.shape[0]), mm.shape, tokens.shape[1]
         if n > bound:
             raise RuntimeError(f"this rank produced {n} classes, more than the bound {bound} every rank agreed on: the eval-set "
                                "loader yields more than TEST.BATCH_SIZE // NUM_SHOTS classes per batch")
-        for x in (mm, v, t, tokens):
-            assert x.dtype == torch.float16 and x.is_contiguous() and x.is_cuda
+        if D % 2:
+            _refuse("pack_rows", "mm", "of even width (the label takes two fp16 columns)", f"{list(mm.shape)}")
+        for name, x, shape in (("mm", mm, (C, D)), ("v", v, (C, D)), ("t", t, (C, D)), ("tokens", tokens, (C, n_ctx, D))):
+            _want("pack_rows", name, x, shape, torch.float16, self.device, dense=True)
         labels = self._dev(labels, torch.int64)
         block = torch.empty((bound, (3 + n_ctx) * D + 2), dtype=torch.float16, device=self.device)
         self._ck(self.lib.ovmr_pack_rows(_ptr(mm), _ptr(v), _ptr(t), _ptr(tokens), _ptr(labels), n, D, n_ctx, bound, _ptr(block), _stream()),
@@ -470,9 +589,9 @@ class Engine:
         return block
 
     def unpack_rows(self, gathered: torch.Tensor, C: int, D: int, n_ctx: int):
-        """The gathered blocks of all ranks -> (mm, v, t [C, D], tokens [C, n_ctx, D], seen int32 [C + 1]); one launch (each result owns its storage: they are saved to files)."""
+        """The gathered blocks of all ranks, [rows, (3 + n_ctx) D + 2] -> (mm, v, t [C, D], tokens [C, n_ctx, D], seen int32 [C + 1]); one launch (each result owns its storage: they are saved to files)."""
+        _want("unpack_rows", "gathered", gathered, (None, (3 + n_ctx) * D + 2))
         gathered = self._dev(gathered, torch.float16)
-        assert gathered.shape[1] == (3 + n_ctx) * D + 2
         z = dict(dtype=torch.float16, device=self.device)                                      # (a class no rank sent stays zero; seen says so)
         mm, v, t, tokens = torch.zeros((C, D), **z), torch.zeros((C, D), **z), torch.zeros((C, D), **z), torch.zeros((C, n_ctx, D), **z)
         seen = torch.zeros(C + 1, dtype=torch.int32, device=self.device)
@@ -480,29 +599,54 @@ class Engine:
                                            _stream()), "ovmr_unpack_rows")
         return mm, v, t, tokens, seen
 
+    def _want_head(self, where: str, feats, clf, w) -> tuple:
+        """feats [B, embed_dim]; the classifiers that are given [C, embed_dim], one C for all; w [C, 3] when given.  Returns (B, C)."""
+        D = self.spec.embed_dim
+        _want(where, "feats", feats, (None, D))
+        given = [(n, x) for n, x in clf if x is not None]
+        if not given:
+            _refuse(where, "mm / v / t", "at least one classifier", "None for all three")
+        _want(where, given[0][0], given[0][1], (None, D))
+        C = int(given[0][1].shape[0])
+        for n, x in given[1:]:
+            _want(where, n, x, (C, D))
+        if w is not None:
+            _want(where, "w", w, (C, 3))
+        return int(feats.shape[0]), C
+
     def fused_logits(self, feats, mm, v, t, w, mode: str = "fusion", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """feats [B, embed_dim]; mm / v / t [C, embed_dim] (None where the mode does not read one); w [C, 3] or None -> [B, C] fp32; out,
+        when given: that tensor, fp32, contiguous, on the engine's device."""
+        B, C = self._want_head("fused_logits", feats, (("mm", mm), ("v", v), ("t", t)), w)
+        if out is not None:
+            _want("fused_logits", "out", out, (B, C), torch.float32, self.device, dense=True)
         feats = self._dev(feats, torch.float16)
         cl = [None if x is None else self._dev(x, torch.float16) for x in (mm, v, t)]
         w = None if w is None else self._dev(w, torch.float32)
-        C = next(x.shape[0] for x in cl if x is not None)
         if out is None:
-            out = torch.empty((feats.shape[0], C), dtype=torch.float32, device=self.device)
-        assert out.shape == (feats.shape[0], C) and out.dtype == torch.float32 and out.is_contiguous()
-        self._ck(self.lib.ovmr_fused_logits(self.h, _ptr(feats), feats.shape[0], _ptr(cl[0]), _ptr(cl[1]), _ptr(cl[2]),
+            out = torch.empty((B, C), dtype=torch.float32, device=self.device)
+        self._ck(self.lib.ovmr_fused_logits(self.h, _ptr(feats), B, _ptr(cl[0]), _ptr(cl[1]), _ptr(cl[2]),
                                             _ptr(w), C, MODES[mode], _ptr(out), _stream()), "ovmr_fused_logits")
         return out
 
     def fused_logits_all(self, feats, mm, v, t, w, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The four eval modes of one batch from one pass over the head (ovmr_fused_logits_all): [4, B, C] fp32 in ALL_MODES order, plane p
-        bit-equal to fused_logits(mode = ALL_MODES[p]).  `out` may be a row slice big[:, r0:r1] of a contiguous [4, Btot, C] tensor."""
+        bit-equal to fused_logits(mode = ALL_MODES[p]).  feats [B, embed_dim], mm / v / t [C, embed_dim], w [C, 3], all required.  `out`
+        may be a row slice big[:, r0:r1] of a contiguous [4, Btot, C] tensor: fp32 on the engine's device, dense [B, C] planes."""
+        for name, x in (("mm", mm), ("v", v), ("t", t), ("w", w)):
+            if x is None:
+                _refuse("fused_logits_all", name, "given (all three classifiers and w are read)", "None")
+        B, C = self._want_head("fused_logits_all", feats, (("mm", mm), ("v", v), ("t", t)), w)
+        if out is not None:
+            _want("fused_logits_all", "out", out, (4, B, C), torch.float32, self.device)
+            if B and not (out.stride(2) == 1 and out.stride(1) == C and out.stride(0) >= B * C):
+                _refuse("fused_logits_all", "out", f"dense [{B}, {C}] planes, at least {B * C} elements apart",
+                        f"strides {tuple(out.stride())}")
         feats = self._dev(feats, torch.float16)
         mm, v, t = (self._dev(x, torch.float16) for x in (mm, v, t))
         w = self._dev(w, torch.float32)
-        B, C = feats.shape[0], mm.shape[0]
         if out is None:
             out = torch.empty((4, B, C), dtype=torch.float32, device=self.device)
-        assert out.shape == (4, B, C) and out.dtype == torch.float32 and out.is_cuda
-        assert B == 0 or (out.stride(2) == 1 and out.stride(1) == C and out.stride(0) >= B * C), "dense [B, C] planes, a plane stride apart"
         self._ck(self.lib.ovmr_fused_logits_all(self.h, _ptr(feats), B, _ptr(mm), _ptr(v), _ptr(t), _ptr(w), C, _ptr(out),
                                                 out.stride(0) if B else 0, _stream()), "ovmr_fused_logits_all")
         return out
@@ -512,11 +656,17 @@ class Engine:
         return int(self.lib.ovmr_head_plan(self.h, int(B), int(C)))
 
     def zeroshot_logits(self, feats, text_feats, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """feats [B, embed_dim], text_feats [C, embed_dim] -> [B, C] fp16; out, when given: that tensor, fp16, contiguous, on the engine's
+        device."""
+        D = self.spec.embed_dim
+        _want("zeroshot_logits", "feats", feats, (None, D))
+        _want("zeroshot_logits", "text_feats", text_feats, (None, D))
+        B, C = int(feats.shape[0]), int(text_feats.shape[0])
+        if out is not None:
+            _want("zeroshot_logits", "out", out, (B, C), torch.float16, self.device, dense=True)
         feats = self._dev(feats, torch.float16)
         text_feats = self._dev(text_feats, torch.float16)
         if out is None:
-            out = torch.empty((feats.shape[0], text_feats.shape[0]), dtype=torch.float16, device=self.device)
-        assert out.shape == (feats.shape[0], text_feats.shape[0]) and out.dtype == torch.float16 and out.is_contiguous()
-        self._ck(self.lib.ovmr_zeroshot_logits(self.h, _ptr(feats), feats.shape[0], _ptr(text_feats), text_feats.shape[0],
-                                               _ptr(out), _stream()), "ovmr_zeroshot_logits")
+            out = torch.empty((B, C), dtype=torch.float16, device=self.device)
+        self._ck(self.lib.ovmr_zeroshot_logits(self.h, _ptr(feats), B, _ptr(text_feats), C, _ptr(out), _stream()), "ovmr_zeroshot_logits")
         return out
