@@ -50,6 +50,22 @@ are used otherwise).  The exemplar (eval) set is NUM_SHOTS images per class fold
 under `--seed` exactly as the reference's generate_fewshot_dataset draws them, the test set is every image of `--test-split`
 (default "val").
 
+Vocabulary edits (MM_CLS_OP only; DESIGN.md section 6, ovmr_amd/bank.py):
+
+    python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --save-bank
+    python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --bank OLD/reference_bank.pt --output-dir NEW \\
+        [--remove-classes NAME [NAME ...]] [--replace-classes DIR] [--add-classes DIR] [--predict IMAGES | the test pass]
+
+`--save-bank` makes a generation job also write OUTPUT_DIR/reference_bank.pt (vocabulary, exemplar features and their paths, classifiers,
+tokens, counters, fusion weights).  `--bank FILE` starts from such a file instead of generating: no exemplar is decoded; with `--predict`
+neither `--root` nor a data-set folder is needed (the class names come from the bank), with a test pass the data set's class names must
+equal the bank's (after the edits), in order.  `--add-classes DIR` / `--replace-classes DIR`: one sub-folder of images per class (sorted
+folder order = append order; names from DIR/classnames.txt, else the folder name; a replaced folder must name an existing class), its
+exemplars drawn under `--seed` and DATASET.NUM_SHOTS as for a data set (`--ragged-shots`: the ragged layout).  `--remove-classes` takes
+class names (put another flag, not the KEY VALUE opts, behind the list).  The edits apply in the order remove, replace, add; only the
+named classes are decoded and generated.  The edited model writes mm_classifiers.pt, visual_tokens.pt and reference_bank.pt into
+OUTPUT_DIR and goes on to the test pass or `--predict`.  One process only.
+
 Input pipeline (ovmr_amd/loader.py): `--workers` processes DECODE into a page-locked shared ring, a side stream uploads a batch and runs
 ovmr_resize_crop_u8 (Resize + CenterCrop, bit-equal to PIL) and ovmr_preprocess_u8 (normalise + fp16) on the GPU while the encoder
 works on the previous one; `--host-resize` keeps the resize in the workers.  JPEG decode on the host's cores remains the bound of the
@@ -348,6 +364,16 @@ def parse(argv=None):
     ap.add_argument("--topk", type=int, default=None, metavar="K", help="classes per image of --predict, best first (default 5; 1 <= K <= min(32, classes))")
     ap.add_argument("--classifiers", metavar="FILE", default="", help="with --predict --trainer MM_CLS_OP: load this mm_classifiers.pt instead of "
                     "generating the classifiers (no exemplar is decoded, no model file is written)")
+    ap.add_argument("--save-bank", action="store_true", help="MM_CLS_OP generation: also write OUTPUT_DIR/reference_bank.pt (ovmr_amd/bank.py), "
+                    "the state a later --bank run starts from; one process only")
+    ap.add_argument("--bank", metavar="FILE", default="", help="MM_CLS_OP: start from this reference bank instead of generating (no exemplar is "
+                    "decoded; with --predict no --root is needed)")
+    ap.add_argument("--add-classes", metavar="DIR", default="", help="with --bank: append the classes of DIR (one sub-folder of images per class, "
+                    "sorted; names from DIR/classnames.txt, else the folder name)")
+    ap.add_argument("--replace-classes", metavar="DIR", default="", help="with --bank: new exemplars for existing classes (layout as --add-classes; "
+                    "every folder must name a class of the bank)")
+    ap.add_argument("--remove-classes", metavar="NAME", nargs="+", default=None, help="with --bank: drop these classes (edits apply in the order "
+                    "remove, replace, add)")
     ap.add_argument("--per-class-result", action="store_true", help="the test pass also prints the reference's `=> per-class result` block and "
                     "reports perclass_accuracy (the reference's TEST.PER_CLASS_RESULT; counted on the GPU by ovmr_eval_detail)")
     ap.add_argument("--confusion-matrix", action="store_true", help="the test pass also writes OUTPUT_DIR/cmat.pt, the row-normalised confusion "
@@ -391,6 +417,67 @@ def build_splits(cfg, eval_split: str = "train", test_split: str = "val", exempl
         raise SystemExit(f"{len(folders) - len(kept)} class folder(s) of {eval_split!r} hold no exemplar image")
     classnames = [all_names[y] for y in kept]                 # lab2cname of the relabelled train_x (base_dataset.py get_lab2cname)
     return classnames, layout_exemplars_ragged(few, shots) if ragged else layout_exemplars(few, shots, seed), test_items
+
+
+def list_edit_classes(directory: str, shots: int, seed: int, ragged: bool = False, flag: str = "--add-classes"):
+    """The classes of an `--add-classes` / `--replace-classes` folder: one sub-folder of images per class, sorted folder order = the
+    loader's labels 0 ... K - 1; names from DIR/classnames.txt (read_classnames), else the folder name.  Every class's exemplars are drawn
+    with fewshot_items and laid out with layout_exemplars (or layout_exemplars_ragged), under `seed` and `shots`, exactly as build_splits
+    does for a data set.  Returns (class names, exemplar items in loader order)."""
+    if not osp.isdir(directory):
+        raise SystemExit(f"{flag} {directory!r}: no such directory")
+    folders = sorted(f.name for f in os.scandir(directory) if f.is_dir() and not f.name.startswith("."))
+    if not folders:
+        raise SystemExit(f"{flag} {directory!r}: no class folder below this directory")
+    items = []
+    for label, folder in enumerate(folders):
+        names = sorted(n for n in os.listdir(osp.join(directory, folder)) if not n.startswith("."))
+        if not names:
+            raise SystemExit(f"{flag} {directory!r}: class folder {folder!r} holds no image")
+        items += [(osp.join(directory, folder, n), label) for n in names]
+    few = fewshot_items(items, shots, seed)
+    return read_classnames(directory, folders), layout_exemplars_ragged(few, shots) if ragged else layout_exemplars(few, shots, seed)
+
+
+def plan_vocabulary_edits(args, bank_names: Sequence[str], shots: int, seed: int, ragged: bool):
+    """What `--remove-classes / --replace-classes / --add-classes` ask for, checked against the bank's class names before the model
+    exists: ([names to remove], (names, items) to replace or None, (names, items) to add or None, the final class names)."""
+    names = list(bank_names)
+    remove = list(args.remove_classes or [])
+    for n in remove:
+        if n not in names:
+            raise SystemExit(f"--remove-classes: the bank has no class {n!r}")
+        if remove.count(n) > 1:
+            raise SystemExit(f"--remove-classes: class {n!r} is named twice")
+    names = [n for n in names if n not in remove]
+    if not names:
+        raise SystemExit("--remove-classes: removing every class leaves no vocabulary")
+    replace = add = None
+    if args.replace_classes:
+        replace = list_edit_classes(args.replace_classes, shots, seed, ragged, "--replace-classes")
+        for n in replace[0]:
+            if n not in names:
+                raise SystemExit(f"--replace-classes {args.replace_classes!r}: the bank has no class {n!r}"
+                                 + (" left (it is removed in the same run)" if n in remove else ""))
+    if args.add_classes:
+        add = list_edit_classes(args.add_classes, shots, seed, ragged, "--add-classes")
+        for n in add[0]:
+            if n in names or add[0].count(n) > 1:
+                raise SystemExit(f"--add-classes {args.add_classes!r}: class {n!r} is in the vocabulary already")
+        names = names + list(add[0])
+    return remove, replace, add, names
+
+
+def _label_order_paths(items):
+    """The paths of exemplar items class after class in label order, a class's rows in loader order: the rows of a bank's `features`."""
+    return [p for p, _ in sorted(items, key=lambda it: it[1])]
+
+
+def _paths_per_class(items, K: int):
+    per = [[] for _ in range(K)]
+    for p, l in items:
+        per[l].append(p)
+    return per
 
 
 BACKBONES = {"ViT-B/16": (768, 16, 12), "ViT-B/32": (768, 32, 12), "ViT-L/14": (1024, 14, 24), "ViT-L/14@336px": (1024, 14, 24)}   # clip/clip.py:32-40 (ViT entries)
@@ -478,6 +565,20 @@ def main(argv=None) -> Dict[str, float]:
                          "ZeroshotCLIP | ZeroshotCLIP2` (zero-shot evaluation) are on the hot path")
     shots, batch, seed = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE, cfg.SEED
     split_cfg = cfg
+    edits = bool(args.add_classes or args.replace_classes or args.remove_classes)
+    if edits and not args.bank:
+        raise SystemExit("--add-classes / --replace-classes / --remove-classes edit a reference bank: give --bank FILE")
+    if zeroshot and (args.bank or args.save_bank):
+        raise SystemExit(f"--bank / --save-bank: --trainer {cfg.TRAINER.NAME} has no generated vocabulary to bank (MM_CLS_OP only; a zero-shot "
+                         "vocabulary is a text call away)")
+    if (args.bank or args.save_bank) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--bank / --save-bank run in one process: a sharded rank holds only its own classes' exemplar features")
+    if args.bank and args.save_bank:
+        raise SystemExit("--save-bank belongs to a generation job: a --bank run writes OUTPUT_DIR/reference_bank.pt whenever it edits")
+    if args.bank and args.classifiers:
+        raise SystemExit("--bank holds the classifiers already: not together with --classifiers")
+    if args.bank and not osp.isfile(args.bank):
+        raise SystemExit(f"--bank {args.bank!r}: no such file")
     predict, images, k = args.predict is not None, [], None
     if predict and cfg.EVAL_MODE == "all" and not zeroshot:
         raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
@@ -498,7 +599,11 @@ def main(argv=None) -> Dict[str, float]:
     elif args.topk is not None or args.classifiers:
         raise SystemExit("--topk / --classifiers belong to --predict PATH (the test pass takes TEST.TOPK)")
     load_classifiers = predict and bool(args.classifiers)
-    if zeroshot or load_classifiers:
+    from_bank = bool(args.bank)
+    if from_bank and edits and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
+        print(f"Oops! The results exist at {cfg.OUTPUT_DIR} (so skip this job)")           # generate_classifier.sh:27-28
+        return {}
+    if zeroshot or load_classifiers or from_bank:
         import copy
         split_cfg = copy.deepcopy(cfg)
         split_cfg.DATASET.NUM_SHOTS = max(1, shots)       # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set)
@@ -508,8 +613,8 @@ def main(argv=None) -> Dict[str, float]:
         except KeyError as e:
             raise SystemExit(e.args[0]) from None
         # (nothing of the few-shot draw is decoded)
-    elif not load_classifiers:
-        if osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
+    elif not load_classifiers and not (from_bank and not edits):
+        if not from_bank and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
             print(f"Oops! The results exist at {cfg.OUTPUT_DIR} (so skip this job)")       # generate_classifier.sh:27-28
             return {}
         if shots < 1:
@@ -533,7 +638,24 @@ def main(argv=None) -> Dict[str, float]:
         print(f"Setting fixed seed: {seed}")                  # train.py:157-159
         torch.manual_seed(seed)
     ragged = bool(args.ragged_shots) and not zeroshot and not load_classifiers
-    classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if predict else args.test_split, args.exemplar_list, ragged)
+    bank_obj = plan = None
+    if from_bank:
+        from . import bank as bank_format
+        try:
+            bank_obj = bank_format.read(args.bank)            # (checked against the model by load_bank below)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        if bank_obj["classnames"] is None:
+            raise SystemExit(f"--bank {args.bank!r}: the bank holds no class names (it was written by a model built from token rows)")
+        plan = plan_vocabulary_edits(args, bank_obj["classnames"], shots, seed, ragged)
+        classnames, exemplars, test_items = plan[3], [], []
+        if not predict:                                       # the data set the test pass runs on must speak of the same classes
+            set_names, _, test_items = build_splits(split_cfg, args.eval_split, args.test_split, "", False)
+            diff = bank_format.first_difference(classnames, set_names)
+            if diff is not None:
+                raise SystemExit(f"--bank {args.bank!r}: its class names" + (" (after the edits)" if edits else "") + f" are not the data set's: {diff}")
+    else:
+        classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if predict else args.test_split, args.exemplar_list, ragged)
     if predict:
         if k > len(classnames):
             raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
@@ -558,8 +680,15 @@ def main(argv=None) -> Dict[str, float]:
             print("Note that load_model() is skipped as no pretrained model is given")       # :464-466
         kw["prompt_learner_state"] = pl_state
     loader = _loader_factory(args, cfg, spec.image_resolution, tfm)
-    if zeroshot or load_classifiers:
+    edit_loaders = {}
+    if zeroshot or load_classifiers or from_bank:
         eval_loader = None
+        for key, part in (("replace", plan[1]), ("add", plan[2])) if from_bank else ():
+            if part is not None:                              # the loaders of the edited classes only: nothing of an old class is listed
+                try:
+                    edit_loaders[key] = loader(part[1], batch if ragged else batch // shots * shots, 0, 1, len(part[0]), ragged=ragged)
+                except ValueError as e:
+                    raise SystemExit(str(e)) from None
     elif ragged:
         try:
             eval_loader = loader(exemplars, batch, rank, world, len(classnames), ragged=True)
@@ -574,6 +703,9 @@ def main(argv=None) -> Dict[str, float]:
     # the decode workers start while the engine takes the weights; one ring, sized for the larger batch, serves both loaders of a rank
     # (a rank whose share of the test batches is empty decodes exemplars alone: its ring is sized for those)
     first = eval_loader if eval_loader is not None and (len(test_loader) == 0 or eval_loader.bs > test_loader.bs) else test_loader
+    for ld in edit_loaders.values():                          # (an edit's loader may be the one that needs the larger ring)
+        if len(first) == 0 or ld.bs > first.bs:
+            first = ld
     if hasattr(first, "warm"):
         first.warm()
     dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
@@ -582,11 +714,31 @@ def main(argv=None) -> Dict[str, float]:
                                compute_cmat=args.confusion_matrix, **kw)
     if load_classifiers:
         tr.model.load_classifiers(args.classifiers)
+    elif from_bank:
+        # (the trainer and its evaluator were built for the FINAL class names; the bank replaces the model's class list, the edits lead to it)
+        try:
+            tr.model.load_bank(args.bank, bank_obj)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        remove, replace, add, _ = plan
+        if remove:
+            tr.model.remove_classes(remove)
+        if replace is not None:
+            tr.model.replace_classes(list(replace[0]), edit_loaders["replace"], exemplar_paths=_paths_per_class(replace[1], len(replace[0])))
+        if add is not None:
+            tr.model.add_classes(list(add[0]), edit_loaders["add"], exemplar_paths=_paths_per_class(add[1], len(add[0])))
+        assert tr.model.classnames == classnames
+        if edits:
+            tr.model.save_classifiers()
+            tr.model.save_bank(osp.join(cfg.OUTPUT_DIR, bank_format.BANK_FILE))
     elif not zeroshot:
         # the reference does this inside the first forward (:341-342); up front it keeps the two loaders' statistics apart.  Rank 0's two
         # files are written by a worker thread while the test set runs (CustomCLIP._write_files), joined at the end of test().  The
         # classifiers are complete on every rank: each goes on to its own batches of the test set
         tr.model.forward_prompt(eval_loader, wait_files=False)
+        if args.save_bank:
+            from . import bank as bank_format
+            tr.model.save_bank(osp.join(cfg.OUTPUT_DIR, bank_format.BANK_FILE), exemplar_paths=_label_order_paths(exemplars))
     if predict:
         values, indices = tr.predict(test_loader, k)
         results = {"predictions": ranked_predictions(images, values, indices, classnames)}
@@ -598,6 +750,8 @@ def main(argv=None) -> Dict[str, float]:
         results = dict(tr.results)
     if eval_loader is not None:
         _report_pipeline(results, "exemplar set", eval_loader)
+    for key, ld in edit_loaders.items():
+        _report_pipeline(results, f"{key} set", ld)
     _report_pipeline(results, "predict set" if predict else "test set", test_loader)
     results["classnames"] = classnames
     if test_loader.batch_shard is not None:
