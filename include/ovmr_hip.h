@@ -64,7 +64,7 @@ void ovmr_destroy(ovmr_handle* h);
 const char* ovmr_last_error(const ovmr_handle* h);
 const char* ovmr_version(void);
 
-/* Kernel-variant switch used by tests/bench to A/B implementations: key in {"gemm","attn","ln_fold","xval_fused","gelu_exact","fuse_im2col","enc_chunk","last_q_cls","fused_head","head_max_grid","agg_max_len"}.
+/* Kernel-variant switch used by tests/bench to A/B implementations: key in {"gemm","attn","ln_fold","xval_fused","gelu_exact","fuse_im2col","enc_chunk","last_q_cls","fused_head","head_max_grid","agg_max_len","gemm_persist"}.
  * "gemm" (default 8): which fp16 GEMM kernel a launch runs, and with which K loop, tile height and cache hints (gemm_f16_route in
  *   csrc/gemm_f16.hip, exported as ovmr_debug_gemm_route):
  *   8 = 256-row LDS-DMA tiles with the ping-pong K loop (half-tile staging, counted waits) and, for latency-bound shapes
@@ -88,6 +88,11 @@ const char* ovmr_version(void);
  *   reference's fp16 tensors (h(1.702 u), h(sigmoid), h(u s)); 0 evaluates x / (1 + exp(-1.702 x)) in fp32 on the unrounded
  *   linear output and rounds once -- closer to the real function, within a few fp16 steps of the reference's value, and 5 % off
  *   the c_fc launch.
+ * "gemm_persist" (default 1): in_proj and c_fc with the LayerNorm folded in, on launches of more 256-row tiles than the 256 CUs, run as a
+ *   tile loop of one workgroup per CU (csrc/gemm_f16_v5.hip "Tile loop": the next tile's operands are requested before a tile's results are
+ *   converted and stored); 0 launches one workgroup per tile.  Bit-identical.  (The library also exports three test hooks that are not part
+ *   of this ABI: ovmr_debug_gemm_plan -- ovmr_debug_gemm_route with this option as an argument and the plan's eleventh field, persist --,
+ *   ovmr_debug_gemm_persist and ovmr_debug_gemm_tile_walk; csrc/gemm_f16.hip and csrc/gemm_f16_v5.hip document them.)
  * "fuse_im2col" (default 1): conv1 on fp16 images with 16 x 16 patches -- the patch-embedding GEMM gathers its A rows from the image
  *   tensor inside its K loop; 0 writes the patch matrix out first (what fp32 images and other patch sizes always do).  Bit-identical.
  * "last_q_cls" (default 1): the last vision block (whose output is read at the CLS row only, clip/model.py:423) projects K and V for every
@@ -438,7 +443,8 @@ int ovmr_debug_attention_route(int variant, int L, int Lq, int causal);
  *   [2] split-K: K-steps of 32 prefetched per wave, [3] groups of that many steps per wave;
  *   tile kernel: [4] tile rows (128 / 256), [5] K loop (0 double-buffered, 1 iteration boundary inside the MFMA stream, 2 ping-pong),
  *   [6] nontemporal A stream, [7] nontemporal C stores, [8] N tiles per group of the tile order (4, or all of them);
- *   [9] QuickGELU in the one-rounding form (epilogues 2 and 7). */
+ *   [9] QuickGELU in the one-rounding form (epilogues 2 and 7).
+ * The plan is that of option "gemm_persist" = 0; no field above depends on that option. */
 int ovmr_debug_gemm_route(int variant, int M, int N, int K, int epi, int ldc, int ldres, int stats, int im2col, int* out);
 /* The instantiations of the tile kernel the library holds, (epilogue, tile rows / 32, option bits) each: returns their number and
  * writes the first `cap` of them to out[3 * cap].  The route reaches every one of them and no other (tests/test_gemm_route_cpu.py). */

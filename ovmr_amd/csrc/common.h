@@ -54,7 +54,7 @@ struct GemmArgs {
     int ln_stride;                         // ... slots between the statistics of consecutive A rows (0 = ln_slots: dense; the CLS-row launch strides over tokens)
     const float* ln_g; const float* ln_b;  // EPI_LN_*: [N] fp32 each
     float* stats_out;                      // EPI_BIAS_RES, optional: partial statistics of the stored C rows, [M][N/256][2]
-    int nt_store;                          // unused (the route decides the store hint); kept because every kernel's instructions carry the offsets behind it
+    int persist;                           // the caller's "gemm_persist" option: gemm_f16_route may plan the tile loop (GemmPlan::persist); no kernel reads it
     float* argmax_out;                     // EPI_SCALE_ARGMAX: [M][ceil(N/256)][2] (value, column index bits)
     int gelu_mode;                         // QuickGELU epilogues: 0 = the reference's three fp16 rounding points, 1 = quick_gelu_f32x2
     // EPI_PATCH, gemm_f16_v5 only: A is the fp16 IMAGE tensor [B, 3, R, R] itself and the K loop gathers the patch rows

@@ -12,6 +12,8 @@
 // The MFMA is issued with W as the A operand and A as the B operand, so the accumulator holds
 // C^T: lane l owns row m = l&15 and four CONSECUTIVE columns n = 4*(l>>4)..+3, which turns the
 // epilogue (bias / residual / QuickGELU / positional add) into 8-byte vector loads and stores.
+#include <string.h>
+
 #include "gemm_epi.h"
 #include "gemm_route.h"
 
@@ -174,6 +176,10 @@ void plan_tile(const GemmArgs& a, bool ping_pong, GemmPlan& p) {
     // but with the ping-pong K loop (r02c, same-process A/B at batch 512) groups of 4 from 8 N tiles on take 1.5-2.5 % off qkv / c_fc
     // (c_fc_ln 496 -> 484 us, qkv_ln 329 -> 325 us), nothing off the N = 768 shapes
     p.n_group = p.loop == LOOP_PINGPONG && tiles_n >= 8 ? 4 : tiles_n;
+    // The tile loop (gemm_f16_v5.hip, "Tile loop": one workgroup per CU walks the tiles, the next tile's operands in flight under a
+    // tile's epilogue) exists for the LayerNorm-folding ping-pong kernels; it is planned where the caller's option asks for it and
+    // the launch has more tiles than the 256 CUs.  Measurements: DESIGN.md section 4.
+    p.persist = a.persist && lnf && p.loop == LOOP_PINGPONG && tiles > 256;
 }
 
 }  // namespace
@@ -239,8 +245,8 @@ GemmPlan gemm_f16_route(const GemmArgs& a, int variant) {
 }
 
 // The route for a launch with 16-byte-aligned operands, lda = ldw = K and every operand a tile-only feature needs present (no GPU).
-// im2col: the image side R, 0 = none.  out[10]: the GemmPlan, field by field (include/ovmr_hip.h).
-extern "C" int ovmr_debug_gemm_route(int variant, int M, int N, int K, int epi, int ldc, int ldres, int stats, int im2col, int* out) {
+// im2col: the image side R, 0 = none; persist: the caller's "gemm_persist" option.  out[11]: the GemmPlan, field by field.
+extern "C" int ovmr_debug_gemm_plan(int variant, int M, int N, int K, int epi, int ldc, int ldres, int stats, int im2col, int persist, int* out) {
     static float operand[4];
     alignas(16) static char base[16];
     GemmArgs a = {};
@@ -248,9 +254,43 @@ extern "C" int ovmr_debug_gemm_route(int variant, int M, int N, int K, int epi, 
     a.A = a.W = a.res = base; a.C = base;
     a.ln_stats = a.ln_g = a.ln_b = operand; a.ln_slots = 1; a.argmax_out = operand; a.stats_out = stats ? operand : nullptr;
     a.im2col_R = im2col; a.rows_in = (im2col >> 4) * (im2col >> 4); a.rows_out = a.rows_in + 1;
-    static_assert(sizeof(GemmPlan) == 10 * sizeof(int), "");
+    a.persist = persist;
+    static_assert(sizeof(GemmPlan) == 11 * sizeof(int), "");
     *(GemmPlan*)out = gemm_f16_route(a, variant);
     return 0;
+}
+
+// ... with the option off; out[10]: the plan's first ten fields (include/ovmr_hip.h)
+extern "C" int ovmr_debug_gemm_route(int variant, int M, int N, int K, int epi, int ldc, int ldres, int stats, int im2col, int* out) {
+    int plan[11];
+    const int rc = ovmr_debug_gemm_plan(variant, M, N, K, epi, ldc, ldres, stats, im2col, 0, plan);
+    memcpy(out, plan, 10 * sizeof(int));
+    return rc;
+}
+
+// A LayerNorm-folding GEMM (epi 6 / 7) with the tile loop chosen by the caller: persist = the "gemm_persist" option of the launch.
+// max_wgs > 0 (tests/test_hip_gemm_persist.py): the launch runs the 256-row ping-pong tile kernel whatever the route says of the
+// shape, as a tile loop of at most max_wgs workgroups -- so that a shape of a few tiles drives the loop; max_wgs >= the number of
+// tiles is the one-tile-per-workgroup form.  A [M, lda], W [N, K], C [M, ldc]; ln_stats [.., ln_slots, 2] with ln_stride slots between
+// the statistics of consecutive A rows (0: dense).
+extern "C" int ovmr_debug_gemm_persist(int variant, const void* A, int lda, const void* W, const float* ln_b, const float* ln_stats, int ln_slots,
+                                       int ln_stride, const float* ln_g, void* C, int ldc, int M, int N, int K, int epi, int persist, int max_wgs,
+                                       void* stream) {
+    if (epi != EPI_LN_BIAS && epi != EPI_LN_BIAS_QGELU) return -1;
+    if (!A || !W || !ln_b || !ln_stats || !ln_g || !C || max_wgs < 0) return -1;
+    GemmArgs a = {};
+    a.A = A; a.lda = lda; a.W = W; a.ldw = K; a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.epi = epi; a.scale = 1.f;
+    a.ln_stats = ln_stats; a.ln_slots = ln_slots; a.ln_stride = ln_stride; a.ln_g = ln_g; a.ln_b = ln_b;
+    a.persist = persist;
+    if (!max_wgs) return launch_gemm_f16(a, variant, (hipStream_t)stream);
+    GemmPlan p = gemm_f16_route(a, variant);
+    if (p.kernel != GEMM_TILE) return p.kernel == GEMM_NONE ? p.rc : -4;
+    if (K % 128) return -2;                                      // the ping-pong loop: two K-tiles per iteration
+    const int tiles_n = (N + 255) / 256;
+    p.tile_rows = 256; p.loop = LOOP_PINGPONG; p.a_nt = 0; p.n_group = tiles_n >= 8 ? 4 : tiles_n; p.persist = 1;
+    a.n_group = p.n_group;
+    a.gelu_mode = p.gelu_mode;
+    return launch_gemm_f16_v5(a, p, (hipStream_t)stream, max_wgs);
 }
 
 int launch_gemm_f16(const GemmArgs& a_in, int variant, hipStream_t s) {

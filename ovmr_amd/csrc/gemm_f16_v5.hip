@@ -21,10 +21,45 @@
 //   * ONE workgroup barrier in the epilogue (the staging tiles are wave-private; the barriers that used to separate the
 //     phases also drained the first half's global stores), packed fp32 / fp16 VALU forms, interior tiles without bounds
 //     compares.
+// Tile loop (the LayerNorm-folding ping-pong instantiations, v5_tile_loop: in_proj <6, 8, 528> and c_fc <7, 8, 2576>; r07a, DESIGN.md
+// section 4).  A workgroup walks the dispatch slots blockIdx.x, + gridDim.x, ...; a slot is a tile by the same XCD-aware map as a
+// block id (v5_tile_of), so a CU computes the tiles it was dispatched before, in the same order.  Where the route plans it
+// (GemmPlan::persist) the grid is one workgroup per CU; with one workgroup per tile the loop runs once.  A one-tile workgroup ends
+// behind its last global_store, the hardware holds it until every store is acknowledged, and only then the CU's next workgroup is
+// dispatched and pays the operand latency of its prologue: acknowledgement, dispatch and first-tile latency one after the other,
+// per tile and CU.  In the loop:
+//   * LDS is 2 x 64 KiB of K slots, TWO 4 KiB constant blocks (tile t uses block t & 1) and 16 KiB of epilogue staging, 2 KiB per
+//     wave: results go through LDS in steps of 16 accumulator rows instead of two 64-row halves laid over the K slots, so that the
+//     K slots belong to the next tile as soon as the K loop is over.  What was traded: a step needs the constants of all four column
+//     blocks, so the 2 x 16 column constants of a lane are held in registers for the whole epilogue, and the conversions of a step
+//     are kept behind the step before (sched_barrier) -- 256 VGPRs, no scratch (234 before);
+//   * behind the K loop's last barrier (the balancing one: every wave of both rows has retired its last fragment read in front of
+//     the barrier it arrives at, so every K slot is free -- the WAR rule of the K loop) the workgroup issues the NEXT tile's prologue
+//     DMA -- K-tile 0 and the first two half-tiles of K-tile 1, the prologue's six stage_half -- and, in front of them, plain loads
+//     of the next tile's column constants and row statistics into registers; only then it converts and stores this tile, and last
+//     it computes rstd / -rstd * mean from those registers and writes the other constant block;
+//   * which wait retires what.  The next tile's K-tile 0: the loop top's counted vmcnt(4) + lgkmcnt(0) + s_barrier, the same three
+//     instructions as the prologue's.  The counter counts this tile's 16 stores too, which were issued AFTER the twelve DMAs: "at
+//     most 4 outstanding" leaves, among the loads, at most the newest four = the two half-tiles of K-tile 1 (loads retire in order
+//     among themselves; no order between loads and stores is assumed), so K-tile 0 has landed whatever the stores do, and every
+//     later counted wait of the K loop is only the stronger for stores still in flight.  The wait therefore costs the later of
+//     {operand latency, store acknowledgement}, both started a whole epilogue earlier, and no dispatch.  There is no
+//     __syncthreads() and no vmcnt(0) between a tile's last store and the next tile's first MFMA;
+//   * the constant loads are hipcc's own: it waits for them in front of the arithmetic at the END of the epilogue, counting that
+//     epilogue's 16 stores -- vmcnt(16) on interior tiles, which drains none of them (the interior and the guarded form each end
+//     with their own copy of that code for this reason).  A guarded tile (last row / column of tiles), whose store count is not
+//     known, gets vmcnt(0) there, and so does a launch with more than four statistics slots (K > 1024: the slots beyond four are
+//     read at that point);
+//   * the constant block written at the end of tile t is first read after the K loop of tile t + 1 (barriers in between), and was
+//     last read in the epilogue of tile t - 1; the staging area is private to its wave (LDS executes a wave's instructions in order).
+// tests/test_hip_gemm_persist.py drives the loop on shapes of a few tiles with the grid capped (ovmr_debug_gemm_persist).
 // Measured and removed (profiles/r01e_gemm_experiments.md, r01g_gemm_epilogue.md): L2 prefetch touches (every workgroup, and
 // designated prefetcher workgroups), staggered LDS-DMA issue, buffer_load ... lds, s_setprio around the MFMA stream, a
 // persistent one-workgroup-per-CU tile loop with the next tile's first K-tile prefetched under the epilogue, W fragments
 // straight from global memory, tile-contiguous C stores, residual as accumulator start value, x ping-pong buffers.
+#include <algorithm>
+#include <type_traits>
+
 #include "gemm_route.h"
 
 namespace {
@@ -45,6 +80,34 @@ constexpr int OPT_PINGPONG = 16;      // the ping-pong K loop (256-row tiles)
 constexpr int OPT_NT_STORE = 512;     // nontemporal C stores (a template bit: the compiler merges a run-time branch around two stores of the
                                       // same value and drops the hint)
 constexpr int OPT_GELU_F32 = 2048;    // the fp32 QuickGELU form
+
+// The LayerNorm-folding ping-pong instantiations (in_proj, c_fc) are written as a TILE LOOP: a workgroup walks the dispatch slots
+// blockIdx.x, + gridDim.x, ... (launched with one workgroup per tile the loop runs once; see the kernel's ping-pong section).
+constexpr bool v5_tile_loop(int epi, int mt, int opt) { return (epi == EPI_LN_BIAS || epi == EPI_LN_BIAS_QGELU) && mt == 8 && (opt & OPT_PINGPONG); }
+constexpr int V5_CONST_BLOCK = 4096, V5_STAGING = 16384;   // tile loop: two constant blocks and the epilogue's staging behind the K buffers
+
+// dispatch slot (block id) -> tile.  XCD-aware: ids congruent mod 8 run on one XCD and get a contiguous range of tiles; inside the
+// range N tiles come in groups of G with M fastest-but-one (n_group, set by gemm_f16_route).
+__host__ __device__ __forceinline__ void v5_tile_of(int bid, int tiles_m, int tiles_n, int n_group, int& tm, int& tn) {
+    const int nwg = tiles_m * tiles_n;
+    {
+        const int xcd = bid & 7, idx = bid >> 3, q = nwg >> 3, r = nwg & 7;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    }
+    const int G = n_group > 0 ? n_group : tiles_n;
+    const int full = tiles_n / G, per = tiles_m * G;
+    const int g = bid / per;
+    if (g < full) {
+        const int r = bid - g * per;
+        tm = r / G;
+        tn = g * G + (r - tm * G);
+    } else {
+        const int Gl = tiles_n - full * G, r = bid - full * per;
+        tm = r / Gl;
+        tn = full * G + (r - tm * Gl);
+    }
+}
+
 template <int EPI, int MT, int OPT>
 __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_m, int tiles_n) {
     constexpr int BM = MT * 32;
@@ -64,30 +127,10 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 2, wn = wave & 3;
 
-    // block id -> tile.  XCD-aware: ids congruent mod 8 run on one XCD and get a contiguous range of tiles; inside the
-    // range N tiles come in groups of G with M fastest-but-one (a.n_group, set by gemm_f16_route).
-    const int nwg = tiles_m * tiles_n;
-    int bid = blockIdx.x;
-    {
-        const int xcd = bid & 7, idx = bid >> 3, q = nwg >> 3, r = nwg & 7;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    constexpr bool LOOPED = v5_tile_loop(EPI, MT, OPT);   // the tile loop (ping-pong section): m0 / n0 move on to the workgroup's next tile
     int tm, tn;
-    {
-        const int G = a.n_group > 0 ? a.n_group : tiles_n;
-        const int full = tiles_n / G, per = tiles_m * G;
-        const int g = bid / per;
-        if (g < full) {
-            const int r = bid - g * per;
-            tm = r / G;
-            tn = g * G + (r - tm * G);
-        } else {
-            const int Gl = tiles_n - full * G, r = bid - full * per;
-            tm = r / Gl;
-            tn = full * G + (r - tm * Gl);
-        }
-    }
-    const int m0 = tm * BM, n0 = tn * BN5;
+    v5_tile_of(blockIdx.x, tiles_m, tiles_n, a.n_group, tm, tn);
+    int m0 = tm * BM, n0 = tn * BN5;
 
     const int nk = a.K / BK5;
     const half_t* A = (const half_t*)a.A;
@@ -150,6 +193,31 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     const int b_row_off = A_BYTES + (wn * 64 + fr) * 128;
     const int ch0 = ((fg) ^ (fr & 7)) << 4, ch1 = ((4 + fg) ^ (fr & 7)) << 4;
 
+    // LayerNorm fold of one accumulator block's four columns (both epilogues below): rstd * acc + (c1 - rstd * mean * c0), QuickGELU, fp16
+    auto ln_fold4 = [&](const float4_t v, const float ln_r, const float ln_t, const float4_t c0, const float4_t c1) -> half4_t {
+        half4_t o;
+#pragma unroll
+        for (int r = 0; r < 4; r += 2) {
+            // two columns per instruction (v_pk_fma_f32): same two fused multiply-adds per element as the scalar form
+            const float2_t t2 = __builtin_elementwise_fma((float2_t){ln_t, ln_t}, (float2_t){c0[r], c0[r + 1]}, (float2_t){c1[r], c1[r + 1]});
+            float2_t x2 = __builtin_elementwise_fma((float2_t){ln_r, ln_r}, (float2_t){v[r], v[r + 1]}, t2);
+            if (EPI == EPI_LN_BIAS_QGELU && GFAST) x2 = quick_gelu_f32x2(x2);
+            const half2_t u2 = __builtin_convertvector(x2, half2_t);
+            o[r] = u2[0];
+            o[r + 1] = u2[1];
+        }
+        if (EPI == EPI_LN_BIAS_QGELU && !GFAST) o = quick_gelu_h4(o);
+        return o;
+    };
+    // epilogue staging tile (both epilogues; the swizzle is described at the epilogue below): byte offset at which a lane writes column
+    // block j of its row fr, byte offset of the 16-byte chunk it reads back from row lane >> 3, and the halves of a chunk put back
+    auto stage_wr = [&](int j) -> int { return fr * EP + (((j * 4 + fg) ^ (((fr & 7) << 1) | (fr >> 3))) << 3); };
+    auto stage_rd = [&]() -> int { return (lane >> 3) * EP + (((lane & 7) ^ (lane >> 3)) << 4); };
+    auto stage_unswap = [](const half8_t v, int it) -> half8_t {
+        if (it & 1) return (half8_t){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
+        return v;
+    };
+
     constexpr bool PH8 = (OPT & OPT_PINGPONG) != 0 && MT == 8;
     if (!PH8) stage(0, 0);
 
@@ -207,16 +275,19 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     constexpr int SLOT = 16384, KBUF = 4 * SLOT;
     enum { hB0 = 0, hA0 = 1, hB1 = 2, hA1 = 3 };
     unsigned sa8[2][2], sb8[2][2];                      // [half][8-row piece]: byte offset of this lane's source row
+    auto source_rows = [&](int tm0, int tn0) {          // ... for the tile at (tm0, tn0)
 #pragma unroll
-    for (int hf = 0; hf < 2; ++hf)
+        for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int lr = wave * 16 + j * 8 + srow;                                    // local row inside the half-tile
-            const int ra = m0 + (lr >> 6) * 128 + hf * 64 + (lr & 63);
-            const int rb = n0 + (lr >> 5) * 64 + hf * 32 + (lr & 31);
-            sa8[hf][j] = a_off(ra);
-            sb8[hf][j] = src_off(min(rb, a.N - 1), a.ldw);
-        }
+            for (int j = 0; j < 2; ++j) {
+                const int lr = wave * 16 + j * 8 + srow;                                    // local row inside the half-tile
+                const int ra = tm0 + (lr >> 6) * 128 + hf * 64 + (lr & 63);
+                const int rb = tn0 + (lr >> 5) * 64 + hf * 32 + (lr & 31);
+                sa8[hf][j] = a_off(ra);
+                sb8[hf][j] = src_off(min(rb, a.N - 1), a.ldw);
+            }
+    };
+    source_rows(m0, n0);
     const unsigned smem_lds = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(lptr_t)smem);
     const unsigned wave_lds = (unsigned)__builtin_amdgcn_readfirstlane(wave * 2048);
     auto stage_half = [&](int buf, int which, int kt) {
@@ -270,10 +341,51 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     __builtin_amdgcn_sched_barrier(0);                                    \
     __builtin_amdgcn_s_barrier();                                         \
     __builtin_amdgcn_sched_barrier(0);
+    // Tile loop (LOOPED): the epilogue constants of a tile as a load into registers and, an epilogue later, the arithmetic and the
+    // LDS write into constant block `blk` -- the same loads, sums and roundings as the prologue's block below.  The first four
+    // statistics slots are loaded at once (predicated); launches with more slots (K > 1024) read the rest at the write.
+    float cr[8];
+    auto load_consts = [&](int tm0, int tn0) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) cr[q] = 0.f;
+        if (tid < BN5) {
+            const int n = tn0 + tid;
+            if (n < a.N) { cr[0] = a.ln_g[n]; cr[1] = a.ln_b[n]; }
+        } else {
+            const float2_t* sp = (const float2_t*)a.ln_stats + (long)min(tm0 + tid - BN5, a.M - 1) * (a.ln_stride ? a.ln_stride : a.ln_slots);
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl)
+                if (sl < a.ln_slots) { const float2_t p = sp[sl]; cr[2 * sl] = p[0]; cr[2 * sl + 1] = p[1]; }
+        }
+    };
+    auto store_consts = [&](int blk, int tm0) {
+        float* cc = (float*)(smem + 2 * KBUF + blk * V5_CONST_BLOCK);
+        if (tid < BN5) {
+            cc[tid] = cr[0];
+            cc[BN5 + tid] = cr[1];
+        } else {
+            const int r = tid - BN5;
+            const float2_t* sp = (const float2_t*)a.ln_stats + (long)min(tm0 + r, a.M - 1) * (a.ln_stride ? a.ln_stride : a.ln_slots);
+            float su = 0.f, sq = 0.f;
+#pragma unroll
+            for (int sl = 0; sl < 4; ++sl)
+                if (sl < a.ln_slots) { su += cr[2 * sl]; sq += cr[2 * sl + 1]; }
+            for (int sl = 4; sl < a.ln_slots; ++sl) { const float2_t p = sp[sl]; su += p[0]; sq += p[1]; }
+            const float inv_k = 1.0f / (float)a.K;
+            const float mean = su * inv_k;
+            const float rstd = 1.0f / sqrtf(fmaxf(sq * inv_k - mean * mean, 0.f) + 1e-5f);
+            cc[2 * BN5 + r] = rstd;
+            cc[2 * BN5 + BM + r] = -rstd * mean;
+        }
+    };
     // prologue: tile 0 complete, two half-tiles of tile 1 in flight
     stage_half(0, hB0, 0); stage_half(0, hA0, 0); stage_half(0, hB1, 0); stage_half(0, hA1, 0);
     // epilogue constants -> LDS (the compiler waits for their global loads with vmcnt(0), i.e. also for tile 0, which the first
     // phase needs anyway; first read after the K loop)
+    if constexpr (LOOPED) {
+        load_consts(m0, n0);
+        store_consts(0, m0);
+    } else
     if (tid < BN5) {
         const int n = n0 + tid;
         float c0 = 0.f, c1 = 0.f;
@@ -296,6 +408,8 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     }
     __builtin_amdgcn_sched_barrier(0);
     stage_half(1, hB0, 1); stage_half(1, hA0, 1);
+    // LOOPED: the tile loop, its body not indented -- dispatch slot `dslot`, constant block `cb`; every other kernel leaves it after the K loop
+    for (int dslot = blockIdx.x, cb = 0;; cb ^= 1) {
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
@@ -356,6 +470,74 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
 #undef OVMR_P4_MID
     if (wm == 0) __builtin_amdgcn_s_barrier();          // balances the extra barrier of the second wave row
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (!LOOPED) break;
+    else {
+        // ---- the next tile's operands, then this tile's epilogue (header: "Tile loop")
+        const int cm0 = m0, cn0 = n0;
+        dslot += (int)gridDim.x;
+        const bool next = dslot < tiles_m * tiles_n;        // workgroup-uniform
+        if (next) {
+            v5_tile_of(dslot, tiles_m, tiles_n, a.n_group, tm, tn);
+            m0 = tm * BM;
+            n0 = tn * BN5;
+            source_rows(m0, n0);
+            load_consts(m0, n0);
+            __builtin_amdgcn_sched_barrier(0);
+            stage_half(0, hB0, 0); stage_half(0, hA0, 0); stage_half(0, hB1, 0); stage_half(0, hA1, 0);
+            stage_half(1, hB0, 1); stage_half(1, hA0, 1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // Results through LDS in steps of 16 accumulator rows: 16 rows x 64 columns = 2 KiB per wave, behind the constant blocks, so
+        // that the K buffers are the next tile's from here on.  Same swizzle, same 16-byte stores of 8 rows x 128 B as the epilogue
+        // below.  A step's constants are needed for all four column blocks, so the column constants of the wave's 64 columns are
+        // held in 32 registers for the whole epilogue (the fragment registers of the K loop are free here); a row's pair is read
+        // once per step.
+        half_t* const C = (half_t*)a.C;
+        const float* const ccol = (const float*)(smem + 2 * KBUF + cb * V5_CONST_BLOCK);
+        const float* const crow = ccol + 2 * BN5;
+        char* const et = smem + 2 * KBUF + 2 * V5_CONST_BLOCK + wave * (16 * EP);
+        const int er = lane >> 3, nn = cn0 + wn * 64 + (lane & 7) * 8;
+        const int rd_off = stage_rd();
+        const bool full_tile = cm0 + BM <= a.M && cn0 + BN5 <= a.N;   // workgroup-uniform
+        float4_t c0[4], c1[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            c0[j] = *(const float4_t*)(ccol + wn * 64 + j * 16 + fg * 4);
+            c1[j] = *(const float4_t*)(ccol + BN5 + wn * 64 + j * 16 + fg * 4);
+        }
+        // interior tiles (all but the last row / column of tiles) store without bounds compares, as below; each form ends with the
+        // next tile's constants, so that the wait hipcc puts in front of them counts that form's own stores and drains none of them
+        auto convert_and_store = [&](auto guarded) {
+            half_t* dst = C + (long)(cm0 + wm * (BM / 2) + er) * a.ldc + nn;
+            const long step = 8L * a.ldc;
+#pragma unroll
+            for (int i = 0; i < MT; ++i) {
+                const int r = wm * (BM / 2) + i * 16 + fr;
+                const float ln_r = crow[r], ln_t = crow[BM + r];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) *(half4_t*)(et + stage_wr(j)) = ln_fold4(acc[i][j], ln_r, ln_t, c0[j], c1[j]);
+                half8_t vv[2];
+#pragma unroll
+                for (int it = 0; it < 2; ++it) vv[it] = stage_unswap(*(const half8_t*)(et + it * 8 * EP + rd_off), it);
+#pragma unroll
+                for (int it = 0; it < 2; ++it, dst += step) {
+                    if (decltype(guarded)::value && !(cm0 + wm * (BM / 2) + i * 16 + it * 8 + er < a.M && nn < a.N)) continue;   // N % 8 == 0 is guaranteed by the launcher
+                    if (NT) __builtin_nontemporal_store(vv[it], (half8_t*)dst);
+                    else *(half8_t*)dst = vv[it];
+                }
+                __builtin_amdgcn_sched_barrier(0);       // a step's conversions are not hoisted over the step before (registers)
+            }
+            if (next) store_consts(cb ^ 1, m0);
+        };
+        if (full_tile) convert_and_store(std::false_type{});
+        else convert_and_store(std::true_type{});
+        if (!next) return;
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = (float4_t){0.f, 0.f, 0.f, 0.f};
+    }
+    }
 #undef OVMR_PH_END
     } else
     if (OPT & OPT_BOUNDARY) {
@@ -532,15 +714,12 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     // arrives with its halves exchanged is a compile-time fact (rows it*8 + er: odd it), so putting them back costs nothing.
     // SQ_LDS_BANK_CONFLICT = 0 (profiles/r03b_pmc_gemm_v109.json); the 144-byte padded rows this replaces were 2-way on every
     // write and on one read group in four (r02o: 11.7 % of the LDS cycles) -- at equal run time (r03c: -0.3 ... +0.8 %).
-    const int fsw = ((fr & 7) << 1) | (fr >> 3);
     int wr_off[4];                                      // phase 1: byte offset of column block j inside this lane's row fr
 #pragma unroll
-    for (int j = 0; j < 4; ++j) wr_off[j] = fr * EP + (((j * 4 + fg) ^ fsw) << 3);
-    const int rd_off = er * EP + (((lane & 7) ^ er) << 4);
+    for (int j = 0; j < 4; ++j) wr_off[j] = stage_wr(j);
+    const int rd_off = stage_rd();
     auto read_staged = [&](int it) -> half8_t {         // rows it*8 + er, this lane's eight columns
-        const half8_t v = *(const half8_t*)(et + it * 8 * EP + rd_off);
-        if (it & 1) return (half8_t){v[4], v[5], v[6], v[7], v[0], v[1], v[2], v[3]};
-        return v;
+        return stage_unswap(*(const half8_t*)(et + it * 8 * EP + rd_off), it);
     };
     const bool emit_stats = EPI == EPI_BIAS_RES && a.stats_out != nullptr;
     const bool full_tile = EPI != EPI_PATCH && m0 + BM <= a.M && n0 + BN5 <= a.N;   // workgroup-uniform
@@ -589,17 +768,7 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
                 const float ln_r = ln_rs[LNF ? i : 0], ln_t = ln_ts[LNF ? i : 0];
                 half4_t o;
                 if (LNF) {
-#pragma unroll
-                    for (int r = 0; r < 4; r += 2) {
-                        // two columns per instruction (v_pk_fma_f32): same two fused multiply-adds per element as the scalar form
-                        const float2_t t2 = __builtin_elementwise_fma((float2_t){ln_t, ln_t}, (float2_t){c0[r], c0[r + 1]}, (float2_t){c1[r], c1[r + 1]});
-                        float2_t x2 = __builtin_elementwise_fma((float2_t){ln_r, ln_r}, (float2_t){v[r], v[r + 1]}, t2);
-                        if (EPI == EPI_LN_BIAS_QGELU && GFAST) x2 = quick_gelu_f32x2(x2);
-                        const half2_t u2 = __builtin_convertvector(x2, half2_t);
-                        o[r] = u2[0];
-                        o[r + 1] = u2[1];
-                    }
-                    if (EPI == EPI_LN_BIAS_QGELU && !GFAST) o = quick_gelu_h4(o);
+                    o = ln_fold4(v, ln_r, ln_t, c0, c1);
                 } else {
                     // float2 sums and __builtin_convertvector: v_pk_add_f32 + v_cvt_pk_f16_f32 (round to nearest even), two
                     // elements per instruction; element-wise casts made hipcc emit cvt + pack + alignbit chains (3.8 -> ~1.6
@@ -699,10 +868,13 @@ __global__ __launch_bounds__(512) void gemm_f16_v5_kernel(GemmArgs a, int tiles_
     }
 }
 
+// max_wgs > 0 (the tile-loop instantiations only): at most so many workgroups walk the tiles; 0: one workgroup per tile
 template <int EPI, int MT, int OPT>
-int launch_v5_k(const GemmArgs& b, int tiles_m, int tiles_n, hipStream_t s) {
+int launch_v5_k(const GemmArgs& b, int tiles_m, int tiles_n, int max_wgs, hipStream_t s) {
     constexpr int BM = MT * 32;
-    const size_t lds = (size_t)2 * (BM + BN5) * 128 + 2 * BN5 * 4 + 2 * BM * 4;
+    constexpr bool LOOPED = v5_tile_loop(EPI, MT, OPT);
+    const size_t lds = LOOPED ? (size_t)2 * (BM + BN5) * 128 + 2 * V5_CONST_BLOCK + V5_STAGING : (size_t)2 * (BM + BN5) * 128 + 2 * BN5 * 4 + 2 * BM * 4;
+    static_assert(2 * BN5 * 4 + 2 * 256 * 4 == V5_CONST_BLOCK && 8 * 16 * 128 == V5_STAGING, "");
     static bool attr_set[OVMR_MAX_DEVICES] = {};      // the attribute is per device (one process may drive several)
     int dev = 0;
     HIP_CHECK_RET(hipGetDevice(&dev));
@@ -710,7 +882,8 @@ int launch_v5_k(const GemmArgs& b, int tiles_m, int tiles_n, hipStream_t s) {
         HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_f16_v5_kernel<EPI, MT, OPT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_set[dev] = true;
     }
-    hipLaunchKernelGGL((gemm_f16_v5_kernel<EPI, MT, OPT>), dim3(tiles_m * tiles_n), dim3(512), lds, s, b, tiles_m, tiles_n);
+    const int tiles = tiles_m * tiles_n, grid = LOOPED && max_wgs > 0 ? std::min(tiles, max_wgs) : tiles;
+    hipLaunchKernelGGL((gemm_f16_v5_kernel<EPI, MT, OPT>), dim3(grid), dim3(512), lds, s, b, tiles_m, tiles_n);
     return (int)hipGetLastError();
 }
 
@@ -731,14 +904,39 @@ int launch_v5_k(const GemmArgs& b, int tiles_m, int tiles_n, hipStream_t s) {
 
 }  // namespace
 
-int launch_gemm_f16_v5(const GemmArgs& a, const GemmPlan& p, hipStream_t s) {
+int launch_gemm_f16_v5(const GemmArgs& a, const GemmPlan& p, hipStream_t s, int max_wgs) {
     const int mt = p.tile_rows / 32, tiles_m = (a.M + p.tile_rows - 1) / p.tile_rows, tiles_n = (a.N + BN5 - 1) / BN5;
     const int opt = (p.a_nt ? OPT_A_NT : 0) | (p.loop == LOOP_BOUNDARY ? OPT_BOUNDARY : 0) | (p.loop == LOOP_PINGPONG ? OPT_PINGPONG : 0) |
                     (p.nt_store ? OPT_NT_STORE : 0) | (p.gelu_mode ? OPT_GELU_F32 : 0);
-#define X(E, MT, OPT) if (a.epi == E && mt == MT && opt == (OPT)) return launch_v5_k<E, MT, (OPT)>(a, tiles_m, tiles_n, s);
+    // GemmPlan::persist: one workgroup per CU (the count is cached per device), or fewer where the caller caps them (max_wgs > 0: tests)
+    int wgs = 0;
+    if (p.persist) {
+        static int n_cu[OVMR_MAX_DEVICES] = {};
+        int dev = 0;
+        HIP_CHECK_RET(hipGetDevice(&dev));
+        if (dev < 0 || dev >= OVMR_MAX_DEVICES) return -100;
+        if (!n_cu[dev]) HIP_CHECK_RET(hipDeviceGetAttribute(&n_cu[dev], hipDeviceAttributeMultiprocessorCount, dev));
+        wgs = std::max(1, n_cu[dev]);
+        if (max_wgs > 0) wgs = std::min(wgs, max_wgs);
+    }
+#define X(E, MT, OPT) if (a.epi == E && mt == MT && opt == (OPT)) return launch_v5_k<E, MT, (OPT)>(a, tiles_m, tiles_n, wgs, s);
     V5_TABLE(X)
 #undef X
     return -3;
+}
+
+// The tile loop's walk, for tests/test_gemm_persist_route_cpu.py (no GPU): workgroup by workgroup of a grid of `grid`, the tiles it
+// computes in the order it computes them, as (workgroup, tm, tn) triples; returns their number (tiles_m * tiles_n), writes at most `cap`.
+extern "C" int ovmr_debug_gemm_tile_walk(int tiles_m, int tiles_n, int n_group, int grid, int* out, int cap) {
+    if (tiles_m < 1 || tiles_n < 1 || grid < 1 || !out) return -1;
+    int n = 0;
+    for (int w = 0; w < grid; ++w)
+        for (int slot = w; slot < tiles_m * tiles_n; slot += grid, ++n)
+            if (n < cap) {
+                out[3 * n] = w;
+                v5_tile_of(slot, tiles_m, tiles_n, n_group, out[3 * n + 1], out[3 * n + 2]);
+            }
+    return n;
 }
 
 // (epilogue, MT, OPT) of every entry of the table, for tests/test_gemm_route_cpu.py: returns their number, writes at most `cap`.

@@ -18,10 +18,11 @@ struct GemmPlan {
     int depth, groups;                                // GEMM_S64: K-steps of 32 prefetched per wave, K groups of `depth` steps per wave
     int tile_rows, loop, a_nt, nt_store, n_group;     // GEMM_TILE: 128 / 256, GemmLoop, nontemporal A stream / C stores, GemmArgs::n_group
     int gelu_mode;                                    // GemmArgs::gelu_mode of the launch (0 unless the epilogue is a QuickGELU one)
+    int persist;                                      // GEMM_TILE, LayerNorm-fold ping-pong launches: one workgroup per CU walks the tiles (gemm_f16_v5.hip, "Tile loop")
 };
 GemmPlan gemm_f16_route(const GemmArgs& a, int variant);
 int launch_gemm_f16_small(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
-int launch_gemm_f16_v5(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
+int launch_gemm_f16_v5(const GemmArgs& a, const GemmPlan& p, hipStream_t s, int max_wgs = 0);   // max_wgs > 0: caps a persistent grid (tests)
 // For the engine: does `variant` send an [M, N] launch to the split-K kernel because the shape is latency-bound (K permitting), and
 // the variant that pins, for a launch on PART of an [M, N] problem, the kernel family the whole launch takes under `variant`.
 bool gemm_f16_latency_bound(int variant, int M, int N);

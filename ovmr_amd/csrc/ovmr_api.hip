@@ -49,6 +49,7 @@ struct ovmr_handle {
     int fuse_im2col = 1;          // patch rows gathered by the patch-embedding GEMM itself (fp16 images, 16 x 16 patches)
     int gemm_variant = 8, attn_variant = 3;   // defaults = fastest verified kernels (tools/gemm_bench.py, tools/attn_bench.py); attention 3 falls back to 1 / 0 by shape
     int ln_fold = 1;                          // fold ln_1 / ln_2 of the fp16 towers into the consuming GEMM where the shape allows
+    int gemm_persist = 1;                     // in_proj / c_fc as a tile loop of one workgroup per CU (gemm_f16_v5.hip "Tile loop"; DESIGN.md section 4 for the default)
     int xval_fused = 1;                       // cross-validation logits: row argmax fused into the GEMM epilogue (never stored)
     int fused_head = 1;                       // ovmr_fused_logits / ovmr_zeroshot_logits as ONE launch (head_fused.hip); 0: scale + GEMMs + softmax
     int head_max_grid = 0;                    // > 0 caps the fused head's grid (tests: workgroups then take several tiles)
@@ -274,6 +275,7 @@ int ln_linear(ovmr_handle* h, const LnLinear& l, const half_t* x, half_t* y, int
         GemmArgs a = gemm(stats ? x : y, p.step * W, (stats ? l.wf : l.w) + (size_t)p.r0 * W, W, p.C, p.ldc, p.M, p.n, W, epi, stats ? nullptr : l.b + p.r0);
         if (stats) { a = gemm_ln(a, stats, slots, l.g + p.r0, l.bf + p.r0); a.ln_stride = p.step * slots; }
         a.gelu_mode = l.gelu && !h->gelu_exact;              // the one-rounding QuickGELU (common.h quick_gelu_f32x2)
+        a.persist = h->gemm_persist;                         // the tile loop, where gemm_f16_route plans it
         CK(launch_gemm_f16(a, variant, s));
     }
     return 0;
@@ -595,6 +597,7 @@ int ovmr_set_option(ovmr_handle* h, const char* key, int value) {
     else if (!strcmp(key, "fused_head")) h->fused_head = value;
     else if (!strcmp(key, "head_max_grid")) h->head_max_grid = value;
     else if (!strcmp(key, "gelu_exact")) h->gelu_exact = value;
+    else if (!strcmp(key, "gemm_persist")) h->gemm_persist = value != 0;
     else if (!strcmp(key, "agg_max_len")) {
         if (value < 128 || value > OVMR_AGG_MAX_LEN_CEILING)
             return fail(h, OVMR_E_ARG, "agg_max_len %d outside [128,%d]", value, OVMR_AGG_MAX_LEN_CEILING);
