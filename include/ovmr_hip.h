@@ -449,6 +449,11 @@ int ovmr_debug_gemm_route(int variant, int M, int N, int K, int epi, int ldc, in
 /* The instantiations of the tile kernel the library holds, (epilogue, tile rows / 32, option bits) each: returns their number and
  * writes the first `cap` of them to out[3 * cap].  The route reaches every one of them and no other (tests/test_gemm_route_cpu.py). */
 int ovmr_debug_gemm_tile_kernels(int* out, int cap);
+/* Fills the whole workspace arena of a finalized handle with the 32-bit pattern on the stream (hipMemsetD32Async): it allocates
+ * nothing and does not synchronise.  OVMR_E_ARG for a NULL handle, OVMR_E_STATE before ovmr_finalize.  It never touches the fused
+ * head's device counters: those must stay zero between launches, and a poisoned counter makes the head's wait spin forever.
+ * For tests/test_hip_poison.py: the result of a pass is a function of its inputs and weights, not of what the arena held. */
+int ovmr_debug_fill_workspace(ovmr_handle* h, uint32_t pattern, ovmr_stream stream);
 
 #ifdef __cplusplus
 }

@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void attn_f16_v0(const half_t* __restrict__ qk
     const bool active = qt < t1;
     const half_t* base = qkv + (long)b * L * ld + h * 64;
     const int q = qt * 16 + fr;
-    const int qc = min(q, L - 1);
+    const int qc = min(q, Lq - 1);     // a spare row repeats the last query, never a Q slot behind it (unwritten where Lq < L)
 
     half8_t qf[2];
 #pragma unroll

@@ -54,7 +54,9 @@ __global__ __launch_bounds__(512, 4) void attn_f16_v1(const half_t* __restrict__
         const int qt = t0 + 2 * wave + u;
         act[u] = qt < t1;
         qrow[u] = qt * 16 + fr;
-        const int qc = min(qrow[u], L - 1);
+        // a spare row repeats the last query (Lq - 1), never a Q slot behind it: with Lq < L those slots may be unwritten (the last vision
+        // block projects Q for the CLS rows only), and a spare row votes in the ballot of attn::lazy_reference
+        const int qc = min(qrow[u], Lq - 1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) qf[u][ks] = *(const half8_t*)(base + (long)qc * ld + ks * 32 + fg * 8);
     }

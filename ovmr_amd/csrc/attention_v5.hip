@@ -63,7 +63,7 @@ __global__ __launch_bounds__(NW * 64, 4) void attn_f16_v5(const half_t* __restri
     const int q = qt * 32 + r;
     half8_t qf[4];
     {
-        const int qc = min(q, L - 1);
+        const int qc = min(q, Lq - 1);                     // a spare row repeats the last query: its vote in the ballot is an input's, never a stale slot's
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const half8_t*)(base + (long)qc * ld + ks * 16 + h * 8);
     }

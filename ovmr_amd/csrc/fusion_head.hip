@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void xval_argmax_reduce(const float* __restric
         const int c = p[2 * t + 1];
         if (v > best || bi == 0x7fffffff) { best = v; bi = c; }
     }
-    const bool ok = live && bi < C;
+    const bool ok = live && (unsigned)bi < (unsigned)C;   // unsigned: a negative column (a pair nothing wrote) must not reach the histograms
     wave_histogram_add(n_pred, bi, ok);
     wave_histogram_add(tp, bi, ok && bi == labels[live ? row : 0]);
 }

@@ -1253,4 +1253,14 @@ int ovmr_debug_attention_q(int variant, const void* qkv, void* out, int B, int L
     return launch_attention_f16_q((const half_t*)qkv, (half_t*)out, B, L, Lq, H, causal, variant, (hipStream_t)stream);
 }
 
+// The whole workspace arena set to one 32-bit pattern (tests/test_hip_poison.py): what a pass computes must not depend on what the
+// arena held before it.  h->head_sync is NOT part of the arena and stays zero: a poisoned counter makes hf_wait spin forever.
+int ovmr_debug_fill_workspace(ovmr_handle* h, uint32_t pattern, ovmr_stream stream) {
+    if (!h) return OVMR_E_ARG;
+    if (!h->finalized) return need_finalized(h);
+    if (!h->ws || h->ws_bytes < 4) return 0;
+    HIP_CHECK_RET(hipMemsetD32Async((hipDeviceptr_t)h->ws, (int)pattern, h->ws_bytes / 4, (hipStream_t)stream));
+    return 0;
+}
+
 }  // extern "C"

@@ -101,6 +101,7 @@ SIGNATURES = {
     "ovmr_debug_attention_route": (c_i, [c_i, c_i, c_i, c_i]),
     "ovmr_debug_gemm_route": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.POINTER(c_i)]),
     "ovmr_debug_gemm_tile_kernels": (c_i, [ctypes.POINTER(c_i), c_i]),
+    "ovmr_debug_fill_workspace": (c_i, [c_p, ctypes.c_uint32, c_p]),
 }
 
 _lib = None

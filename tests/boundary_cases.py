@@ -110,6 +110,7 @@ EXEMPT = {
     "ovmr_create", "ovmr_destroy", "ovmr_last_error", "ovmr_version", "ovmr_set_option", "ovmr_finalize", "ovmr_head_plan", "ovmr_logit_scale",
     "ovmr_encode_chunk", "ovmr_encode_plan", "ovmr_flops_per_image", "ovmr_flops_per_image_executed", "ovmr_flops_executed",
     "ovmr_flops_per_prompt", "ovmr_debug_attention_route", "ovmr_debug_gemm_route", "ovmr_debug_gemm_tile_kernels",
+    "ovmr_debug_fill_workspace",
     # loader.DeviceResizer.run hands in buffers it sizes from its own plan (ovmr_amd/resize.py): no caller's tensor shape is involved
     "ovmr_resize_crop_u8",
     # the kernel-test hooks have no wrapper in the package: the tests that call them size their operands themselves

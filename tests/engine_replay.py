@@ -341,18 +341,42 @@ class Torch(Backend):
 
 class Hooks(Backend):
     """Every step as ONE call of the library's debug hook of that name on device buffers; a non-zero return code raises.  weights: name ->
-    tensor as the library stores it (fp16 / fp32), inputs as the entry point takes them.  Every buffer has PAD elements of slack."""
+    tensor as the library stores it (fp16 / fp32), inputs as the entry point takes them.  Every buffer has PAD elements of slack.
+    fill (a name of poison.FILLS): every buffer instead comes from a poison.Arena under that fill -- the scratch of alloc, and guarded
+    copies of the weights, the inputs and the offset tables --, with one 256-row tile of the widest weight row (4 * width: the widest
+    row of any operand) in front of each operand and behind it, and the operand itself starting as the fill.  Weights handed over as a
+    poison.Placed are guarded already (one copy shared by several replays) and used as they are."""
     PAD = 4096
     KINDS = {"f16": torch.float16, "f32": torch.float32, "i32": torch.int32}
 
-    def __init__(self, lib, weights, inputs, n_cu, device="cuda"):
+    def __init__(self, lib, weights, inputs, n_cu, device="cuda", fill=None):
         super().__init__(n_cu)
-        self.lib, self.device, self.keep = lib, device, []
-        self.buf = {k: v for k, v in weights.items()}
-        self.buf.update({k: v.contiguous().to(device) for k, v in inputs.items()})
+        self.lib, self.device, self.keep, self.arena = lib, device, [], None
+        if fill is None:
+            self.buf = {k: v for k, v in weights.items()}
+            self.buf.update({k: v.contiguous().to(device) for k, v in inputs.items()})
+            return
+        import poison
+        if isinstance(weights, poison.Placed):                # guarded already, by a caller who shares them among replays
+            assert weights.arena.fill == fill and str(weights.arena.device) == str(device)
+            self.arena = poison.Arena(fill, device, weights.arena.guard)
+            self.buf = dict(weights)
+            weights = {}
+        else:
+            self.arena = poison.Arena(fill, device, poison.guard_elems(self.widest_row(weights)))
+            self.buf = {}
+        self.buf.update({k: self.arena.place(v) for k, v in list(weights.items()) + list(inputs.items())})
+
+    @staticmethod
+    def widest_row(weights):
+        """The widest row of any operand: 4 * width, the K of c_proj (and the N of c_fc)."""
+        return max([v.shape[-1] for v in weights.values() if v.dim() >= 1], default=16)
 
     def alloc(self, name, elems, kind="f16"):
-        if name not in self.buf or self.buf[name].numel() < elems + self.PAD:
+        if self.arena is not None:
+            if name not in self.buf or self.buf[name].numel() < elems:
+                self.buf[name] = self.arena.take(elems, kind)
+        elif name not in self.buf or self.buf[name].numel() < elems + self.PAD:
             self.buf[name] = torch.zeros(elems + self.PAD, dtype=self.KINDS[kind], device=self.device)
 
     def p(self, r):
@@ -400,7 +424,8 @@ class Hooks(Backend):
     def _table(self, offsets):
         if offsets is None:
             return None
-        self.keep.append(torch.tensor(offsets, dtype=torch.int32).to(self.device))
+        table = torch.tensor(offsets, dtype=torch.int32)
+        self.keep.append(table.to(self.device) if self.arena is None else self.arena.place(table))
         return ctypes.c_void_p(self.keep[-1].data_ptr())
 
     def attention_f32_varlen(self, qkv, out, offsets, nseq, n_ctx, max_len, H):

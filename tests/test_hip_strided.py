@@ -315,12 +315,25 @@ def _check_attention_q(lib, B, L, Lq, H, variants):
         assert bool(torch.isfinite(out[:B * Lq]).all()), f"{what}: unwritten or non-finite rows"
         got = out[:B * Lq].view(B, Lq, -1)[seqs.cuda()].float().cpu().reshape(len(seqs) * Lq, -1)
         assert float((got - ref).abs().max()) < 6e-3, f"{what}: max err {(got - ref).abs().max()}"
-        if _attn_kernel(variant, L, Lq) == _attn_kernel(variant, L, L):
+        kernel = _attn_kernel(variant, L, Lq)
+        if kernel == _attn_kernel(variant, L, L):
+            # Against the all-query launch, bit for bit.  v1 and v5 move their softmax reference on a ballot over a query tile (16 / 32
+            # rows), and the spare rows of the subset launch's last tile repeat query Lq - 1 -- they must not read the Q slots behind it,
+            # which the last vision block leaves unwritten (test_hip_poison.py).  So: (i) every complete tile equals the all-query
+            # launch on the same qkv (v0 has no ballot: every row does); (ii) EVERY row equals the all-query launch on the qkv whose
+            # Q rows from Lq on repeat row Lq - 1, where the last tile holds the same voters.
+            tile = {"v0": 1, "v1": 16, "v5": 32}[kernel]
+            whole = Lq // tile * tile
+            rep = qkv.clone()
+            rep.view(B, L, -1)[:, Lq:, :H * 64] = rep.view(B, L, -1)[:, Lq - 1:Lq, :H * 64]
             full = torch.empty((B * L, H * 64), dtype=torch.float16, device="cuda")
-            assert lib.ovmr_debug_attention(0, variant, _p(qkv), _p(full), B, L, H, 0, _s()) == 0
-            torch.cuda.synchronize()
-            first = full.view(B, L, -1)[:, :Lq].reshape(B * Lq, -1)
-            assert torch.equal(out[:B * Lq].view(torch.int16), first.view(torch.int16)), f"{what}: != the first Lq rows of the full launch"
+            for src, rows, name in ((qkv, whole, "the same qkv"), (rep, Lq, "the qkv whose Q rows from Lq on repeat row Lq - 1")):
+                assert lib.ovmr_debug_attention(0, variant, _p(src), _p(full), B, L, H, 0, _s()) == 0
+                torch.cuda.synchronize()
+                first = full.view(B, L, -1)[:, :rows]
+                assert torch.equal(out[:B * Lq].view(B, Lq, -1)[:, :rows].view(torch.int16), first.view(torch.int16)), \
+                    f"{what}: != the first {rows} rows of the full launch on {name}"
+            del rep, full
     assert lib.ovmr_debug_attention_q(variants[0], _p(qkv), _p(out), B, L, L + 1, H, 0, _s()) == -2
 
 
@@ -331,7 +344,8 @@ def test_attention_cls_query_only(lib, L, B, H):
     """Lq = 1, the last vision block's CLS query: output row b is sequence b's query 0, against fp64 on the first, middle and last
     sequences, the rows behind B stay sentinel, Lq > L is refused with -2.  Bit-equal to the first row of each sequence of the
     all-query launch wherever both take the same kernel (v0 at L < 128 and under variant 0, v1 under variants 1 / 3 / 5 for L >= 128
-    where the all-query launch does not go to v3 / v5)."""
+    where the all-query launch does not go to v3 / v5) -- for v1, whose tile votes on moving the softmax reference, of the all-query
+    launch in which the tile's other rows repeat the CLS query, as the spare rows of the CLS-only launch do (_check_attention_q)."""
     _check_attention_q(lib, B, L, 1, H, ATTN_VARIANTS)
 
 
@@ -340,7 +354,8 @@ def test_attention_cls_query_only(lib, L, B, H):
 def test_attention_query_subset(lib, L, Lq):
     """Lq in {16, 17, 33, 64}: ragged query tiles of v0 / v1 (16-row tiles) and v5's Lq >= 32 path (32-row tiles, 3- or 4-wave
     workgroups by the tile count).  fp64 and sentinel as above; bit-equal to the all-query launch wherever the kernel is the same --
-    for v5 as well: a query tile's arithmetic does not depend on the workgroup's wave count or on the other tiles."""
+    for v5 as well: a query tile's arithmetic does not depend on the workgroup's wave count or on the other tiles.  The ragged last
+    tile of v1 / v5 is compared with the all-query launch whose rows behind Lq repeat query Lq - 1 (_check_attention_q)."""
     _check_attention_q(lib, 3, L, Lq, 12, ATTN_VARIANTS)
 
 
