@@ -14,6 +14,8 @@ runs the zero-shot trainers of trainers/zsclip.py on the same folder data set, a
 
 ranks the job's classes for UNLABELLED images (a directory, or a text file of paths) instead of the test pass: OUTPUT_DIR/predictions.csv holds
 `image,rank,label,classname,score` (any of the three trainers; `--classifiers` loads a generated file instead of generating again).
+With `--nearest N` (MM_CLS_OP, after a generation in this run or from `--bank`; 1 <= N <= 32) OUTPUT_DIR/neighbours.csv also holds
+`image,rank,label,classname,neighbour,row,exemplar,similarity`: the N nearest exemplars of every (image, predicted class), predictions.csv unchanged.
 
     python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --eval_mode all
 
@@ -319,6 +321,48 @@ def write_predictions(path: str, predictions) -> None:
                 w.writerow([image, rank, label, name, repr(float(score))])
 
 
+MAX_NEAREST = 32              # ovmr_nearest_rows (include/ovmr_hip_nearest.h)
+NEIGHBOUR_COLUMNS = ["image", "rank", "label", "classname", "neighbour", "row", "exemplar", "similarity"]
+
+
+def nearest_neighbours(paths: Sequence[str], indices, similarities, rows, classnames: Sequence[str], exemplar_paths=None):
+    """[(image, class rank, label, classname, neighbour rank, bank row, exemplar path, similarity)] from the [N, k] indices and the
+    [N, k, n] similarities / rows of a prediction pass with --nearest; a class with fewer than n exemplars (row -1) has fewer entries."""
+    out = []
+    for p, cs, ss, rs in zip(paths, indices.tolist(), similarities.tolist(), rows.tolist()):
+        for rank, (c, sv, rv) in enumerate(zip(cs, ss, rs)):
+            for j, (sim, row) in enumerate(zip(sv, rv)):
+                if row >= 0:
+                    out.append((p, rank, int(c), classnames[int(c)], j, int(row), "" if exemplar_paths is None else exemplar_paths[int(row)], float(sim)))
+    return out
+
+
+def write_neighbours(path: str, neighbours) -> None:
+    """neighbours.csv: `image,rank,label,classname,neighbour,row,exemplar,similarity`, one line per (image, class rank, neighbour rank) in
+    input order; the similarity is repr(float), as the score of predictions.csv."""
+    import csv
+    os.makedirs(osp.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, delimiter=",", lineterminator="\n")
+        w.writerow(NEIGHBOUR_COLUMNS)
+        for image, rank, label, name, j, row, exemplar, sim in neighbours:
+            w.writerow([image, rank, label, name, j, row, exemplar, repr(float(sim))])
+
+
+def check_nearest(args, trainer_name: str, zeroshot: bool):
+    """The refusals of `--nearest N`, before anything is listed or loaded."""
+    if args.nearest is None:
+        return
+    if args.predict is None:
+        raise SystemExit("--nearest N belongs to --predict PATH: the nearest exemplars of every predicted class")
+    if zeroshot:
+        raise SystemExit(f"--nearest: --trainer {trainer_name} has no exemplars to search (MM_CLS_OP only; a zero-shot trainer's classifier rows are text features)")
+    if args.classifiers:
+        raise SystemExit(f"--nearest: --classifiers {args.classifiers!r} holds no exemplar features (generate in this run, or start from --bank)")
+    if not 1 <= args.nearest <= MAX_NEAREST:
+        raise SystemExit(f"--nearest {args.nearest}: N must lie in [1, {MAX_NEAREST}]")
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     # the reference's flags, with the reference's defaults (train.py:183-255)
@@ -362,6 +406,8 @@ def parse(argv=None):
     ap.add_argument("--predict", metavar="PATH", default=None, help="ranked prediction on UNLABELLED images instead of the test pass: a directory "
                     "(every image file below it, sorted by path) or a text file with one image path per line; writes OUTPUT_DIR/predictions.csv")
     ap.add_argument("--topk", type=int, default=None, metavar="K", help="classes per image of --predict, best first (default 5; 1 <= K <= min(32, classes))")
+    ap.add_argument("--nearest", type=int, default=None, metavar="N", help="with --predict --trainer MM_CLS_OP: also write OUTPUT_DIR/neighbours.csv, the N "
+                    "nearest exemplars of every (image, predicted class) (1 <= N <= 32; after a generation in this run, or from --bank)")
     ap.add_argument("--classifiers", metavar="FILE", default="", help="with --predict --trainer MM_CLS_OP: load this mm_classifiers.pt instead of "
                     "generating the classifiers (no exemplar is decoded, no model file is written)")
     ap.add_argument("--save-bank", action="store_true", help="MM_CLS_OP generation: also write OUTPUT_DIR/reference_bank.pt (ovmr_amd/bank.py), "
@@ -580,6 +626,7 @@ def main(argv=None) -> Dict[str, float]:
     if args.bank and not osp.isfile(args.bank):
         raise SystemExit(f"--bank {args.bank!r}: no such file")
     predict, images, k = args.predict is not None, [], None
+    check_nearest(args, cfg.TRAINER.NAME, zeroshot)
     if predict and cfg.EVAL_MODE == "all" and not zeroshot:
         raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
     if predict:
@@ -740,11 +787,24 @@ def main(argv=None) -> Dict[str, float]:
             from . import bank as bank_format
             tr.model.save_bank(osp.join(cfg.OUTPUT_DIR, bank_format.BANK_FILE), exemplar_paths=_label_order_paths(exemplars))
     if predict:
-        values, indices = tr.predict(test_loader, k)
+        if args.nearest is not None:
+            values, indices, sims, rows = tr.predict_explained(test_loader, k, args.nearest)
+        else:
+            values, indices = tr.predict(test_loader, k)
         results = {"predictions": ranked_predictions(images, values, indices, classnames)}
         out_csv = osp.join(cfg.OUTPUT_DIR, "predictions.csv")
         write_predictions(out_csv, results["predictions"])
         print(f"=> top-{k} predictions of {len(images):,} images: {out_csv}")
+        if args.nearest is not None:
+            # one path per bank row in label order: the bank's own (after the edits), or this run's exemplar items
+            per_class = tr.model._exemplar_paths
+            bank_paths = [p for ps in per_class for p in ps] if per_class is not None else (_label_order_paths(exemplars) if exemplars else None)
+            if bank_paths is not None and len(bank_paths) != tr.model._exemplar_bank()[0].shape[0]:
+                bank_paths = None                             # (no path per row: the column stays empty)
+            results["neighbours"] = nearest_neighbours(images, indices, sims, rows, classnames, bank_paths)
+            out_csv = osp.join(cfg.OUTPUT_DIR, "neighbours.csv")
+            write_neighbours(out_csv, results["neighbours"])
+            print(f"=> the {args.nearest} nearest exemplars of every predicted class: {out_csv}")
     else:
         tr.test()
         results = dict(tr.results)

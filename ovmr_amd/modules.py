@@ -887,7 +887,9 @@ class CustomCLIP(_TwoInFlight):
     __call__ = forward
 
     def _forward_on(self, engine: Engine, image, out=None):
-        image_features = engine.encode_image(image, normalize=True)                # :305-307
+        return self._head_on(engine, engine.encode_image(image, normalize=True), out)       # :305-307
+
+    def _head_on(self, engine: Engine, image_features, out=None):
         mode = self.cfg.EVAL_MODE
         if mode not in ("text", "vision", "multimodal", "fusion", "all"):
             raise ValueError(f"unknown EVAL_MODE {mode}")
@@ -954,6 +956,86 @@ class CustomCLIP(_TwoInFlight):
         self._one_mode("predict_topk_batches")               # (raised by the call, not by the first next())
         outs = self.forward_batches(batches, eval_set_loader=eval_set_loader, overlap=overlap, stable_inputs=stable_inputs)
         return (self._topk(out, k) for out in outs)
+
+    # ------------------------------------------------------------------ nearest exemplars (no counterpart in the reference's API)
+    MAX_NEAREST = 32              # ovmr_nearest_rows (include/ovmr_hip_nearest.h)
+
+    def _exemplar_bank(self):
+        """(bank [R, D] fp16, starts int64 [C + 1] on the device): the exemplar features class after class in label order -- the uniform
+        [C, S, D] store viewed as [C S, D], the packed store as it is once its rows are in label order (load_bank and the edits leave it
+        so; a ragged generation's loader order is sorted once and kept) -- and the prefix sum of the classes' shots."""
+        src, lab = self.eval_feat4cls, getattr(self, "eval_row_labels", None)
+        kept = self.__dict__.get("_nearest_bank")
+        if kept is not None and kept[0] is src and kept[1] is lab:
+            return kept[2], kept[3]
+        if lab is None:
+            C, S, D = src.shape
+            bank, shots = src.reshape(C * S, D), torch.full((C,), S, dtype=torch.int64)
+        else:
+            per_class = self._class_rows()
+            bank, shots = torch.cat(per_class).contiguous(), torch.tensor([int(r.shape[0]) for r in per_class], dtype=torch.int64)
+        starts = torch.cat([torch.zeros(1, dtype=torch.int64), shots.cumsum(0)]).to(self.device)
+        self._nearest_bank = (src, lab, bank, starts)
+        return bank, starts
+
+    @torch.no_grad()
+    def nearest_exemplars(self, feats_or_image, k: int, classes=None):
+        """The k exemplars nearest to every query, by h(query . exemplar) on the L2-normalised features (ovmr_nearest_rows, one fused
+        launch pair on the current stream).  feats_or_image: image features [B, D] fp16 on the device (what engine.encode_image(...,
+        normalize=True) returns), or an image batch [B, 3, R, R], which is encoded.  1 <= k <= 32.
+        classes None: the whole bank -> (values fp32 [B, k], rows int64 [B, k], labels int64 [B, k]); rows index the bank's `features`
+        (and its exemplar_paths), labels are the rows' classes.
+        classes int64 [B] or [B, m] (host or device; [B] is m = 1): the nearest exemplars INSIDE each named class, one launch over B m
+        queries -> three [B, m, k] tensors.  A class with fewer than k exemplars fills its tail with value -inf, row -1, label -1."""
+        from . import runtime
+        self._needs_state("nearest_exemplars")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= self.MAX_NEAREST:
+            raise ValueError(f"nearest_exemplars: k must be an integer in [1, {self.MAX_NEAREST}], got {k!r}")
+        k = int(k)
+        bank, starts = self._exemplar_bank()
+        if k > bank.shape[0]:
+            raise ValueError(f"nearest_exemplars: k = {k} exceeds the bank's {bank.shape[0]} exemplar rows")
+        feats = feats_or_image
+        if isinstance(feats, (torch.Tensor, np.ndarray)) and feats.ndim == 4:
+            feats = self.engine.encode_image(feats, normalize=True)
+        runtime._want("nearest_exemplars", "feats_or_image", feats, (None, bank.shape[1]), torch.float16, self.device)
+        B, C = feats.shape[0], starts.shape[0] - 1
+        if classes is None:
+            values, rows = runtime.nearest_rows(feats, bank, k)
+            rows = rows.long()
+            labels = torch.searchsorted(starts[1:], rows, right=True)
+            return values, rows, torch.where(rows >= 0, labels, rows)
+        runtime._want("nearest_exemplars", "classes", classes)
+        classes = torch.as_tensor(classes)
+        if classes.dtype != torch.int64 or classes.ndim not in (1, 2) or classes.shape[0] != B:
+            raise ValueError(f"nearest_exemplars: classes must be int64 [{B}] or [{B}, m], got {classes.dtype} {list(classes.shape)}")
+        runtime._want_range("nearest_exemplars", "classes", classes, 0, C, "class labels")
+        classes = classes.to(self.device).reshape(B, -1)
+        m = classes.shape[1]
+        flat = classes.reshape(-1).clamp(0, C - 1)           # (device values are the caller's contract: clamped, so that nothing reads outside `starts`)
+        ranges = torch.stack([starts[flat], starts[flat + 1]], 1).to(torch.int32)
+        values, rows = runtime.nearest_rows(feats.repeat_interleave(m, 0) if m != 1 else feats, bank, k, ranges)
+        rows = rows.long().view(B, m, k)
+        return values.view(B, m, k), rows, torch.where(rows >= 0, classes[:, :, None].expand(B, m, k), rows)
+
+    @torch.no_grad()
+    def predict_explained(self, image, k: int, n: int, eval_set_loader=None):
+        """predict_topk with its evidence: the image is encoded ONCE, the head and ovmr_topk_rows run on those features as in predict_topk,
+        then nearest_exemplars(features, n, classes = the k predicted classes) on the same stream.  Returns (values fp32 [B, k], indices
+        int64 [B, k], similarities fp32 [B, k, n], rows int64 [B, k, n]): the first two are predict_topk's, bit for bit; rows index the
+        bank's features / exemplar_paths, -1 (similarity -inf) where a class has fewer than n exemplars."""
+        self._one_mode("predict_explained")
+        if self.mm_classifier is None:
+            if eval_set_loader is None:
+                raise ValueError("predict_explained: the model has no classifiers yet (pass eval_set_loader=, or load_bank)")
+            self.forward_prompt(eval_set_loader, wait_files=False)
+        self._needs_state("predict_explained")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= self.MAX_NEAREST:
+            raise ValueError(f"predict_explained: n must be an integer in [1, {self.MAX_NEAREST}], got {n!r}")
+        feats = self.engine.encode_image(image, normalize=True)
+        values, indices = self._topk(self._head_on(self.engine, feats), k)
+        sims, rows, _ = self.nearest_exemplars(feats, int(n), classes=indices)
+        return values, indices, sims, rows
 
     @torch.no_grad()
     def load_classifiers(self, path: str):

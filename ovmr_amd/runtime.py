@@ -104,6 +104,13 @@ SIGNATURES = {
     "ovmr_debug_fill_workspace": (c_i, [c_p, ctypes.c_uint32, c_p]),
 }
 
+# the extension header include/ovmr_hip_nearest.h, mirrored the same way (tests/test_nearest_cpu.py holds the pair to each other)
+EXT_SIGNATURES = {
+    "ovmr_nearest_scratch_bytes": (ctypes.c_long, [c_i, ctypes.c_long, c_i]),
+    "ovmr_nearest_rows": (c_i, [c_p, c_i, c_p, ctypes.c_long, c_i, c_i, c_p, c_p, c_p, c_p, ctypes.c_long, c_p]),
+    "ovmr_debug_nearest_rows": (c_i, [c_p, c_i, c_p, ctypes.c_long, c_i, c_i, c_p, c_p, c_p, c_p, ctypes.c_long, c_i, c_p]),
+}
+
 _lib = None
 
 
@@ -117,7 +124,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         raise RuntimeError(f"{p} not found: build it with `python -m ovmr_amd.build` (hipcc, gfx950). "
                            "ovmr_amd has no CPU fallback.")
     lib = ctypes.CDLL(p)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -246,6 +253,70 @@ def eval_detail(mo: torch.Tensor, labels: torch.Tensor, k: int, counts: torch.Te
                                   ctypes.c_void_p(torch.cuda.current_stream(mo.device).cuda_stream))
     if rc != 0:
         raise OvmrError(f"ovmr_eval_detail failed with {rc} (B = {B}, C = {C}, k = {k})")
+
+
+_nearest_scratch: Dict[torch.device, torch.Tensor] = {}          # per device: the scratch of nearest_rows, grown on demand
+
+
+def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Optional[torch.Tensor] = None, out=None):
+    """ovmr_nearest_rows on the current stream (include/ovmr_hip_nearest.h): queries [B, D] and bank [R, D], fp16 on the GPU, D a multiple of
+    64 in [64, 1024], 1 <= k <= min(R, 32) -> (values fp32 [B, k], indices int32 [B, k]): per query the k bank rows of largest
+    h(queries[b] . bank[r]), best first in the library's total order, equal scores to the lower row.  ranges int32 [B, 2] (lo, hi): query b
+    looks at the rows lo <= r < hi only; fewer than k of them leave a tail of index -1, value -inf.  Host ranges are checked
+    (0 <= lo <= hi <= R) and copied; device ranges are the caller's contract (the kernel clamps what it reads).  A strided queries / bank /
+    ranges view is made contiguous.  out: (values, indices) to write into.  The scratch is one cached buffer per device: calls are
+    ordered on one stream, like everything that shares a workspace."""
+    where = "nearest_rows"
+    _want(where, "queries", queries, (None, None), torch.float16, "cuda")
+    _want(where, "bank", bank, (None, None), torch.float16, queries.device)
+    B, D = queries.shape
+    R = bank.shape[0]
+    if bank.shape[1] != D:
+        _refuse(where, "bank", f"of shape [*, {D}] (the queries' width)", f"{list(bank.shape)}")
+    if D % 64 or not 64 <= D <= 1024:
+        _refuse(where, "queries", "of a width that is a multiple of 64 in [64, 1024]", f"{list(queries.shape)}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= min(R, 32):
+        _refuse(where, "k", f"an integer in [1, {min(R, 32)}]", repr(k))
+    k = int(k)
+    if ranges is not None:
+        _want(where, "ranges", ranges, (B, 2))
+        if isinstance(ranges, np.ndarray):
+            ranges = torch.from_numpy(ranges)
+        if ranges.is_floating_point() or ranges.is_complex() or ranges.dtype == torch.bool:
+            _refuse(where, "ranges", "of an integer dtype", str(ranges.dtype))
+        if not ranges.is_cuda:
+            _want_range(where, "ranges", ranges, 0, R + 1, "row bounds")
+            if ranges.numel() and bool((ranges[:, 0] > ranges[:, 1]).any()):
+                _refuse(where, "ranges", "pairs lo <= hi", "a pair with lo > hi")
+        elif not _same_device(ranges.device, queries.device):
+            _refuse(where, "ranges", f"on {queries.device} or on the host", f"a tensor on {ranges.device}")
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            _refuse(where, "out", "a pair (values, indices)", type(out).__name__)
+        _want(where, "out[0]", out[0], (B, k), torch.float32, queries.device, dense=True)
+        _want(where, "out[1]", out[1], (B, k), torch.int32, queries.device, dense=True)
+    lib = load_library()
+    dev = queries.device
+    with torch.cuda.device(dev):
+        queries, bank = queries.contiguous(), bank.contiguous()
+        if ranges is not None:
+            ranges = ranges.to(dev, torch.int32).contiguous()
+        values, indices = out if out is not None else (torch.empty((B, k), dtype=torch.float32, device=dev),
+                                                        torch.empty((B, k), dtype=torch.int32, device=dev))
+        if B == 0:
+            return values, indices
+        need = int(lib.ovmr_nearest_scratch_bytes(B, R, k))
+        if need < 0:
+            raise OvmrError(f"ovmr_nearest_scratch_bytes refuses B = {B}, R = {R}, k = {k}")
+        key = torch.device(dev.type, torch.cuda.current_device())
+        scratch = _nearest_scratch.get(key)
+        if scratch is None or scratch.numel() * 8 < need:
+            scratch = _nearest_scratch[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+        rc = lib.ovmr_nearest_rows(_ptr(queries), B, _ptr(bank), R, D, k, _ptr(ranges), _ptr(values), _ptr(indices), _ptr(scratch),
+                                   scratch.numel() * 8, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise OvmrError(f"ovmr_nearest_rows failed with {rc} (B = {B}, R = {R}, D = {D}, k = {k})")
+    return values, indices
 
 
 class Engine:

@@ -218,6 +218,23 @@ class _EvalTrainer:
             return torch.zeros((0, k), dtype=torch.float32), torch.zeros((0, k), dtype=torch.int64)
         return torch.cat([v for v, _ in pairs]).cpu(), torch.cat([i for _, i in pairs]).cpu()
 
+    NO_EXEMPLARS = "nearest exemplars need a model that holds exemplar features (MM_CLS_OP only; a zero-shot trainer's classifier rows are text features)"
+
+    def explained(self, inputs, k, n):
+        """predict_explained for every input batch, in order: (values, indices, similarities, rows) per batch."""
+        raise ValueError(f"--trainer {self.cfg.TRAINER.NAME}: {self.NO_EXEMPLARS}")
+
+    @torch.no_grad()
+    def predict_explained(self, data_loader, k: int = 5, n: int = 3):
+        """predict() with the n nearest exemplars of every (image, predicted class): (values fp32 [N, k], indices int64 [N, k],
+        similarities fp32 [N, k, n], rows int64 [N, k, n]) on the host, rows in loader order -- the first two are predict()'s."""
+        outs = list(self.explained((self.parse_batch_test(batch)[0] for batch in data_loader), k, n))
+        self.after_test()
+        if not outs:
+            return (torch.zeros((0, k), dtype=torch.float32), torch.zeros((0, k), dtype=torch.int64),
+                    torch.zeros((0, k, n), dtype=torch.float32), torch.zeros((0, k, n), dtype=torch.int64))
+        return tuple(torch.cat([o[i] for o in outs]).cpu() for i in range(4))
+
     def forward_backward(self, batch):
         raise NotImplementedError(self.NOT_TRAINED)
 
@@ -274,6 +291,9 @@ class MM_CLS_OP(_EvalTrainer):
 
     def ranked(self, inputs, k):
         return self.model.predict_topk_batches(inputs, k, eval_set_loader=self.eval_set_loader)
+
+    def explained(self, inputs, k, n):
+        return (self.model.predict_explained(image, k, n, eval_set_loader=self.eval_set_loader) for image in inputs)
 
     def after_test(self):
         self.model.wait_files()                      # mm_classifiers.pt / visual_tokens.pt were written while the test set ran
