@@ -17,6 +17,12 @@ ranks the job's classes for UNLABELLED images (a directory, or a text file of pa
 With `--nearest N` (MM_CLS_OP, after a generation in this run or from `--bank`; 1 <= N <= 32) OUTPUT_DIR/neighbours.csv also holds
 `image,rank,label,classname,neighbour,row,exemplar,similarity`: the N nearest exemplars of every (image, predicted class), predictions.csv unchanged.
 
+    python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --bank OUT/reference_bank.pt --audit-bank 5 [--dup-threshold T]
+
+audits the exemplar features themselves: OUTPUT_DIR/bank_audit.csv (one line per exemplar: its nearest class-mate, its nearest image of
+another class, `suspect` where the latter is strictly closer, `duplicate_of`), bank_audit_neighbours.csv and bank_audit_classes.csv.  From
+`--bank` alone nothing is decoded or encoded and no `--root` is needed; it also runs after a generation or an edit, and next to `--predict`.
+
     python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --eval_mode all
 
 evaluates the four modes of the reference's result tables (fusion, text, vision, multimodal; trainers/mm_classifier_one_prompt.py:348-363)
@@ -363,6 +369,60 @@ def check_nearest(args, trainer_name: str, zeroshot: bool):
         raise SystemExit(f"--nearest {args.nearest}: N must lie in [1, {MAX_NEAREST}]")
 
 
+AUDIT_COLUMNS = ["row", "label", "classname", "exemplar", "in_row", "in_similarity", "out_row", "out_label", "out_classname", "out_similarity",
+                 "suspect", "duplicate_of"]
+AUDIT_NEIGHBOUR_COLUMNS = ["row", "side", "rank", "neighbour_row", "neighbour_label", "similarity"]
+AUDIT_CLASS_COLUMNS = ["label", "classname", "exemplars", "suspects", "duplicates"]
+AUDIT_FILES = ("bank_audit.csv", "bank_audit_neighbours.csv", "bank_audit_classes.csv")
+
+
+def bank_audit_tables(audit: dict, classnames: Sequence[str], shots: Sequence[int], exemplar_paths=None):
+    """The three tables of `--audit-bank` from CustomCLIP.audit_bank's tensors (host or device): one line per exemplar (its first
+    neighbour on either side; a missing one is row -1, label -1, an empty class name, similarity -inf), one per (exemplar, side, rank)
+    for the neighbours that exist, one per class."""
+    a = {k: v.cpu().tolist() for k, v in audit.items()}
+    rows, neighbours = [], []
+    for i, (row, label) in enumerate(zip(a["rows"], a["labels"])):
+        ir, isim, orow, olab, osim = a["in_row"][i], a["in_sim"][i], a["out_row"][i], a["out_label"][i], a["out_sim"][i]
+        rows.append((row, label, classnames[label], "" if exemplar_paths is None else exemplar_paths[row], ir[0], float(isim[0]), orow[0], olab[0],
+                     classnames[olab[0]] if olab[0] >= 0 else "", float(osim[0]), int(bool(a["suspect"][i])), a["duplicate_of"][i]))
+        for side, rs, ls, ss in (("in", ir, [label] * len(ir), isim), ("out", orow, olab, osim)):
+            neighbours += [(row, side, j, r, l, float(v)) for j, (r, l, v) in enumerate(zip(rs, ls, ss)) if r >= 0]
+    classes = [(c, classnames[c], int(shots[c]), a["class_suspects"][c], a["class_duplicates"][c]) for c in range(len(classnames))]
+    return rows, neighbours, classes
+
+
+def write_bank_audit(out_dir: str, tables) -> None:
+    """bank_audit.csv, bank_audit_neighbours.csv and bank_audit_classes.csv in out_dir; similarities are repr(float), as the score of
+    predictions.csv."""
+    import csv
+    os.makedirs(out_dir or ".", exist_ok=True)
+    for name, cols, lines, floats in zip(AUDIT_FILES, (AUDIT_COLUMNS, AUDIT_NEIGHBOUR_COLUMNS, AUDIT_CLASS_COLUMNS), tables, ((5, 9), (5,), ())):
+        with open(osp.join(out_dir, name), "w", newline="") as f:
+            w = csv.writer(f, delimiter=",", lineterminator="\n")
+            w.writerow(cols)
+            for line in lines:
+                w.writerow([repr(float(x)) if i in floats else x for i, x in enumerate(line)])
+
+
+def check_audit(args, trainer_name: str, zeroshot: bool):
+    """The refusals of `--audit-bank [K]` / `--dup-threshold T`, before anything is listed or loaded."""
+    if args.audit_bank is None:
+        if args.dup_threshold is not None:
+            raise SystemExit("--dup-threshold T belongs to --audit-bank [K]: the similarity from which a neighbour counts as a duplicate")
+        return
+    if zeroshot:
+        raise SystemExit(f"--audit-bank: --trainer {trainer_name} has no exemplars to audit (MM_CLS_OP only; a zero-shot trainer's classifier rows are text features)")
+    if args.classifiers:
+        raise SystemExit(f"--audit-bank: --classifiers {args.classifiers!r} holds no exemplar features (generate in this run, or start from --bank)")
+    if not 1 <= args.audit_bank <= MAX_NEAREST:
+        raise SystemExit(f"--audit-bank {args.audit_bank}: K must lie in [1, {MAX_NEAREST}]")
+    if args.dup_threshold is not None and args.dup_threshold != args.dup_threshold:
+        raise SystemExit("--dup-threshold nan: T must be a number")
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--audit-bank runs in one process: a sharded rank holds only its own classes' exemplar features")
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     # the reference's flags, with the reference's defaults (train.py:183-255)
@@ -408,6 +468,16 @@ def parse(argv=None):
     ap.add_argument("--topk", type=int, default=None, metavar="K", help="classes per image of --predict, best first (default 5; 1 <= K <= min(32, classes))")
     ap.add_argument("--nearest", type=int, default=None, metavar="N", help="with --predict --trainer MM_CLS_OP: also write OUTPUT_DIR/neighbours.csv, the N "
                     "nearest exemplars of every (image, predicted class) (1 <= N <= 32; after a generation in this run, or from --bank)")
+    ap.add_argument("--audit-bank", type=int, nargs="?", const=5, default=None, metavar="K", help="MM_CLS_OP: audit the exemplar features -- every "
+                    "exemplar's K (default 5; 1 <= K <= 32) nearest neighbours inside its class (itself left out) and outside it -- and write "
+                    "OUTPUT_DIR/bank_audit.csv (one line per exemplar: `suspect` = the closest image of another class is strictly closer than the "
+                    "closest class-mate; `duplicate_of` = the best neighbour where its similarity reaches --dup-threshold), bank_audit_neighbours.csv "
+                    "and bank_audit_classes.csv.  From --bank FILE without --predict or an edit nothing else runs: nothing is decoded or encoded "
+                    "and no --root is needed; otherwise the audit runs on the state at the end of the generation or the edit, before --predict "
+                    "or the test pass")
+    ap.add_argument("--dup-threshold", type=float, default=None, metavar="T", help="with --audit-bank: a neighbour of similarity >= T is reported as a "
+                    "duplicate (default 0.995: an fp16 L2-normalised feature scores a byte-identical copy at least 0.9990, so copies are always "
+                    "found; re-compressed near-duplicates need a lower value, which nobody has measured on real images)")
     ap.add_argument("--classifiers", metavar="FILE", default="", help="with --predict --trainer MM_CLS_OP: load this mm_classifiers.pt instead of "
                     "generating the classifiers (no exemplar is decoded, no model file is written)")
     ap.add_argument("--save-bank", action="store_true", help="MM_CLS_OP generation: also write OUTPUT_DIR/reference_bank.pt (ovmr_amd/bank.py), "
@@ -627,6 +697,8 @@ def main(argv=None) -> Dict[str, float]:
         raise SystemExit(f"--bank {args.bank!r}: no such file")
     predict, images, k = args.predict is not None, [], None
     check_nearest(args, cfg.TRAINER.NAME, zeroshot)
+    check_audit(args, cfg.TRAINER.NAME, zeroshot)
+    audit_only = args.audit_bank is not None and bool(args.bank) and not edits and not predict      # the bank alone: no data set, no test pass
     if predict and cfg.EVAL_MODE == "all" and not zeroshot:
         raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
     if predict:
@@ -696,7 +768,7 @@ def main(argv=None) -> Dict[str, float]:
             raise SystemExit(f"--bank {args.bank!r}: the bank holds no class names (it was written by a model built from token rows)")
         plan = plan_vocabulary_edits(args, bank_obj["classnames"], shots, seed, ragged)
         classnames, exemplars, test_items = plan[3], [], []
-        if not predict:                                       # the data set the test pass runs on must speak of the same classes
+        if not predict and not audit_only:                    # the data set the test pass runs on must speak of the same classes
             set_names, _, test_items = build_splits(split_cfg, args.eval_split, args.test_split, "", False)
             diff = bank_format.first_difference(classnames, set_names)
             if diff is not None:
@@ -786,7 +858,28 @@ def main(argv=None) -> Dict[str, float]:
         if args.save_bank:
             from . import bank as bank_format
             tr.model.save_bank(osp.join(cfg.OUTPUT_DIR, bank_format.BANK_FILE), exemplar_paths=_label_order_paths(exemplars))
-    if predict:
+    audit_tables = None
+    if args.audit_bank is not None:
+        m = tr.model
+        try:
+            audit = m.audit_bank(args.audit_bank, dup_threshold=0.995 if args.dup_threshold is None else args.dup_threshold)
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        n_rows = m._exemplar_bank()[0].shape[0]
+        per_class = m._exemplar_paths
+        bank_paths = [p for ps in per_class for p in ps] if per_class is not None else (_label_order_paths(exemplars) if exemplars else None)
+        if bank_paths is not None and len(bank_paths) != n_rows:
+            bank_paths = None                                 # (no path per row: the column stays empty)
+        starts, _ = m._bank_starts_host()
+        audit_tables = bank_audit_tables(audit, classnames, [b - a for a, b in zip(starts, starts[1:])], bank_paths)
+        write_bank_audit(cfg.OUTPUT_DIR, audit_tables)
+        suspects, dups = sum(r[10] for r in audit_tables[0]), sum(r[11] >= 0 for r in audit_tables[0])
+        print(f"=> bank audit: {len(audit_tables[0]):,} exemplars, {suspects:,} suspects in {sum(c[3] > 0 for c in audit_tables[2]):,} classes, "
+              f"{dups:,} duplicates")
+        print(f"=> {', '.join(osp.join(cfg.OUTPUT_DIR, n) for n in AUDIT_FILES)}")
+    if audit_only:
+        results = {}
+    elif predict:
         if args.nearest is not None:
             values, indices, sims, rows = tr.predict_explained(test_loader, k, args.nearest)
         else:
@@ -812,7 +905,10 @@ def main(argv=None) -> Dict[str, float]:
         _report_pipeline(results, "exemplar set", eval_loader)
     for key, ld in edit_loaders.items():
         _report_pipeline(results, f"{key} set", ld)
-    _report_pipeline(results, "predict set" if predict else "test set", test_loader)
+    if not audit_only:
+        _report_pipeline(results, "predict set" if predict else "test set", test_loader)
+    if audit_tables is not None:
+        results["bank_audit"] = {"exemplars": audit_tables[0], "neighbours": audit_tables[1], "classes": audit_tables[2]}
     results["classnames"] = classnames
     if test_loader.batch_shard is not None:
         results["test_shard"] = {"rank": rank, "world": world, "batches": list(test_loader.batch_range), "images": len(test_loader.items)}

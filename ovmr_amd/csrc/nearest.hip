@@ -25,10 +25,16 @@
 // stores index and value (decoded from the key) coalesced.  No atomics on global memory, no counters, nothing to re-arm: the scratch is
 // written completely before it is read.
 //
+// include/ovmr_hip_audit.h adds an excluded row range per query: nearest_tiles_kernel<QB, EXCL = true> keeps the clamped exclusions beside the
+// ranges in LDS and turns excluded candidates into key 0 (the instantiations without EXCL are the code they were), and ovmr_neighbours_rows
+// takes the one-wave-per-query launch of neighbours.hip where the host promises short ranges.  The list helpers live in nearest_list.h.
+//
 // Registers (hipcc -O3, gfx950, --save-temps): see DESIGN.md section 4.
 #include "../../include/ovmr_hip_nearest.h"
+#include "../../include/ovmr_hip_audit.h"
 #include "common.h"
 #include "eval_common.h"
+#include "nearest_list.h"
 
 #include <algorithm>
 
@@ -40,55 +46,26 @@ typedef unsigned long long key_t;
 constexpr int NR_BN = 256;                  // bank rows per tile: 4 waves x 64
 constexpr int NR_SLD = NR_BN + 4;           // score tile row stride in halves (8-byte aligned rows)
 constexpr int NR_KMAX = 32;
+constexpr int NB_MAX_RANGE = 4096;          // ovmr_neighbours_rows: the ceiling of max_range, the project's ceiling for a class (agg_max_len)
 constexpr int NR_CUS = 256;                 // the launcher's S is a pure function of B and R (ovmr_nearest_scratch_bytes): no device query
 
-__device__ __forceinline__ key_t wave_read_key(key_t v, int lane) { return (key_t)wave_read((long)v, lane); }
-
-// The sorted list of one query: lane j < k holds the key of rank j (descending; 0 = empty), lanes >= k hold 0.  Inserts the (wave-uniform)
-// key c > 0, which differs from every key in the list; the last key falls off a full list.
-__device__ __forceinline__ void list_insert(key_t& mine, key_t c, int lane, int k) {
-    const int pos = (int)__builtin_popcountll(__builtin_amdgcn_ballot_w64(mine > c));
-    const unsigned lo = __shfl_up((unsigned)mine, 1, 64), hi = __shfl_up((unsigned)(mine >> 32), 1, 64);
-    const key_t up = ((key_t)hi << 32) | lo;
-    if (lane == pos) mine = c;
-    else if (lane > pos) mine = up;
-    if (lane >= k) mine = 0;
-}
-
-// Every candidate (one per lane, 0 = none) that belongs among the k best enters the list.  Returns whether the list changed.
-__device__ __forceinline__ bool list_offer(key_t& mine, key_t cand, int lane, int k) {
-    key_t thr = wave_read_key(mine, k - 1);                        // the k-th best (0 while the list is not full)
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(cand > thr);
-    const bool any = todo != 0;
-    while (todo) {
-        const int src = __builtin_ctzll(todo);
-        list_insert(mine, wave_read_key(cand, src), lane, k);
-        thr = wave_read_key(mine, k - 1);
-        todo &= todo - 1;
-        todo &= __builtin_amdgcn_ballot_w64(cand > thr);           // the threshold rose: fewer survive
-    }
-    return any;
-}
-
-// the value a key was built from (topk_key inverted): NaN for every NaN, +0 for either zero
-__device__ __forceinline__ float key_value(key_t key) {
-    const unsigned u = (unsigned)(key >> 32);
-    if (u == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
-    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
-}
+using ovmr_list::wave_read_key; using ovmr_list::list_insert; using ovmr_list::list_offer; using ovmr_list::key_value;   // nearest_list.h
 
 struct NearestArgs {
     const half_t* Q; const half_t* X; const int32_t* ranges; key_t* scratch;
     int B, D, k, S;
     unsigned R, Tq;
     int tiles_per_slice;
+    const int32_t* exclude;                     // EXCL instantiations only (last: the other fields keep their places)
 };
 
-size_t nearest_lds_bytes(int BM, int D) {
-    return (size_t)BM * NR_KMAX * 8 + (size_t)BM * (D + 8) * 2 + (size_t)BM * NR_SLD * 2 + (size_t)BM * 2 * 4;
+size_t nearest_lds_bytes(int BM, int D, bool excl = false) {
+    return (size_t)BM * NR_KMAX * 8 + (size_t)BM * (D + 8) * 2 + (size_t)BM * NR_SLD * 2 + (size_t)BM * (excl ? 4 : 2) * 4;
 }
 
-template <int QB>
+// EXCL: query b also leaves out the rows xlo <= r < xhi of a.exclude (ovmr_neighbours_rows).  Exclusion only turns candidates into key 0:
+// the "meets" and tile-skip tests below look at the ranges alone and stay correct, because they over-approximate.
+template <int QB, bool EXCL = false>
 __global__ __launch_bounds__(256) void nearest_tiles_kernel(const NearestArgs a) {
     constexpr int BM = 32 * QB;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -98,6 +75,8 @@ __global__ __launch_bounds__(256) void nearest_tiles_kernel(const NearestArgs a)
     half_t* sc = sq + (size_t)BM * ldq;                             // [BM][NR_SLD] fp16 scores of the current tile
     unsigned* qlo = (unsigned*)(sc + (size_t)BM * NR_SLD);          // [BM], then qhi [BM]
     unsigned* qhi = qlo + BM;
+    unsigned* qxlo = qhi + BM;                                      // [BM], then qxhi [BM]: EXCL only
+    unsigned* qxhi = qxlo + BM;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 31, h = lane >> 5;
@@ -140,6 +119,17 @@ __global__ __launch_bounds__(256) void nearest_tiles_kernel(const NearestArgs a)
     const unsigned t_beg = std::max(s0, wlo) / NR_BN * NR_BN, t_end = std::min(s1, whi);   // s0 is a multiple of the tile: so is t_beg >= s0
 
     if (wave == 0 && lane < BM) { qlo[lane] = lo; qhi[lane] = hi; }
+    if constexpr (EXCL) {
+        if (wave == 1 && lane < BM) {                               // clamped like the range; rows past B: empty
+            unsigned xlo = 0, xhi = 0;
+            if (q0 + lane < a.B) {
+                const long l = a.exclude[2 * (long)(q0 + lane)], u = a.exclude[2 * (long)(q0 + lane) + 1];
+                xlo = (unsigned)std::min<long>(std::max<long>(l, 0), (long)R);
+                xhi = (unsigned)std::min<long>(std::max<long>(u, (long)xlo), (long)R);
+            }
+            qxlo[lane] = xlo; qxhi[lane] = xhi;
+        }
+    }
     for (int i = tid; i < BM * NR_KMAX; i += 256) list[i] = 0;
     for (int i = tid; i < BM * (D / 8); i += 256) {
         const int row = i / (D / 8), ch = i % (D / 8);
@@ -215,13 +205,17 @@ __global__ __launch_bounds__(256) void nearest_tiles_kernel(const NearestArgs a)
             const int q = wave * (BM / 4) + qi;
             const unsigned long long ql = qlo[q], qh = qhi[q];
             if (std::max<unsigned long long>(ql, t0) >= std::min<unsigned long long>(qh, (unsigned long long)t0 + NR_BN)) continue;   // (wave-uniform)
+            unsigned long long xl = 0, xh = 0;
+            if constexpr (EXCL) { xl = qxlo[q]; xh = qxhi[q]; }
             key_t mine = lane < NR_KMAX ? list[q * NR_KMAX + lane] : 0;
             const half4_t sv = *(const half4_t*)(sc + q * NR_SLD + lane * 4);
             bool changed = false;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned long long r = (unsigned long long)t0 + lane * 4 + e;
-                const key_t cand = (r >= ql && r < qh) ? topk_key((float)sv[e], (int)(unsigned)r) : 0;
+                bool in = r >= ql && r < qh;
+                if constexpr (EXCL) in = in && !(r >= xl && r < xh);
+                const key_t cand = in ? topk_key((float)sv[e], (int)(unsigned)r) : 0;
                 changed |= list_offer(mine, cand, lane, k);
             }
             if (changed && lane < NR_KMAX) list[q * NR_KMAX + lane] = mine;
@@ -252,9 +246,9 @@ __global__ __launch_bounds__(256) void nearest_merge_kernel(const key_t* __restr
     }
 }
 
-template <int QB>
+template <int QB, bool EXCL = false>
 int launch_tiles(const NearestArgs& a, int grid, size_t lds, hipStream_t s) {
-    auto kern = nearest_tiles_kernel<QB>;
+    auto kern = nearest_tiles_kernel<QB, EXCL>;
     static size_t lds_set[OVMR_MAX_DEVICES] = {};                    // per QB and device: the largest dynamic LDS size granted so far
     if (lds > 64 * 1024) {
         int dev = 0;
@@ -280,23 +274,27 @@ int pick_slices(int B, long R) {
 bool bad_shape(int B, long R, int k) { return B < 0 || R < 1 || R >= 0xFFFFFFFFL || k < 1 || k > NR_KMAX; }
 
 int nearest_rows(const void* Q, int B, const void* X, long R, int D, int k, const int32_t* ranges, float* values, int32_t* indices,
-                 void* scratch, long scratch_bytes, int S, hipStream_t stream) {
+                 void* scratch, long scratch_bytes, int S, hipStream_t stream, const int32_t* exclude = nullptr) {
     if (bad_shape(B, R, k) || k > R || D < 64 || D > 1024 || D % 64 || S < 1) return OVMR_E_ARG;
     if (B == 0) return 0;
     if (!Q || !X || !values || !indices || !scratch) return OVMR_E_ARG;
-    if (((uintptr_t)Q | (uintptr_t)X) & 15 || (uintptr_t)scratch & 7 || ((uintptr_t)values | (uintptr_t)indices | (uintptr_t)ranges) & 3)
+    if (((uintptr_t)Q | (uintptr_t)X) & 15 || (uintptr_t)scratch & 7 || ((uintptr_t)values | (uintptr_t)indices | (uintptr_t)ranges | (uintptr_t)exclude) & 3)
         return OVMR_E_ARG;
     if (scratch_bytes < 0 || (unsigned long long)scratch_bytes < (unsigned long long)B * S * k * 8) return OVMR_E_ARG;
     // 64-query tiles where they fit the 160 KB of LDS and there are more than 32 queries, else 32-query tiles
-    const int BM = (B > 32 && nearest_lds_bytes(64, D) <= 160 * 1024) ? 64 : 32;
+    const int BM = (B > 32 && nearest_lds_bytes(64, D, exclude != nullptr) <= 160 * 1024) ? 64 : 32;
     const long Tq = (B + BM - 1) / BM, grid = (S + 7L) / 8 * 8 * Tq;     // slices in groups of eight (nearest_tiles_kernel)
     if (grid > 0x7FFFFFFFL) return OVMR_E_ARG;
     NearestArgs a;
     a.Q = (const half_t*)Q; a.X = (const half_t*)X; a.ranges = ranges; a.scratch = (key_t*)scratch;
     a.B = B; a.D = D; a.k = k; a.S = S; a.R = (unsigned)R; a.Tq = (unsigned)Tq;
     a.tiles_per_slice = (int)((bank_tiles(R) + S - 1) / S);
-    const size_t lds = nearest_lds_bytes(BM, D);
-    if (int rc = BM == 64 ? launch_tiles<2>(a, (int)grid, lds, stream) : launch_tiles<1>(a, (int)grid, lds, stream)) return rc;
+    a.exclude = exclude;
+    const size_t lds = nearest_lds_bytes(BM, D, exclude != nullptr);
+    if (exclude) {
+        if (int rc = BM == 64 ? launch_tiles<2, true>(a, (int)grid, lds, stream) : launch_tiles<1, true>(a, (int)grid, lds, stream)) return rc;
+    } else if (int rc = BM == 64 ? launch_tiles<2>(a, (int)grid, lds, stream) : launch_tiles<1>(a, (int)grid, lds, stream))
+        return rc;
     hipLaunchKernelGGL(nearest_merge_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, stream, (const key_t*)scratch, B, S, k, values, indices);
     return (int)hipGetLastError();
 }
@@ -319,6 +317,35 @@ int ovmr_nearest_rows(const void* queries_f16, int B, const void* bank_f16, long
 int ovmr_debug_nearest_rows(const void* queries_f16, int B, const void* bank_f16, long R, int D, int k, const int32_t* ranges, float* values,
                             int32_t* indices, void* scratch, long scratch_bytes, int slices, ovmr_stream stream) {
     return nearest_rows(queries_f16, B, bank_f16, R, D, k, ranges, values, indices, scratch, scratch_bytes, slices, (hipStream_t)stream);
+}
+
+// ---- include/ovmr_hip_audit.h: the search with an excluded row range per query; max_range > 0 takes the one-wave-per-query launch of
+// neighbours.hip, 0 the tiled launch pair above
+
+long ovmr_neighbours_scratch_bytes(int B, long R, int k, int max_range) {
+    if (bad_shape(B, R, k) || max_range < 0 || max_range > NB_MAX_RANGE) return -1;
+    return max_range > 0 ? 0 : (long)B * pick_slices(B, R) * k * 8;
+}
+
+int ovmr_debug_neighbours_rows(const void* queries_f16, int B, const void* bank_f16, long R, int D, int k, const int32_t* ranges,
+                               const int32_t* exclude, int max_range, float* values, int32_t* indices, void* scratch, long scratch_bytes,
+                               int path, int slices, ovmr_stream stream) {
+    if (path == 0)
+        return nearest_rows(queries_f16, B, bank_f16, R, D, k, ranges, values, indices, scratch, scratch_bytes, slices, (hipStream_t)stream, exclude);
+    if (path != 1 || bad_shape(B, R, k) || k > R || D < 64 || D > 1024 || D % 64 || max_range < 1 || max_range > NB_MAX_RANGE) return OVMR_E_ARG;
+    if (B == 0) return 0;
+    if (!queries_f16 || !bank_f16 || !values || !indices || !ranges) return OVMR_E_ARG;
+    if (((uintptr_t)queries_f16 | (uintptr_t)bank_f16) & 15 || ((uintptr_t)values | (uintptr_t)indices | (uintptr_t)ranges | (uintptr_t)exclude) & 3)
+        return OVMR_E_ARG;
+    return launch_neighbours_short(queries_f16, B, bank_f16, R, D, k, ranges, exclude, max_range, values, indices, (hipStream_t)stream);
+}
+
+int ovmr_neighbours_rows(const void* queries_f16, int B, const void* bank_f16, long R, int D, int k, const int32_t* ranges,
+                         const int32_t* exclude, int max_range, float* values, int32_t* indices, void* scratch, long scratch_bytes,
+                         ovmr_stream stream) {
+    if (bad_shape(B, R, k) || max_range < 0 || max_range > NB_MAX_RANGE || (max_range > 0 && !ranges)) return OVMR_E_ARG;
+    return ovmr_debug_neighbours_rows(queries_f16, B, bank_f16, R, D, k, ranges, exclude, max_range, values, indices, scratch, scratch_bytes,
+                                      max_range > 0 ? 1 : 0, max_range > 0 ? 1 : pick_slices(B, R), stream);
 }
 
 }  // extern "C"

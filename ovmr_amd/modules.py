@@ -1037,6 +1037,95 @@ class CustomCLIP(_TwoInFlight):
         sims, rows, _ = self.nearest_exemplars(feats, int(n), classes=indices)
         return values, indices, sims, rows
 
+    # ------------------------------------------------------------------ auditing the reference bank (no counterpart in the reference's API)
+    def _bank_starts_host(self):
+        """(starts: list of C + 1 ints, the longest class) of _exemplar_bank()'s view, on the host; kept with the store it describes (the
+        packed store's class sizes are read back once)."""
+        src, lab = self.eval_feat4cls, getattr(self, "eval_row_labels", None)
+        kept = self.__dict__.get("_audit_starts")
+        if kept is not None and kept[0] is src and kept[1] is lab:
+            return kept[2], kept[3]
+        shots = [int(src.shape[1])] * int(src.shape[0]) if lab is None else [int(n) for n in self._ragged_n_label.tolist()]
+        starts = [0]
+        for n in shots:
+            starts.append(starts[-1] + n)
+        self._audit_starts = (src, lab, starts, max(shots) if shots else 0)
+        return starts, self._audit_starts[3]
+
+    @torch.no_grad()
+    def audit_bank(self, k: int = 5, classes=None, dup_threshold: float = 0.995, batch: int = 1024):
+        """Every exemplar's nearest neighbours inside its own class (itself left out) and outside it, by h(row . row) on the view of
+        _exemplar_bank() (uniform or packed store), and what follows from them.  1 <= k <= 32.  classes (host ints, None = all): the
+        classes whose rows are audited, for instance freshly added ones; the search always sees the whole bank.  With N audited rows,
+        a dict of device tensors:
+          rows int64 [N], labels int64 [N]                   the audited bank rows, increasing, and their classes;
+          in_sim fp32 [N, k], in_row int64 [N, k]            the class-mates nearest to the row: ONE launch over all N queries
+                                                             (ovmr_neighbours_rows, range = the class, exclusion = the row itself,
+                                                             max_range = the longest class); a full audit queries the bank itself, no copy;
+          out_sim, out_row, out_label [N, k]                 the nearest rows of other classes (range = the bank, exclusion = the class),
+                                                             the tiled launch pair in batches of `batch` queries on the same stream;
+          suspect bool [N]                                   the closest image of another class is STRICTLY closer than the closest
+                                                             class-mate (the library's order on values: NaN largest, -0 == +0); a class
+                                                             of one image is never suspect;
+          duplicate_of int64 [N]                             the better of the two first neighbours (larger value, then lower row) where
+                                                             its similarity is >= dup_threshold (a NaN never is), else -1;
+          class_suspects, class_duplicates int64 [C]         their counts per class.
+        Missing neighbours are row -1, label -1, similarity -inf.  dup_threshold: an fp16 L2-normalised row scores a byte-identical copy at
+        least 0.9990, so the default 0.995 always finds one; re-compressed near-duplicates need a lower value, which nobody has
+        measured on real images.  Nothing synchronises with the host (the packed store's class sizes are read back once per store)."""
+        from . import runtime
+        self._needs_state("audit_bank")
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= self.MAX_NEAREST:
+            raise ValueError(f"audit_bank: k must be an integer in [1, {self.MAX_NEAREST}], got {k!r}")
+        k = int(k)
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) or int(batch) < 1:
+            raise ValueError(f"audit_bank: batch must be a positive integer, got {batch!r}")
+        if isinstance(dup_threshold, bool) or not isinstance(dup_threshold, (int, float, np.floating, np.integer)) or dup_threshold != dup_threshold:
+            raise ValueError(f"audit_bank: dup_threshold must be a number, got {dup_threshold!r}")
+        bank, starts = self._exemplar_bank()
+        R, C, dev = bank.shape[0], starts.shape[0] - 1, self.device
+        if k > R:
+            raise ValueError(f"audit_bank: k = {k} exceeds the bank's {R} exemplar rows")
+        hstarts, longest = self._bank_starts_host()
+        if classes is None:
+            rows, queries = torch.arange(R, dtype=torch.int64, device=dev), bank
+        else:
+            which = np.unique(np.asarray(classes.cpu() if isinstance(classes, torch.Tensor) else classes).reshape(-1))
+            if which.size and (not np.issubdtype(which.dtype, np.integer) or which.min() < 0 or which.max() >= C):
+                raise ValueError(f"audit_bank: classes must be integer labels in [0, {C}), got {classes!r}")
+            rows = torch.cat([torch.arange(hstarts[c], hstarts[c + 1], dtype=torch.int64) for c in which.tolist()]
+                             + [torch.zeros(0, dtype=torch.int64)]).to(dev)
+            queries = bank.index_select(0, rows)
+        n = int(rows.shape[0])
+        labels = torch.searchsorted(starts[1:], rows, right=True)
+        own = torch.stack([starts[labels], starts[labels + 1]], 1).to(torch.int32)
+        me = torch.stack([rows, rows + 1], 1).to(torch.int32)
+        # inside the class: one wave per query (DESIGN.md section 4); a class beyond the short launch's ceiling takes the tiled pair
+        in_sim, in_row = runtime.neighbour_rows(queries, bank, k, own, me, longest if longest <= runtime.MAX_RANGE else 0)
+        out_sim = torch.empty((n, k), dtype=torch.float32, device=dev)
+        out_row = torch.empty((n, k), dtype=torch.int32, device=dev)
+        for i in range(0, n, int(batch)):
+            j = min(n, i + int(batch))
+            runtime.neighbour_rows(queries[i:j], bank, k, None, own[i:j], 0, out=(out_sim[i:j], out_row[i:j]))
+        in_row, out_row = in_row.long(), out_row.long()
+        out_label = torch.where(out_row >= 0, torch.searchsorted(starts[1:], out_row.clamp(min=0), right=True), out_row)
+        a, b = out_sim[:, 0], in_sim[:, 0]
+        a_nan, b_nan = torch.isnan(a), torch.isnan(b)
+        a_gt = (a_nan & ~b_nan) | (~a_nan & ~b_nan & (a > b))        # the library's order on values: NaN largest, -0 == +0
+        b_gt = (b_nan & ~a_nan) | (~a_nan & ~b_nan & (b > a))
+        has_in, has_out = in_row[:, 0] >= 0, out_row[:, 0] >= 0
+        suspect = has_in & has_out & a_gt
+        out_wins = has_out & (~has_in | a_gt | (~b_gt & (out_row[:, 0] < in_row[:, 0])))
+        best_row = torch.where(out_wins, out_row[:, 0], in_row[:, 0])
+        best_sim = torch.where(out_wins, a, b)
+        duplicate_of = torch.where((best_row >= 0) & (best_sim >= float(dup_threshold)), best_row, torch.full_like(best_row, -1))
+        ones = torch.ones_like(labels)
+        class_suspects = torch.zeros(C, dtype=torch.int64, device=dev).index_add_(0, labels, ones * suspect)
+        class_duplicates = torch.zeros(C, dtype=torch.int64, device=dev).index_add_(0, labels, ones * (duplicate_of >= 0))
+        return {"rows": rows, "labels": labels, "in_sim": in_sim, "in_row": in_row, "out_sim": out_sim, "out_row": out_row,
+                "out_label": out_label, "suspect": suspect, "duplicate_of": duplicate_of, "class_suspects": class_suspects,
+                "class_duplicates": class_duplicates}
+
     @torch.no_grad()
     def load_classifiers(self, path: str):
         """Installs the classifiers of a mm_classifiers.pt written by forward_prompt (:276-285: text / vision / multimodal classifier

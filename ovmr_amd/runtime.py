@@ -111,6 +111,13 @@ EXT_SIGNATURES = {
     "ovmr_debug_nearest_rows": (c_i, [c_p, c_i, c_p, ctypes.c_long, c_i, c_i, c_p, c_p, c_p, c_p, ctypes.c_long, c_i, c_p]),
 }
 
+# the second extension header include/ovmr_hip_audit.h (tests/test_audit_cpu.py holds the pair to each other)
+AUDIT_SIGNATURES = {
+    "ovmr_neighbours_scratch_bytes": (ctypes.c_long, [c_i, ctypes.c_long, c_i, c_i]),
+    "ovmr_neighbours_rows": (c_i, [c_p, c_i, c_p, ctypes.c_long, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, ctypes.c_long, c_p]),
+    "ovmr_debug_neighbours_rows": (c_i, [c_p, c_i, c_p, ctypes.c_long, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, ctypes.c_long, c_i, c_i, c_p]),
+}
+
 _lib = None
 
 
@@ -124,7 +131,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         raise RuntimeError(f"{p} not found: build it with `python -m ovmr_amd.build` (hipcc, gfx950). "
                            "ovmr_amd has no CPU fallback.")
     lib = ctypes.CDLL(p)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(AUDIT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -316,6 +323,90 @@ def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Opti
                                    scratch.numel() * 8, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise OvmrError(f"ovmr_nearest_rows failed with {rc} (B = {B}, R = {R}, D = {D}, k = {k})")
+    return values, indices
+
+
+MAX_RANGE = 4096                                                  # ovmr_neighbours_rows: the ceiling of max_range (include/ovmr_hip_audit.h)
+
+
+def _want_pairs(where: str, name: str, t, B: int, R: int, dev):
+    """ranges / exclude of neighbour_rows: [B, 2] of an integer dtype; host values are checked (0 <= lo <= hi <= R), device values are the
+    caller's contract (the kernels clamp what they read).  Returns the tensor (a numpy array as a tensor)."""
+    _want(where, name, t, (B, 2))
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(t)
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        _refuse(where, name, "of an integer dtype", str(t.dtype))
+    if not t.is_cuda:
+        _want_range(where, name, t, 0, R + 1, "row bounds")
+        if t.numel() and bool((t[:, 0] > t[:, 1]).any()):
+            _refuse(where, name, "pairs lo <= hi", "a pair with lo > hi")
+    elif not _same_device(t.device, dev):
+        _refuse(where, name, f"on {dev} or on the host", f"a tensor on {t.device}")
+    return t
+
+
+def neighbour_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Optional[torch.Tensor] = None,
+                   exclude: Optional[torch.Tensor] = None, max_range: int = 0, out=None):
+    """ovmr_neighbours_rows on the current stream (include/ovmr_hip_audit.h): nearest_rows with an excluded row range per query and a launch
+    for short ranges.  queries [B, D], bank [R, D], k, ranges, out: as nearest_rows.  exclude int32 [B, 2] (xlo, xhi): query b leaves the
+    rows xlo <= r < xhi out; host values are checked like ranges and copied, device values are clamped by the kernel.  max_range 0: the
+    tiled launch pair; 1 .. 4096: a promise that no range is longer, which takes the one-wave-per-query launch (ranges required; host
+    ranges are held to the promise, device ranges are truncated to it by the kernel).  The scratch is nearest_rows' cached buffer."""
+    where = "neighbour_rows"
+    _want(where, "queries", queries, (None, None), torch.float16, "cuda")
+    _want(where, "bank", bank, (None, None), torch.float16, queries.device)
+    B, D = queries.shape
+    R = bank.shape[0]
+    if bank.shape[1] != D:
+        _refuse(where, "bank", f"of shape [*, {D}] (the queries' width)", f"{list(bank.shape)}")
+    if D % 64 or not 64 <= D <= 1024:
+        _refuse(where, "queries", "of a width that is a multiple of 64 in [64, 1024]", f"{list(queries.shape)}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= min(R, 32):
+        _refuse(where, "k", f"an integer in [1, {min(R, 32)}]", repr(k))
+    k = int(k)
+    if isinstance(max_range, bool) or not isinstance(max_range, (int, np.integer)) or not 0 <= int(max_range) <= MAX_RANGE:
+        _refuse(where, "max_range", f"an integer in [0, {MAX_RANGE}]", repr(max_range))
+    max_range = int(max_range)
+    if max_range > 0 and ranges is None:
+        _refuse(where, "ranges", f"given where max_range = {max_range} promises their length", "None")
+    if ranges is not None:
+        ranges = _want_pairs(where, "ranges", ranges, B, R, queries.device)
+        if max_range > 0 and not ranges.is_cuda and ranges.numel() and int((ranges[:, 1] - ranges[:, 0]).max()) > max_range:
+            _refuse(where, "ranges", f"pairs with hi - lo <= max_range = {max_range}", f"a range of {int((ranges[:, 1] - ranges[:, 0]).max())} rows")
+    if exclude is not None:
+        exclude = _want_pairs(where, "exclude", exclude, B, R, queries.device)
+    if out is not None:
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            _refuse(where, "out", "a pair (values, indices)", type(out).__name__)
+        _want(where, "out[0]", out[0], (B, k), torch.float32, queries.device, dense=True)
+        _want(where, "out[1]", out[1], (B, k), torch.int32, queries.device, dense=True)
+    lib = load_library()
+    dev = queries.device
+    with torch.cuda.device(dev):
+        queries, bank = queries.contiguous(), bank.contiguous()
+        if ranges is not None:
+            ranges = ranges.to(dev, torch.int32).contiguous()
+        if exclude is not None:
+            exclude = exclude.to(dev, torch.int32).contiguous()
+        values, indices = out if out is not None else (torch.empty((B, k), dtype=torch.float32, device=dev),
+                                                        torch.empty((B, k), dtype=torch.int32, device=dev))
+        if B == 0:
+            return values, indices
+        need = int(lib.ovmr_neighbours_scratch_bytes(B, R, k, max_range))
+        if need < 0:
+            raise OvmrError(f"ovmr_neighbours_scratch_bytes refuses B = {B}, R = {R}, k = {k}, max_range = {max_range}")
+        scratch = None
+        if need:
+            key = torch.device(dev.type, torch.cuda.current_device())
+            scratch = _nearest_scratch.get(key)
+            if scratch is None or scratch.numel() * 8 < need:
+                scratch = _nearest_scratch[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+        rc = lib.ovmr_neighbours_rows(_ptr(queries), B, _ptr(bank), R, D, k, _ptr(ranges), _ptr(exclude), max_range, _ptr(values),
+                                      _ptr(indices), _ptr(scratch), 0 if scratch is None else scratch.numel() * 8,
+                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise OvmrError(f"ovmr_neighbours_rows failed with {rc} (B = {B}, R = {R}, D = {D}, k = {k}, max_range = {max_range})")
     return values, indices
 
 

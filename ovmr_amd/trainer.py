@@ -295,6 +295,10 @@ class MM_CLS_OP(_EvalTrainer):
     def explained(self, inputs, k, n):
         return (self.model.predict_explained(image, k, n, eval_set_loader=self.eval_set_loader) for image in inputs)
 
+    def audit_bank(self, k=5, classes=None, dup_threshold=0.995, batch=1024):
+        """CustomCLIP.audit_bank on the trainer's model (generated in this run, or installed by load_bank)."""
+        return self.model.audit_bank(k, classes, dup_threshold, batch)
+
     def after_test(self):
         self.model.wait_files()                      # mm_classifiers.pt / visual_tokens.pt were written while the test set ran
 
