@@ -23,6 +23,16 @@ audits the exemplar features themselves: OUTPUT_DIR/bank_audit.csv (one line per
 another class, `suspect` where the latter is strictly closer, `duplicate_of`), bank_audit_neighbours.csv and bank_audit_classes.csv.  From
 `--bank` alone nothing is decoded or encoded and no `--root` is needed; it also runs after a generation or an edit, and next to `--predict`.
 
+    python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --retrieve IMAGES [--per-class M] [--within-top K]
+
+searches an UNLABELLED image pool (listed as `--predict` lists it) by class instead of the test pass: OUTPUT_DIR/retrieval.csv holds
+`label,classname,rank,image,score`, the M (default 32, at most 32) best images of every class in class order then rank, equal scores to the
+image listed first; with `--within-top K` a class is searched only among the images that rank it within their K best scores (ties at the
+cut included).  Any of the three trainers; after a generation, from `--classifiers FILE`, or from `--bank FILE` without `--root`.  Not with
+`--predict`, `--eval_mode all` or the test pass's detail flags.  Under `torch.distributed.run` the pool's batches are sharded over the
+ranks like the test pass's, the per-class lists are all-gathered and merged on every rank, and rank 0 writes the one-process file byte for
+byte (`--predict` stays one process).
+
     python -m ovmr_amd.cli --eval-only --trainer MM_CLS_OP ... --eval_mode all
 
 evaluates the four modes of the reference's result tables (fusion, text, vision, multimodal; trainers/mm_classifier_one_prompt.py:348-363)
@@ -279,22 +289,22 @@ PREDICT_ONE_PROCESS = "--predict runs in one process: sharding the prediction pa
 MAX_TOPK = 32                 # ovmr_topk_rows (include/ovmr_hip.h)
 
 
-def list_predict_images(path: str) -> List[str]:
-    """`--predict PATH`: a directory -- every image file below it (IMAGE_EXTENSIONS, hidden names skipped), sorted by path -- or a text
+def list_predict_images(path: str, flag: str = "--predict") -> List[str]:
+    """`--predict PATH` (and `--retrieve PATH`: `flag` names the one in the messages): a directory -- every image file below it (IMAGE_EXTENSIONS, hidden names skipped), sorted by path -- or a text
     file with one image path per line, in file order.  Checked before anything is loaded: an empty PATH or a missing file is a SystemExit
     that names it."""
     if not path:
-        raise SystemExit("--predict: PATH is empty (a directory of images, or a text file with one image path per line)")
+        raise SystemExit(f"{flag}: PATH is empty (a directory of images, or a text file with one image path per line)")
     if osp.isdir(path):
         images = []
         for d, dirs, files in os.walk(path):
             dirs[:] = [x for x in dirs if not x.startswith(".")]
             images += [osp.join(d, n) for n in files if not n.startswith(".") and n.lower().endswith(IMAGE_EXTENSIONS)]
         if not images:
-            raise SystemExit(f"--predict {path!r}: no image file below this directory ({', '.join(IMAGE_EXTENSIONS)})")
+            raise SystemExit(f"{flag} {path!r}: no image file below this directory ({', '.join(IMAGE_EXTENSIONS)})")
         return sorted(images)
     if not osp.isfile(path):
-        raise SystemExit(f"--predict {path!r}: no such directory or list file")
+        raise SystemExit(f"{flag} {path!r}: no such directory or list file")
     images = []
     with open(path) as f:
         for no, raw in enumerate(f, 1):
@@ -305,7 +315,7 @@ def list_predict_images(path: str) -> List[str]:
                 raise SystemExit(f"{path}:{no}: image {img!r} does not exist")
             images.append(img)
     if not images:
-        raise SystemExit(f"--predict {path!r}: the list names no image")
+        raise SystemExit(f"{flag} {path!r}: the list names no image")
     return images
 
 
@@ -325,6 +335,61 @@ def write_predictions(path: str, predictions) -> None:
         for image, ranks in predictions:
             for rank, (label, name, score) in enumerate(ranks):
                 w.writerow([image, rank, label, name, repr(float(score))])
+
+
+MAX_PER_CLASS = 32            # ovmr_retrieve_update (include/ovmr_hip_retrieve.h)
+MAX_POOL = 2 ** 32 - 1        # image indices of a pool lie in [0, 2^32 - 1)
+RETRIEVAL_COLUMNS = ["label", "classname", "rank", "image", "score"]
+
+
+def check_retrieve(args, trainer_name: str, zeroshot: bool, eval_mode: str):
+    """The refusals of `--retrieve PATH [--per-class M] [--within-top K]`, before anything is listed or loaded."""
+    if args.retrieve is None:
+        for flag, v in (("--per-class M", args.per_class), ("--within-top K", args.within_top)):
+            if v is not None:
+                raise SystemExit(f"{flag} belongs to --retrieve PATH: the search of an image pool by class")
+        return
+    if args.predict is not None:
+        raise SystemExit("--retrieve searches a pool by class, --predict ranks the classes of every image: one of the two per run")
+    if eval_mode == "all" and not zeroshot:
+        raise SystemExit("--retrieve searches under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
+    for flag, on in (("--per-class-result", args.per_class_result), ("--confusion-matrix", args.confusion_matrix)):
+        if on:
+            raise SystemExit(f"{flag} belongs to the test pass: --retrieve searches unlabelled images, there is nothing to count")
+    if args.topk is not None:
+        raise SystemExit("--topk K belongs to --predict PATH (--retrieve takes --per-class M and --within-top K)")
+    m = MAX_PER_CLASS if args.per_class is None else args.per_class
+    if not 1 <= m <= MAX_PER_CLASS:
+        raise SystemExit(f"--per-class {m}: M must lie in [1, {MAX_PER_CLASS}]")
+    if args.within_top is not None and not 1 <= args.within_top <= MAX_TOPK:
+        raise SystemExit(f"--within-top {args.within_top}: K must lie in [1, min({MAX_TOPK}, number of classes)]")
+
+
+def check_pool_size(n: int, path: str):
+    """An image's position in the pool takes the 32 low bits of a key, 2^32 - 1 excluded (include/ovmr_hip_retrieve.h)."""
+    if n >= MAX_POOL:
+        raise SystemExit(f"--retrieve {path!r}: a pool of {n:,} images; one search takes fewer than 2^32 - 1 = {MAX_POOL:,}")
+
+
+def retrieval_rows(values, indices, images: Sequence[str], classnames: Sequence[str]):
+    """[(label, classname, rank, image, score)] from the [C, m] values / indices of a search, class after class, best first; an unfilled
+    rank (index -1) has no entry."""
+    out = []
+    for c, (vs, ix) in enumerate(zip(values.tolist(), indices.tolist())):
+        out += [(c, classnames[c], rank, images[i], float(v)) for rank, (v, i) in enumerate(zip(vs, ix)) if i >= 0]
+    return out
+
+
+def write_retrieval(path: str, rows) -> None:
+    """retrieval.csv: `label,classname,rank,image,score`, one line per filled (class, rank) in class order then rank; the score is
+    repr(float), as in predictions.csv."""
+    import csv
+    os.makedirs(osp.dirname(path) or ".", exist_ok=True)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, delimiter=",", lineterminator="\n")
+        w.writerow(RETRIEVAL_COLUMNS)
+        for label, name, rank, image, score in rows:
+            w.writerow([label, name, rank, image, repr(float(score))])
 
 
 MAX_NEAREST = 32              # ovmr_nearest_rows (include/ovmr_hip_nearest.h)
@@ -466,6 +531,14 @@ def parse(argv=None):
     ap.add_argument("--predict", metavar="PATH", default=None, help="ranked prediction on UNLABELLED images instead of the test pass: a directory "
                     "(every image file below it, sorted by path) or a text file with one image path per line; writes OUTPUT_DIR/predictions.csv")
     ap.add_argument("--topk", type=int, default=None, metavar="K", help="classes per image of --predict, best first (default 5; 1 <= K <= min(32, classes))")
+    ap.add_argument("--retrieve", metavar="PATH", default=None, help="search an UNLABELLED image pool by class instead of the test pass: PATH is listed "
+                    "as --predict lists it; writes OUTPUT_DIR/retrieval.csv (label,classname,rank,image,score: the --per-class best images of "
+                    "every class, best first, equal scores to the image listed first).  Any of the three trainers, after a generation, from "
+                    "--classifiers FILE or from --bank FILE (no --root needed); under torch.distributed.run the pool's batches are sharded over "
+                    "the ranks and rank 0 writes the one-process file")
+    ap.add_argument("--per-class", type=int, default=None, metavar="M", help="images per class of --retrieve (default 32; 1 <= M <= 32)")
+    ap.add_argument("--within-top", type=int, default=None, metavar="K", help="with --retrieve: search a class only among the images that rank it "
+                    "within their K best scores, ties at the cut included (1 <= K <= min(32, classes); default: among all images)")
     ap.add_argument("--nearest", type=int, default=None, metavar="N", help="with --predict --trainer MM_CLS_OP: also write OUTPUT_DIR/neighbours.csv, the N "
                     "nearest exemplars of every (image, predicted class) (1 <= N <= 32; after a generation in this run, or from --bank)")
     ap.add_argument("--audit-bank", type=int, nargs="?", const=5, default=None, metavar="K", help="MM_CLS_OP: audit the exemplar features -- every "
@@ -696,9 +769,12 @@ def main(argv=None) -> Dict[str, float]:
     if args.bank and not osp.isfile(args.bank):
         raise SystemExit(f"--bank {args.bank!r}: no such file")
     predict, images, k = args.predict is not None, [], None
+    retrieve = args.retrieve is not None
+    check_retrieve(args, cfg.TRAINER.NAME, zeroshot, cfg.EVAL_MODE)
+    pool = predict or retrieve                                # unlabelled images instead of the labelled test split
     check_nearest(args, cfg.TRAINER.NAME, zeroshot)
     check_audit(args, cfg.TRAINER.NAME, zeroshot)
-    audit_only = args.audit_bank is not None and bool(args.bank) and not edits and not predict      # the bank alone: no data set, no test pass
+    audit_only = args.audit_bank is not None and bool(args.bank) and not edits and not pool      # the bank alone: no data set, no test pass
     if predict and cfg.EVAL_MODE == "all" and not zeroshot:
         raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
     if predict:
@@ -715,9 +791,16 @@ def main(argv=None) -> Dict[str, float]:
         if args.classifiers and not osp.isfile(args.classifiers):
             raise SystemExit(f"--classifiers {args.classifiers!r}: no such file")
         images = list_predict_images(args.predict)
+    elif retrieve:
+        if args.classifiers and zeroshot:
+            raise SystemExit(f"--classifiers {args.classifiers!r}: --trainer {cfg.TRAINER.NAME} has no generated classifiers to load (MM_CLS_OP only)")
+        if args.classifiers and not osp.isfile(args.classifiers):
+            raise SystemExit(f"--classifiers {args.classifiers!r}: no such file")
+        images = list_predict_images(args.retrieve, "--retrieve")
+        check_pool_size(len(images), args.retrieve)
     elif args.topk is not None or args.classifiers:
         raise SystemExit("--topk / --classifiers belong to --predict PATH (the test pass takes TEST.TOPK)")
-    load_classifiers = predict and bool(args.classifiers)
+    load_classifiers = pool and bool(args.classifiers)
     from_bank = bool(args.bank)
     if from_bank and edits and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
         print(f"Oops! The results exist at {cfg.OUTPUT_DIR} (so skip this job)")           # generate_classifier.sh:27-28
@@ -768,16 +851,19 @@ def main(argv=None) -> Dict[str, float]:
             raise SystemExit(f"--bank {args.bank!r}: the bank holds no class names (it was written by a model built from token rows)")
         plan = plan_vocabulary_edits(args, bank_obj["classnames"], shots, seed, ragged)
         classnames, exemplars, test_items = plan[3], [], []
-        if not predict and not audit_only:                    # the data set the test pass runs on must speak of the same classes
+        if not pool and not audit_only:                       # the data set the test pass runs on must speak of the same classes
             set_names, _, test_items = build_splits(split_cfg, args.eval_split, args.test_split, "", False)
             diff = bank_format.first_difference(classnames, set_names)
             if diff is not None:
                 raise SystemExit(f"--bank {args.bank!r}: its class names" + (" (after the edits)" if edits else "") + f" are not the data set's: {diff}")
     else:
-        classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if predict else args.test_split, args.exemplar_list, ragged)
+        classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if pool else args.test_split, args.exemplar_list, ragged)
     if predict:
         if k > len(classnames):
             raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
+    if retrieve and args.within_top is not None and args.within_top > len(classnames):
+        raise SystemExit(f"--within-top {args.within_top}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
+    if pool:
         test_items = [(p, 0) for p in images]             # the loader protocol carries a label: a dummy one, never read
 
     # what the loaders need to know of the model is in the weights' shapes: the decode workers start before the engine exists
@@ -898,6 +984,18 @@ def main(argv=None) -> Dict[str, float]:
             out_csv = osp.join(cfg.OUTPUT_DIR, "neighbours.csv")
             write_neighbours(out_csv, results["neighbours"])
             print(f"=> the {args.nearest} nearest exemplars of every predicted class: {out_csv}")
+    elif retrieve:
+        # every rank walks its own batches of the pool and ends with the job's lists (trainer.retrieve); rank 0 writes
+        m = MAX_PER_CLASS if args.per_class is None else args.per_class
+        values, indices = tr.retrieve(test_loader, m, args.within_top)
+        results = {"retrieval": retrieval_rows(values, indices, images, classnames)}
+        if rank == 0:
+            out_csv = osp.join(cfg.OUTPUT_DIR, "retrieval.csv")
+            write_retrieval(out_csv, results["retrieval"])
+            filled = len({r[0] for r in results["retrieval"]})
+            print(f"=> the {m} best of {len(images):,} images for each of {len(classnames):,} classes"
+                  + (f" (within each image's top {args.within_top})" if args.within_top is not None else "")
+                  + f": {len(results['retrieval']):,} lines, {filled:,} classes with an image: {out_csv}")
     else:
         tr.test()
         results = dict(tr.results)
@@ -906,7 +1004,7 @@ def main(argv=None) -> Dict[str, float]:
     for key, ld in edit_loaders.items():
         _report_pipeline(results, f"{key} set", ld)
     if not audit_only:
-        _report_pipeline(results, "predict set" if predict else "test set", test_loader)
+        _report_pipeline(results, "predict set" if predict else "retrieve set" if retrieve else "test set", test_loader)
     if audit_tables is not None:
         results["bank_audit"] = {"exemplars": audit_tables[0], "neighbours": audit_tables[1], "classes": audit_tables[2]}
     results["classnames"] = classnames

@@ -365,6 +365,39 @@ class _TwoInFlight:
         values, indices = runtime.topk_rows(out, k)
         return values, indices.long()
 
+    def _retrieve_outputs(self, what: str, batches, eval_set_loader, overlap, stable_inputs):
+        """(number of classes, the [B, C] outputs of `batches` in order) for retrieve_batches; whatever the model owes before its first
+        output (CustomCLIP: one mode, generated classifiers) happens here, in the call."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def retrieve_batches(self, batches, m: int, within_top: Optional[int] = None, base: int = 0, eval_set_loader=None,
+                         overlap: Optional[bool] = None, stable_inputs: bool = False):
+        """Search a pool by class (no counterpart in the reference's API): the m best images of every class over the image batches of
+        `batches`, two batches in flight as in the test loop; each output is offered to a runtime.ColumnTopM on the current stream as it is
+        handed over, row b of a batch being image `base` + (rows of the earlier batches) + b.  Returns the ColumnTopM: finish() gives
+        (values fp32 [C, m], indices int64 [C, m]) on the device, best first, equal scores to the lower image index, index -1 / value -inf
+        where a class has fewer than m images; its `state` merges with that of other ranks (disjoint images).
+        within_top = K (1 <= K <= min(32, C)): each batch first runs ovmr_topk_rows(out, K) and its K-th value is the row's floor, so a
+        class is searched only among the images that rank it within their K best scores.  Ties at the cut are INCLUDED: an image whose
+        score for a class equals its own K-th best score is eligible for that class, also where topk_rows listed another column of the
+        same score."""
+        from . import runtime
+        what = "retrieve_batches"
+        C, outs = self._retrieve_outputs(what, batches, eval_set_loader, overlap, stable_inputs)
+        m = runtime._want_int(what, "m", m, 1, runtime.MAX_PER_CLASS)
+        if within_top is not None:
+            within_top = runtime._want_int(what, "within_top", within_top, 1, min(32, C))
+        base = runtime._want_int(what, "base", base, 0, runtime.MAX_POOL)
+        top = runtime.ColumnTopM(C, m, self.device)
+        for out in outs:
+            floor = None
+            if within_top is not None:
+                floor = runtime.topk_rows(out, within_top)[0][:, within_top - 1].contiguous()
+            top.update(out, base, floor)
+            base += int(out.shape[0])
+        return top
+
     def _run_batches(self, batches, overlap, stable_inputs):
         cur = torch.cuda.current_stream(self.device)
 
@@ -938,9 +971,9 @@ class CustomCLIP(_TwoInFlight):
         return out
 
     # ------------------------------------------------------------------ ranked prediction (no counterpart in the reference's API)
-    def _one_mode(self, what: str):
+    def _one_mode(self, what: str, noun: str = "a ranked prediction"):
         if self.cfg.EVAL_MODE == "all":
-            raise ValueError(f"{what}: a ranked prediction needs one mode; EVAL_MODE all yields four outputs per image "
+            raise ValueError(f"{what}: {noun} needs one mode; EVAL_MODE all yields four outputs per image "
                              "(set EVAL_MODE to fusion, text, vision or multimodal)")
 
     @torch.no_grad()
@@ -956,6 +989,14 @@ class CustomCLIP(_TwoInFlight):
         self._one_mode("predict_topk_batches")               # (raised by the call, not by the first next())
         outs = self.forward_batches(batches, eval_set_loader=eval_set_loader, overlap=overlap, stable_inputs=stable_inputs)
         return (self._topk(out, k) for out in outs)
+
+    def _retrieve_outputs(self, what: str, batches, eval_set_loader, overlap, stable_inputs):
+        self._one_mode(what, "a search by class")
+        if self.mm_classifier is None:
+            if eval_set_loader is None:
+                raise NotImplementedError("pass eval_set_loader= to generate the classifiers")
+            self.forward_prompt(eval_set_loader, wait_files=False)
+        return int(self.mm_classifier.shape[0]), self._run_batches(batches, overlap, stable_inputs)
 
     # ------------------------------------------------------------------ nearest exemplars (no counterpart in the reference's API)
     MAX_NEAREST = 32              # ovmr_nearest_rows (include/ovmr_hip_nearest.h)
@@ -1625,6 +1666,9 @@ class ZeroshotCLIP(_TwoInFlight):
         """predict_topk for every image batch, in order, over inference_batches (two batches in flight)."""
         for out in self.inference_batches(batches, overlap=overlap, stable_inputs=stable_inputs):
             yield self._topk(out, k)
+
+    def _retrieve_outputs(self, what: str, batches, eval_set_loader, overlap, stable_inputs):
+        return int(self.text_features.shape[0]), self._run_batches(batches, overlap, stable_inputs)
 
     @torch.no_grad()
     def inference_batches(self, batches: Iterable, overlap: Optional[bool] = None, stable_inputs: bool = False):

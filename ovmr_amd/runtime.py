@@ -118,6 +118,15 @@ AUDIT_SIGNATURES = {
     "ovmr_debug_neighbours_rows": (c_i, [c_p, c_i, c_p, ctypes.c_long, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, ctypes.c_long, c_i, c_i, c_p]),
 }
 
+# the third extension header include/ovmr_hip_retrieve.h (tests/test_retrieve_cpu.py holds the pair to each other)
+RETRIEVE_SIGNATURES = {
+    "ovmr_retrieve_state_bytes": (ctypes.c_long, [c_i, c_i]),
+    "ovmr_retrieve_reset": (c_i, [c_p, c_i, c_i, c_p]),
+    "ovmr_retrieve_update": (c_i, [c_p, c_i, ctypes.c_long, c_i, c_i, c_i, ctypes.c_long, c_p, c_p, c_p]),
+    "ovmr_retrieve_merge": (c_i, [c_p, c_p, c_i, c_i, c_p]),
+    "ovmr_retrieve_finish": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
+}
+
 _lib = None
 
 
@@ -131,7 +140,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         raise RuntimeError(f"{p} not found: build it with `python -m ovmr_amd.build` (hipcc, gfx950). "
                            "ovmr_amd has no CPU fallback.")
     lib = ctypes.CDLL(p)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(AUDIT_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(AUDIT_SIGNATURES.items())
+                              + list(RETRIEVE_SIGNATURES.items())):
         fn = getattr(lib, name)          # AttributeError if the .so does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -408,6 +418,99 @@ def neighbour_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Op
     if rc != 0:
         raise OvmrError(f"ovmr_neighbours_rows failed with {rc} (B = {B}, R = {R}, D = {D}, k = {k}, max_range = {max_range})")
     return values, indices
+
+
+MAX_PER_CLASS = 32                                                # ovmr_retrieve_*: the ceiling of m (include/ovmr_hip_retrieve.h)
+MAX_POOL = 2 ** 32 - 1                                            # image indices lie in [0, MAX_POOL)
+
+
+def _want_int(where: str, name: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        _refuse(where, name, f"an integer in [{lo}, {hi}]", repr(v))
+    return int(v)
+
+
+class ColumnTopM:
+    """The m best images of each of C classes over a stream of [B, C] output matrices (include/ovmr_hip_retrieve.h): owns the state and
+    calls ovmr_retrieve_update / _merge / _finish on the current stream.  The order is the library's total order on (score, image index):
+    larger score first, equal scores to the lower image, NaN largest, -0 == +0.  `state` is the int64 [C, m] tensor itself -- opaque,
+    all-zero = empty, byte-copyable: it goes through an all-gather as it is, and what comes back goes into merge().  The state is a
+    function of what was offered, not of the batches it came in or of their order.  base is a scalar, so an update is for eager streams
+    (a captured graph would replay the same base)."""
+
+    def __init__(self, C: int, m: int, device="cuda:0"):
+        self.C = _want_int("ColumnTopM", "C", C, 1, 2 ** 31 - 1)
+        self.m = _want_int("ColumnTopM", "m", m, 1, MAX_PER_CLASS)
+        self.device = torch.device(device)
+        self.state = torch.zeros((self.C, self.m), dtype=torch.int64, device=self.device)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def reset(self):
+        """Empties every list (ovmr_retrieve_reset)."""
+        with torch.cuda.device(self.device):
+            rc = load_library().ovmr_retrieve_reset(_ptr(self.state), self.C, self.m, self._stream())
+        if rc != 0:
+            raise OvmrError(f"ovmr_retrieve_reset failed with {rc} (C = {self.C}, m = {self.m})")
+        return self
+
+    def update(self, out: torch.Tensor, base: int, floor: Optional[torch.Tensor] = None):
+        """Offers a batch: out [B, C] fp16 / fp32 on the state's device, taken as it is (rows may be strided: stride(1) == 1,
+        stride(0) >= C); row b is image base + b of the pool, 0 <= base, base + B <= 2^32 - 1.  floor fp32 [B] (dense, same device):
+        element (b, c) is offered only if it is not below floor[b] in the value order (equal is eligible; a NaN floor admits only NaNs)."""
+        where = "ColumnTopM.update"
+        _want_rows(where, "out", out)
+        _want(where, "out", out, (None, self.C), device=self.device)
+        B, C = out.shape
+        if C > 1 and out.stride(1) != 1 or B > 1 and out.stride(0) < C:
+            _refuse(where, "out", f"rows of unit column stride, at least {C} elements apart", f"strides {tuple(out.stride())}")
+        base = _want_int(where, "base", base, 0, MAX_POOL - B)
+        if floor is not None:
+            _want(where, "floor", floor, (B,), torch.float32, self.device, dense=True)
+        if B == 0:
+            return self
+        lib = load_library()
+        with torch.cuda.device(self.device):
+            ld = out.stride(0) if B > 1 else max(C, out.stride(0))
+            rc = lib.ovmr_retrieve_update(_ptr(out), F32 if out.dtype == torch.float32 else F16, ld, B, C, self.m, base, _ptr(floor),
+                                          _ptr(self.state), self._stream())
+        if rc != 0:
+            raise OvmrError(f"ovmr_retrieve_update failed with {rc} (B = {B}, C = {C}, m = {self.m}, base = {base})")
+        return self
+
+    def merge(self, other):
+        """The state becomes that of both streams together (ovmr_retrieve_merge); they must hold disjoint images.  other: a ColumnTopM
+        of the same C and m, or a state tensor int64 [C, m] (dense, same device), e.g. a rank's slice of an all-gather."""
+        where = "ColumnTopM.merge"
+        if isinstance(other, ColumnTopM):
+            other = other.state
+        _want(where, "other", other, (self.C, self.m), torch.int64, self.device, dense=True)
+        if other.data_ptr() == self.state.data_ptr():
+            _refuse(where, "other", "the state of ANOTHER stream (disjoint images)", "this object's own state")
+        with torch.cuda.device(self.device):
+            rc = load_library().ovmr_retrieve_merge(_ptr(self.state), _ptr(other), self.C, self.m, self._stream())
+        if rc != 0:
+            raise OvmrError(f"ovmr_retrieve_merge failed with {rc} (C = {self.C}, m = {self.m})")
+        return self
+
+    def finish(self, out=None):
+        """(values fp32 [C, m], indices int64 [C, m]) on the device, best first; an unfilled rank is index -1, value -inf.  The state
+        stays as it is.  out: (values, indices) to write into."""
+        where = "ColumnTopM.finish"
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != 2:
+                _refuse(where, "out", "a pair (values, indices)", type(out).__name__)
+            _want(where, "out[0]", out[0], (self.C, self.m), torch.float32, self.device, dense=True)
+            _want(where, "out[1]", out[1], (self.C, self.m), torch.int64, self.device, dense=True)
+        lib = load_library()
+        with torch.cuda.device(self.device):
+            values, indices = out if out is not None else (torch.empty((self.C, self.m), dtype=torch.float32, device=self.device),
+                                                            torch.empty((self.C, self.m), dtype=torch.int64, device=self.device))
+            rc = lib.ovmr_retrieve_finish(_ptr(self.state), self.C, self.m, _ptr(values), _ptr(indices), self._stream())
+        if rc != 0:
+            raise OvmrError(f"ovmr_retrieve_finish failed with {rc} (C = {self.C}, m = {self.m})")
+        return values, indices
 
 
 class Engine:

@@ -146,6 +146,16 @@ def all_gather_block(block: torch.Tensor, dist) -> torch.Tensor:
     return out.to(block.device)
 
 
+def all_gather_retrieve_state(state: torch.Tensor, dist) -> torch.Tensor:
+    """ONE all-gather of every rank's runtime.ColumnTopM.state, int64 [C, m] (opaque, byte-copyable: include/ovmr_hip_retrieve.h) ->
+    [world, C, m] on the state's device, rank-major.  A rank without a batch sends its empty (all-zero) state."""
+    s = _staged(state.contiguous(), dist)
+    world = dist.get_world_size()
+    out = torch.empty((world * s.shape[0], s.shape[1]), dtype=torch.int64, device=s.device)      # (gloo takes the concatenated form only)
+    dist.all_gather_into_tensor(out, s)
+    return out.view(world, s.shape[0], s.shape[1]).to(state.device)
+
+
 def all_reduce_counts(counts: torch.Tensor, dist) -> torch.Tensor:
     """ONE all-reduce (sum) of the int32 [3, 2, C] argmax counters."""
     c = _staged(counts, dist)

@@ -218,6 +218,37 @@ class _EvalTrainer:
             return torch.zeros((0, k), dtype=torch.float32), torch.zeros((0, k), dtype=torch.int64)
         return torch.cat([v for v, _ in pairs]).cpu(), torch.cat([i for _, i in pairs]).cpu()
 
+    def searched(self, inputs, m, within_top, base):
+        """retrieve_batches over the input batches: the model's runtime.ColumnTopM."""
+        raise NotImplementedError
+
+    @torch.no_grad()
+    def retrieve(self, data_loader, m: int = 32, within_top=None):
+        """Search an unlabelled pool by class (no counterpart in the reference): the m best images of every class among the images of
+        `data_loader` (the loader protocol's batches; their labels are not read), through the model's retrieve_batches -- two batches in
+        flight, one ovmr_retrieve_update per output, the device-to-host copy at the end.  Returns (values fp32 [C, m], indices int64
+        [C, m]) on the host: indices are positions in loader order, best first, equal scores to the lower position, -1 / -inf where a
+        class has fewer than m images.  within_top = K: a class is searched only among the images that rank it within their K best
+        scores (ties at the cut included).
+        Under an initialised process group with a loader that carries `batch_shard` (and `batch_range`, `bs`: cli.FolderLoader,
+        loader.PipelinedFolderLoader) every rank walks its own batches with the GLOBAL position of its first image as base, the states
+        are all-gathered (int64 [C, m] each, shard.all_gather_retrieve_state) and merged on every rank: every rank returns the
+        one-process result, bit for bit, because the state is a function of what was offered and not of who offered it."""
+        dist = self._pass_group(data_loader)
+        base = 0
+        if dist is not None:
+            base = int(data_loader.batch_range[0]) * int(data_loader.bs)
+        top = self.searched((self.parse_batch_test(batch)[0] for batch in data_loader), m, within_top, base)
+        if dist is not None:
+            from .shard import all_gather_retrieve_state
+            states = all_gather_retrieve_state(top.state, dist)
+            for r in range(dist.get_world_size()):
+                if r != dist.get_rank():
+                    top.merge(states[r])
+        self.after_test()
+        values, indices = top.finish()
+        return values.cpu(), indices.cpu()
+
     NO_EXEMPLARS = "nearest exemplars need a model that holds exemplar features (MM_CLS_OP only; a zero-shot trainer's classifier rows are text features)"
 
     def explained(self, inputs, k, n):
@@ -292,6 +323,9 @@ class MM_CLS_OP(_EvalTrainer):
     def ranked(self, inputs, k):
         return self.model.predict_topk_batches(inputs, k, eval_set_loader=self.eval_set_loader)
 
+    def searched(self, inputs, m, within_top, base):
+        return self.model.retrieve_batches(inputs, m, within_top, base, eval_set_loader=self.eval_set_loader)
+
     def explained(self, inputs, k, n):
         return (self.model.predict_explained(image, k, n, eval_set_loader=self.eval_set_loader) for image in inputs)
 
@@ -341,6 +375,9 @@ class ZeroshotCLIP(_EvalTrainer):
 
     def ranked(self, inputs, k):
         return self.model.predict_topk_batches(inputs, k)
+
+    def searched(self, inputs, m, within_top, base):
+        return self.model.retrieve_batches(inputs, m, within_top, base)
 
 
 class ZeroshotCLIP2(ZeroshotCLIP):
