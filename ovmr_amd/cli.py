@@ -365,6 +365,42 @@ def check_retrieve(args, trainer_name: str, zeroshot: bool, eval_mode: str):
         raise SystemExit(f"--within-top {args.within_top}: K must lie in [1, min({MAX_TOPK}, number of classes)]")
 
 
+MAX_BINS = 4096               # ovmr_eval_curves (include/ovmr_hip_curves.h)
+DEFAULT_BINS = 256
+
+
+def check_score_curves(args, trainer_name: str, zeroshot: bool):
+    """The refusals of `--score-curves [BINS] [--score-range LO HI]`, before anything is listed or loaded -> (bins, (lo, hi)), or
+    (None, None) without the flag.  MM_CLS_OP's outputs are probabilities: the range defaults to 0 1.  The zero-shot trainers return
+    logits, which have no natural range: there the range must be given."""
+    import math
+    if args.score_curves is None:
+        if args.score_range is not None:
+            raise SystemExit("--score-range LO HI belongs to --score-curves [BINS]: the range the score histograms of the test pass cover")
+        return None, None
+    for flag, v in (("--predict", args.predict), ("--retrieve", args.retrieve)):
+        if v is not None:
+            raise SystemExit(f"--score-curves belongs to the test pass: {flag} reads unlabelled images, a score has no label to be held against")
+    bins = args.score_curves
+    if not 1 <= bins <= MAX_BINS:
+        raise SystemExit(f"--score-curves {bins}: BINS must lie in [1, {MAX_BINS}]")
+    if args.score_range is None:
+        if zeroshot:
+            raise SystemExit(f"--score-curves: --trainer {trainer_name} returns logits, which have no natural range: give --score-range LO HI")
+        return bins, (0.0, 1.0)
+    lo, hi = args.score_range
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise SystemExit(f"--score-range {lo} {hi}: LO and HI must be finite")
+    if not lo < hi:
+        raise SystemExit(f"--score-range {lo} {hi}: LO must lie below HI")
+    from .runtime import curve_scale
+    try:
+        curve_scale(lo, hi, bins, "--score-range")
+    except ValueError:
+        raise SystemExit(f"--score-range {lo} {hi}: as fp32 the range must be finite, increasing and wide enough for {bins} bins") from None
+    return bins, (lo, hi)
+
+
 def check_pool_size(n: int, path: str):
     """An image's position in the pool takes the 32 low bits of a key, 2^32 - 1 excluded (include/ovmr_hip_retrieve.h)."""
     if n >= MAX_POOL:
@@ -567,6 +603,11 @@ def parse(argv=None):
                     "reports perclass_accuracy (the reference's TEST.PER_CLASS_RESULT; counted on the GPU by ovmr_eval_detail)")
     ap.add_argument("--confusion-matrix", action="store_true", help="the test pass also writes OUTPUT_DIR/cmat.pt, the row-normalised confusion "
                     "matrix (the reference's TEST.COMPUTE_CMAT; counted on the GPU by ovmr_eval_detail)")
+    ap.add_argument("--score-curves", type=int, nargs="?", const=DEFAULT_BINS, default=None, metavar="BINS", help="the test pass also keeps, per "
+                    "class, the histograms of the scores of its own images and of all others (BINS bins, default 256, at most 4096), reports "
+                    "mAP and mean AUROC and writes OUTPUT_DIR/curves_per_class.csv and score_hist.pt (per mode under --eval_mode all)")
+    ap.add_argument("--score-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --score-curves: the scores the bins "
+                    "cover (default 0 1 for MM_CLS_OP's probabilities; required for the zero-shot trainers' logits)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode worker processes of the pipelined loader (default: DATALOADER.NUM_WORKERS); 0 = decode in this thread")
@@ -744,7 +785,8 @@ def main(argv=None) -> Dict[str, float]:
     writes mm_classifiers.pt / visual_tokens.pt and evaluates the test set; the zero-shot trainers take the classes and test items of the
     same job (build_splits; no exemplar is decoded) and the text classifier from DATASET.NAME's template(s), and write no model file.
     The result block and acc_per_class.csv / f1_per_class.csv land in OUTPUT_DIR; --per-class-result adds the per-class block and
-    results["perclass_accuracy"], --confusion-matrix adds OUTPUT_DIR/cmat.pt."""
+    results["perclass_accuracy"], --confusion-matrix adds OUTPUT_DIR/cmat.pt, --score-curves adds two result lines, results["mAP"] /
+    ["mean_auroc"], curves_per_class.csv and score_hist.pt."""
     from . import config, templates
     args = parse(argv)
     cfg = config.setup_cfg(args)                              # train.py:134-155
@@ -772,6 +814,7 @@ def main(argv=None) -> Dict[str, float]:
     retrieve = args.retrieve is not None
     check_retrieve(args, cfg.TRAINER.NAME, zeroshot, cfg.EVAL_MODE)
     pool = predict or retrieve                                # unlabelled images instead of the labelled test split
+    curve_bins, curve_range = check_score_curves(args, cfg.TRAINER.NAME, zeroshot)
     check_nearest(args, cfg.TRAINER.NAME, zeroshot)
     check_audit(args, cfg.TRAINER.NAME, zeroshot)
     audit_only = args.audit_bank is not None and bool(args.bank) and not edits and not pool      # the bank alone: no data set, no test pass
@@ -916,7 +959,7 @@ def main(argv=None) -> Dict[str, float]:
     dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
     tr = trainer.build_trainer(cfg, dm, clip_weights=clip_sd, tokenizer=BPETokenizer(args.bpe_path), device=args.device,
                                reserve=(batch, 256, max(1024, len(classnames))), per_class_result=args.per_class_result,
-                               compute_cmat=args.confusion_matrix, **kw)
+                               compute_cmat=args.confusion_matrix, score_curves=curve_bins, score_range=curve_range, **kw)
     if load_classifiers:
         tr.model.load_classifiers(args.classifiers)
     elif from_bank:

@@ -127,6 +127,12 @@ RETRIEVE_SIGNATURES = {
     "ovmr_retrieve_finish": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p]),
 }
 
+# the fourth extension header include/ovmr_hip_curves.h (tests/test_curves_cpu.py holds the pair to each other)
+CURVES_SIGNATURES = {
+    "ovmr_eval_curves_state_bytes": (ctypes.c_long, [c_i, c_i]),
+    "ovmr_eval_curves": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, ctypes.c_float, ctypes.c_float, c_i, c_p, c_p]),
+}
+
 _lib = None
 
 
@@ -141,7 +147,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                            "ovmr_amd has no CPU fallback.")
     lib = ctypes.CDLL(p)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(AUDIT_SIGNATURES.items())
-                              + list(RETRIEVE_SIGNATURES.items())):
+                              + list(RETRIEVE_SIGNATURES.items()) + list(CURVES_SIGNATURES.items())):
         fn = getattr(lib, name)          # AttributeError if the .so does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -272,7 +278,56 @@ def eval_detail(mo: torch.Tensor, labels: torch.Tensor, k: int, counts: torch.Te
         raise OvmrError(f"ovmr_eval_detail failed with {rc} (B = {B}, C = {C}, k = {k})")
 
 
-_nearest_scratch: Dict[torch.device, torch.Tensor] = {}          # per device: the scratch of nearest_rows, grown on demand
+MAX_BINS = 4096                                                   # ovmr_eval_curves: the ceiling of bins (include/ovmr_hip_curves.h)
+
+
+def curve_scale(lo, hi, bins: int, where: str = "eval_curves"):
+    """(lo, hi, scale) of the slot function of include/ovmr_hip_curves.h as numpy float32: lo and hi rounded to fp32, lo < hi, both finite,
+    scale = fp32(bins) / (hi - lo) with the subtraction and the division rounded once each, finite and positive -- what the launcher
+    computes on the host.  Raises ValueError otherwise."""
+    for name, v in (("lo", lo), ("hi", hi)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            _refuse(where, name, "a number", type(v).__name__)
+    with np.errstate(all="ignore"):
+        flo, fhi = np.float32(lo), np.float32(hi)
+        if not np.isfinite(flo) or not np.isfinite(fhi):
+            _refuse(where, "lo" if not np.isfinite(flo) else "hi", "finite as fp32", repr(lo if not np.isfinite(flo) else hi))
+        if not flo < fhi:
+            _refuse(where, "hi", f"above lo = {float(flo)!r} as fp32", repr(hi))
+        scale = np.float32(bins) / np.float32(fhi - flo)
+    if not np.isfinite(scale) or not scale > 0:
+        _refuse(where, "hi", f"far enough from lo for bins / (hi - lo) to be a finite positive fp32 (bins = {bins})", f"lo = {lo!r}, hi = {hi!r}")
+    return flo, fhi, scale
+
+
+def eval_curves(mo: torch.Tensor, labels: torch.Tensor, lo: float, hi: float, bins: int, state: torch.Tensor):
+    """ovmr_eval_curves on the current stream (include/ovmr_hip_curves.h): mo [B, C] fp16 / fp32 on the GPU (stride(1) == 1, stride(0) >= C,
+    no copy), labels int64 [B]; state int32 [C, 2, bins + 3] accumulates: for every row whose label lies in [0, C) and every class c,
+    state[c, labels[b] == c, slot(mo[b, c])] += 1 with the slot function of the header over [lo, hi) in `bins` bins.  One launch; an empty
+    batch launches nothing."""
+    where = "eval_curves"
+    _want_rows(where, "mo", mo)
+    B, C = mo.shape
+    if C < 1:
+        _refuse(where, "mo", "of at least one column", f"{list(mo.shape)}")
+    if C > 1 and mo.stride(1) != 1 or B > 1 and mo.stride(0) < C:
+        _refuse(where, "mo", f"rows of unit column stride, at least {C} elements apart", f"strides {tuple(mo.stride())}")
+    _want(where, "labels", labels, (B,), torch.int64, mo.device, dense=True)
+    bins = _want_int(where, "bins", bins, 1, MAX_BINS)
+    flo, fhi, _ = curve_scale(lo, hi, bins, where)
+    _want(where, "state", state, (C, 2, bins + 3), torch.int32, mo.device, dense=True)
+    lib = load_library()
+    if B == 0:
+        return
+    with torch.cuda.device(mo.device):
+        ld = mo.stride(0) if B > 1 else max(C, mo.stride(0))
+        rc = lib.ovmr_eval_curves(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, _ptr(labels), B, C, float(flo), float(fhi), bins,
+                                  _ptr(state), ctypes.c_void_p(torch.cuda.current_stream(mo.device).cuda_stream))
+    if rc != 0:
+        raise OvmrError(f"ovmr_eval_curves failed with {rc} (B = {B}, C = {C}, lo = {float(flo)!r}, hi = {float(fhi)!r}, bins = {bins})")
+
+
+_nearest_scratch: Dict[torch.device, torch.Tensor] = {}         # per device: the scratch of nearest_rows, grown on demand
 
 
 def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Optional[torch.Tensor] = None, out=None):

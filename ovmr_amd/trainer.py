@@ -45,7 +45,7 @@ class _EvalTrainer:
     NOT_TRAINED = ""              # the NotImplementedError of forward_backward / train / save_model
 
     def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, per_class_result=False,
-                 compute_cmat=False):
+                 compute_cmat=False, score_curves=None, score_range=None):
         self.check_cfg(cfg)
         self.cfg, self.dm, self.device = cfg, dm, torch.device(device)
         self._clip_weights, self._tokenizer, self._reserve = clip_weights, tokenizer, reserve
@@ -59,6 +59,12 @@ class _EvalTrainer:
         self.build_model()
         # per_class_result / compute_cmat: what the reference reads from TEST.PER_CLASS_RESULT / TEST.COMPUTE_CMAT (evaluator.py:38, 165)
         self._evaluator_args = dict(per_class=per_class_result, confusion=compute_cmat)
+        # score_curves = BINS: every evaluator of the pass keeps the per-class score histograms over score_range (evaluator.Classification:
+        # curves=, score_range=; None = its default (0, 1), the range of MM_CLS_OP's probabilities -- logits have no natural range)
+        if score_range is not None and score_curves is None:
+            raise ValueError("score_range= belongs to score_curves=BINS")
+        if score_curves is not None:
+            self._evaluator_args.update(curves=score_curves, **({} if score_range is None else {"score_range": tuple(score_range)}))
         self.evaluator = self._new_evaluator()
         self.mode_evaluators = None                  # EVAL_MODE all: one Classification per mode of ALL_MODES, made by the first such test()
 
@@ -281,9 +287,9 @@ class MM_CLS_OP(_EvalTrainer):
     NOT_TRAINED = "training (autograd through CustomCLIP.forward, :310-338) is out of scope of the HIP hot path"
 
     def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, prompt_learner_state=None,
-                 per_class_result=False, compute_cmat=False):
+                 per_class_result=False, compute_cmat=False, score_curves=None, score_range=None):
         self._prompt_learner_state = prompt_learner_state
-        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve, per_class_result, compute_cmat)
+        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve, per_class_result, compute_cmat, score_curves, score_range)
 
     # :369-370
     def check_cfg(self, cfg):
