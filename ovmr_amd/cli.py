@@ -324,17 +324,23 @@ def ranked_predictions(paths: Sequence[str], values, indices, classnames: Sequen
     return [(p, [(int(c), classnames[int(c)], float(v)) for v, c in zip(vs, cs)]) for p, vs, cs in zip(paths, values.tolist(), indices.tolist())]
 
 
-def write_predictions(path: str, predictions) -> None:
-    """predictions.csv: `image,rank,label,classname,score`, one line per (image, rank) in input order, ranks 0..k-1; the score is
-    repr(float), so it parses back to the same value."""
+def _write_csv(path: str, columns: Sequence[str], lines, float_columns=()) -> None:
+    """The writer behind every table of the runner: the header, then one line per entry of `lines` in order; the columns whose
+    positions float_columns names are written as repr(float), so they parse back to the same value.  Creates the directory."""
     import csv
     os.makedirs(osp.dirname(path) or ".", exist_ok=True)
     with open(path, "w", newline="") as f:
         w = csv.writer(f, delimiter=",", lineterminator="\n")
-        w.writerow(["image", "rank", "label", "classname", "score"])
-        for image, ranks in predictions:
-            for rank, (label, name, score) in enumerate(ranks):
-                w.writerow([image, rank, label, name, repr(float(score))])
+        w.writerow(columns)
+        for line in lines:
+            w.writerow([repr(float(x)) if i in float_columns else x for i, x in enumerate(line)])
+
+
+def write_predictions(path: str, predictions) -> None:
+    """predictions.csv: `image,rank,label,classname,score`, one line per (image, rank) in input order, ranks 0..k-1; the score is
+    repr(float), so it parses back to the same value."""
+    lines = [(image, rank, label, name, score) for image, ranks in predictions for rank, (label, name, score) in enumerate(ranks)]
+    _write_csv(path, ["image", "rank", "label", "classname", "score"], lines, (4,))
 
 
 MAX_PER_CLASS = 32            # ovmr_retrieve_update (include/ovmr_hip_retrieve.h)
@@ -419,13 +425,7 @@ def retrieval_rows(values, indices, images: Sequence[str], classnames: Sequence[
 def write_retrieval(path: str, rows) -> None:
     """retrieval.csv: `label,classname,rank,image,score`, one line per filled (class, rank) in class order then rank; the score is
     repr(float), as in predictions.csv."""
-    import csv
-    os.makedirs(osp.dirname(path) or ".", exist_ok=True)
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f, delimiter=",", lineterminator="\n")
-        w.writerow(RETRIEVAL_COLUMNS)
-        for label, name, rank, image, score in rows:
-            w.writerow([label, name, rank, image, repr(float(score))])
+    _write_csv(path, RETRIEVAL_COLUMNS, rows, (4,))
 
 
 MAX_NEAREST = 32              # ovmr_nearest_rows (include/ovmr_hip_nearest.h)
@@ -447,13 +447,7 @@ def nearest_neighbours(paths: Sequence[str], indices, similarities, rows, classn
 def write_neighbours(path: str, neighbours) -> None:
     """neighbours.csv: `image,rank,label,classname,neighbour,row,exemplar,similarity`, one line per (image, class rank, neighbour rank) in
     input order; the similarity is repr(float), as the score of predictions.csv."""
-    import csv
-    os.makedirs(osp.dirname(path) or ".", exist_ok=True)
-    with open(path, "w", newline="") as f:
-        w = csv.writer(f, delimiter=",", lineterminator="\n")
-        w.writerow(NEIGHBOUR_COLUMNS)
-        for image, rank, label, name, j, row, exemplar, sim in neighbours:
-            w.writerow([image, rank, label, name, j, row, exemplar, repr(float(sim))])
+    _write_csv(path, NEIGHBOUR_COLUMNS, neighbours, (7,))
 
 
 def check_nearest(args, trainer_name: str, zeroshot: bool):
@@ -496,14 +490,8 @@ def bank_audit_tables(audit: dict, classnames: Sequence[str], shots: Sequence[in
 def write_bank_audit(out_dir: str, tables) -> None:
     """bank_audit.csv, bank_audit_neighbours.csv and bank_audit_classes.csv in out_dir; similarities are repr(float), as the score of
     predictions.csv."""
-    import csv
-    os.makedirs(out_dir or ".", exist_ok=True)
     for name, cols, lines, floats in zip(AUDIT_FILES, (AUDIT_COLUMNS, AUDIT_NEIGHBOUR_COLUMNS, AUDIT_CLASS_COLUMNS), tables, ((5, 9), (5,), ())):
-        with open(osp.join(out_dir, name), "w", newline="") as f:
-            w = csv.writer(f, delimiter=",", lineterminator="\n")
-            w.writerow(cols)
-            for line in lines:
-                w.writerow([repr(float(x)) if i in floats else x for i, x in enumerate(line)])
+        _write_csv(osp.join(out_dir, name), cols, lines, floats)
 
 
 def check_audit(args, trainer_name: str, zeroshot: bool):

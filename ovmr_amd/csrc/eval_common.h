@@ -1,9 +1,16 @@
 // What the evaluator's kernels share (fusion_head.hip: xval_argmax_reduce, eval_counts_kernel; topk.hip: topk_rows_kernel;
-// eval_detail.hip: eval_detail_kernel): the selection key and round of the library's total order, and the wave-aggregated histogram update.
+// eval_detail.hip: eval_detail_kernel): the selection key and round of the library's total order, and the wave-aggregated histogram update;
+// and what the kernels that work along the COLUMNS of a [B, C] output share (retrieve.hip, eval_curves.hip): the launchers' test of that
+// matrix and the transposed tile load.
 #pragma once
 #include "common.h"
 
 namespace {
+
+// out [B, C], rows ld elements apart, as ovmr_retrieve_update and ovmr_eval_curves take it: there, rows at least C apart, element-aligned
+inline bool bad_out_matrix(const void* out, int out_is_f32, long ld, int C) {
+    return !out || ld < C || (uintptr_t)out & (out_is_f32 ? 3 : 1);
+}
 
 // v of lane `lane`, for all lanes
 __device__ __forceinline__ int wave_read(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
@@ -70,6 +77,44 @@ __device__ __forceinline__ unsigned long long topk_round(const T* __restrict__ r
         if (other > best) best = other;
     }
     return best;
+}
+
+// The [ROWS rows][TILE classes] corner at (r0, c0) of out [B, C] (TILE at least a 16-byte vector wide), loaded along the rows -- 16-byte
+// loads where the address is aligned and the vector lies within the C classes, element loads otherwise (C odd: every second fp16 row)
+// -- and written TRANSPOSED to LDS as fp32, tile[class][row], rows past B and classes past C as zeros; the caller's barrier follows.
+// PITCH = 66 floats between two classes for ROWS = 64: ds_write_b32 and ds_read_b32 bank by (address / 4) mod 32 over groups of 32
+// lanes; the 32 lanes of a store group hold 16 rows x 2 vectors (fp16) or 8 rows x 4 vectors (fp32) and element e of every vector goes
+// out in one store: bank = (2 class + row) mod 32 is distinct over the group; a reader with lane = row walks consecutive addresses.
+template <typename T, int TILE, int ROWS, int PITCH>
+__device__ __forceinline__ void load_tile_transposed(float* tile, const T* out, long ld, long r0, int B, long c0, int C, int tid) {
+    constexpr int V = 16 / (int)sizeof(T);                           // elements per 16-byte vector
+    constexpr int SEGS = TILE / V;                                   // vectors per row of the tile
+    if (tid < ROWS * SEGS) {
+        const int lrow = tid / SEGS, seg = tid % SEGS;               // the loader's row and vector
+        float v[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) v[e] = 0.f;
+        const long c = c0 + seg * V;
+        if (r0 + lrow < B && c < C) {
+            const T* p = out + (r0 + lrow) * ld + c;
+            if (c + V <= C && (((uintptr_t)p) & 15) == 0) {
+                if constexpr (sizeof(T) == 4) {
+                    const float4 q = *(const float4*)p;
+                    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+                } else {
+                    const half8_t q = *(const half8_t*)p;
+#pragma unroll
+                    for (int e = 0; e < V; ++e) v[e] = (float)q[e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < V; ++e)
+                    if (c + e < C) v[e] = (float)p[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) tile[(seg * V + e) * PITCH + lrow] = v[e];
+    }
 }
 
 }  // namespace

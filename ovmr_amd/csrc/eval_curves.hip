@@ -1,7 +1,7 @@
 // Score curves from the test pass: per class, the histogram of the scores of its own rows and of everybody else's, over a stream of
 // [B, C] output matrices (include/ovmr_hip_curves.h; DESIGN.md sections 4 and 6).  No counterpart in the reference.  The work goes along
-// the COLUMNS of the output, as retrieve.hip's does, and that file's loader is this one's: a [64 rows][16 classes] corner is read along
-// the rows and turned by ninety degrees through LDS, so that a wave takes a class with lane = row.
+// the COLUMNS of the output, as retrieve.hip's does, through the same loader (eval_common.h: load_tile_transposed): a [64 rows][16 classes]
+// corner is read along the rows and turned by ninety degrees through LDS, so that a wave takes a class with lane = row.
 //
 // eval_curves_kernel<T>: a 256-thread workgroup owns EC_TILE = 16 consecutive classes (blockIdx.x), wave w the EC_CPW = 4 classes
 // 4 w .. 4 w + 3, and walks the chunks of EC_ROWS = 64 rows blockIdx.y, blockIdx.y + gridDim.y, ...  Unlike the lists of retrieve.hip the
@@ -9,9 +9,7 @@
 // 1000 classes is 63 x 4 workgroups and needs no narrower tile to fill the machine, and there is ONE tiling.  gridDim.y is capped at
 // EC_MAX_ROW_BLOCKS; beyond 64 x that many rows a workgroup takes several chunks.  Per chunk:
 //   * each wave reads the 64 labels of the chunk, one coalesced load, lane = row;
-//   * the corner is loaded along the rows -- 16-byte loads where the address is aligned and the vector lies within the C classes, element
-//     loads otherwise (C odd: every second fp16 row) -- and written TRANSPOSED to LDS as fp32, tile[class][row], pitch 66 floats (the
-//     derivation is in retrieve.hip: the 32 lanes of a store group fall into 32 distinct banks, the read walks consecutive addresses);
+//   * load_tile_transposed writes the corner to LDS as fp32, tile[class][row], pitch 66 floats;
 //   * per class, lane l computes the slot of row l's score and its polarity (label == class), and ONE wave_histogram_add
 //     (eval_common.h) sends one atomic per DISTINCT cell: after a softmax that is one to three per (class, chunk) -- nearly every
 //     negative of a class falls into one slot, which as 64 same-address atomics would serialise -- with logits it can be 64.
@@ -29,7 +27,7 @@ constexpr int EC_MAX_BINS = 4096;
 constexpr int EC_TILE = 16;                 // classes per workgroup: four per wave
 constexpr int EC_CPW = EC_TILE / 4;
 constexpr int EC_ROWS = 64;                 // rows per chunk: one per lane
-constexpr int EC_PITCH = EC_ROWS + 2;       // floats between two classes of the LDS tile (retrieve.hip: RT_PITCH)
+constexpr int EC_PITCH = EC_ROWS + 2;       // floats between two classes of the LDS tile (eval_common.h: load_tile_transposed)
 constexpr int EC_MAX_ROW_BLOCKS = 256;      // gridDim.y at most: 16 384 rows in one sweep
 
 // the slot of include/ovmr_hip_curves.h; klo / khi: the value part of the selection key of lo / hi.  -ffp-contract=off (build.py): the
@@ -52,35 +50,8 @@ __global__ __launch_bounds__(256) void eval_curves_kernel(const T* __restrict__ 
     const long c0 = (long)blockIdx.x * EC_TILE;                      // < C: gridDim.x is ceil(C / EC_TILE)
     const int S = bins + 3;
     const unsigned klo = (unsigned)(topk_key(lo, 0) >> 32), khi = (unsigned)(topk_key(hi, 0) >> 32);
-    constexpr int V = 16 / (int)sizeof(T);                           // elements per 16-byte vector
-    constexpr int SEGS = EC_TILE / V;                                // vectors per row of the tile
     for (long r0 = (long)blockIdx.y * EC_ROWS; r0 < B; r0 += (long)gridDim.y * EC_ROWS) {      // (workgroup-uniform)
-        if (tid < EC_ROWS * SEGS) {
-            const int lrow = tid / SEGS, seg = tid % SEGS;           // the loader's row and vector
-            float v[V];
-#pragma unroll
-            for (int e = 0; e < V; ++e) v[e] = 0.f;
-            const long c = c0 + seg * V;
-            if (r0 + lrow < B && c < C) {
-                const T* p = out + (r0 + lrow) * ld + c;
-                if (c + V <= C && (((uintptr_t)p) & 15) == 0) {
-                    if constexpr (sizeof(T) == 4) {
-                        const float4 q = *(const float4*)p;
-                        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-                    } else {
-                        const half8_t q = *(const half8_t*)p;
-#pragma unroll
-                        for (int e = 0; e < V; ++e) v[e] = (float)q[e];
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < V; ++e)
-                        if (c + e < C) v[e] = (float)p[e];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < V; ++e) tile[(seg * V + e) * EC_PITCH + lrow] = v[e];
-        }
+        load_tile_transposed<T, EC_TILE, EC_ROWS, EC_PITCH>(tile, out, ld, r0, B, c0, C, tid);
         const bool row_ok = r0 + lane < B;
         const long label = row_ok ? (long)labels[r0 + lane] : -1;
         const bool offered = row_ok && label >= 0 && label < C;
@@ -109,9 +80,8 @@ long ovmr_eval_curves_state_bytes(int C, int bins) {
 
 int ovmr_eval_curves(const void* out, int out_is_f32, long ld, const int64_t* labels, int B, int C, float lo, float hi, int bins,
                      int* state, ovmr_stream stream) {
-    if (bad_state(C, bins) || B < 0 || ld < C) return OVMR_E_ARG;
-    if (!out || !labels || !state) return OVMR_E_ARG;
-    if ((uintptr_t)out & (out_is_f32 ? 3 : 1) || (uintptr_t)labels & 7 || (uintptr_t)state & 3) return OVMR_E_ARG;
+    if (bad_state(C, bins) || B < 0 || bad_out_matrix(out, out_is_f32, ld, C)) return OVMR_E_ARG;
+    if (!labels || !state || (uintptr_t)labels & 7 || (uintptr_t)state & 3) return OVMR_E_ARG;
     if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi)) return OVMR_E_ARG;
     const volatile float width = hi - lo;                            // rounded to fp32 here, not carried in a wider register
     const volatile float scale = (float)bins / width;

@@ -59,5 +59,8 @@ int launch_fused_softmax(const half_t* l0, const half_t* l1, const half_t* l2, c
 int launch_text_ensemble(const half_t* feats, int T, int rows, int E, half_t* out, hipStream_t s);
 int launch_topk_rows(const void* out, int out_is_f32, long ld, int B, int C, int k, float* values, int32_t* indices, const int64_t* labels,
                      int* hits, hipStream_t s);
+// neighbours.hip: the one-wave-per-query launch of ovmr_neighbours_rows (max_range in [1, 4096]; operands already checked by the caller)
+int launch_neighbours_short(const void* Q, int B, const void* X, long R, int D, int k, const int32_t* ranges, const int32_t* exclude,
+                            int max_range, float* values, int32_t* indices, hipStream_t stream);
 int launch_eval_detail(const void* out, int out_is_f32, long ld, const int64_t* labels, int B, int C, int k, int* counts, int* hits,
                        int* class_hits, int* cmat, hipStream_t s);

@@ -22,12 +22,13 @@
 //     and skips, by the same uniform test, every tile none of its ranges reaches.
 //   * per-slice lists -> scratch [B][S][k] keys (0 = no row).
 // Launch 2, nearest_merge_kernel: one wave per query takes the k largest of its S k keys with the same insertion, lane j keeps rank j and
-// stores index and value (decoded from the key) coalesced.  No atomics on global memory, no counters, nothing to re-arm: the scratch is
+// stores index and value (key_decode) coalesced.  No atomics on global memory, no counters, nothing to re-arm: the scratch is
 // written completely before it is read.
 //
 // include/ovmr_hip_audit.h adds an excluded row range per query: nearest_tiles_kernel<QB, EXCL = true> keeps the clamped exclusions beside the
 // ranges in LDS and turns excluded candidates into key 0 (the instantiations without EXCL are the code they were), and ovmr_neighbours_rows
-// takes the one-wave-per-query launch of neighbours.hip where the host promises short ranges.  The list helpers live in nearest_list.h.
+// takes the one-wave-per-query launch of neighbours.hip where the host promises short ranges.  The list helpers, key_decode and the
+// range clamp (clamp_pair) live in nearest_list.h.
 //
 // Registers (hipcc -O3, gfx950, --save-temps): see DESIGN.md section 4.
 #include "../../include/ovmr_hip_nearest.h"
@@ -49,7 +50,8 @@ constexpr int NR_KMAX = 32;
 constexpr int NB_MAX_RANGE = 4096;          // ovmr_neighbours_rows: the ceiling of max_range, the project's ceiling for a class (agg_max_len)
 constexpr int NR_CUS = 256;                 // the launcher's S is a pure function of B and R (ovmr_nearest_scratch_bytes): no device query
 
-using ovmr_list::wave_read_key; using ovmr_list::list_insert; using ovmr_list::list_offer; using ovmr_list::key_value;   // nearest_list.h
+using ovmr_list::wave_read_key; using ovmr_list::list_insert; using ovmr_list::list_offer;   // nearest_list.h
+using ovmr_list::key_decode; using ovmr_list::clamp_pair;
 
 struct NearestArgs {
     const half_t* Q; const half_t* X; const int32_t* ranges; key_t* scratch;
@@ -95,12 +97,8 @@ __global__ __launch_bounds__(256) void nearest_tiles_kernel(const NearestArgs a)
     // every wave: the ranges of all BM queries (lane = query), clamped to [0, R]; does any of them meet the slice?
     unsigned lo = 0, hi = 0;
     if (lane < BM && q0 + lane < a.B) {
-        if (a.ranges) {
-            const long l = a.ranges[2 * (long)(q0 + lane)], u = a.ranges[2 * (long)(q0 + lane) + 1];
-            lo = (unsigned)std::min<long>(std::max<long>(l, 0), (long)R);
-            hi = (unsigned)std::min<long>(std::max<long>(u, (long)lo), (long)R);
-        } else
-            hi = R;
+        if (a.ranges) clamp_pair(a.ranges, q0 + lane, (long)R, lo, hi);
+        else hi = R;
     }
     const bool meets = std::max(lo, s0) < std::min(hi, s1);
     unsigned wlo = meets ? lo : 0xFFFFFFFFu, whi = meets ? hi : 0u;
@@ -122,11 +120,7 @@ __global__ __launch_bounds__(256) void nearest_tiles_kernel(const NearestArgs a)
     if constexpr (EXCL) {
         if (wave == 1 && lane < BM) {                               // clamped like the range; rows past B: empty
             unsigned xlo = 0, xhi = 0;
-            if (q0 + lane < a.B) {
-                const long l = a.exclude[2 * (long)(q0 + lane)], u = a.exclude[2 * (long)(q0 + lane) + 1];
-                xlo = (unsigned)std::min<long>(std::max<long>(l, 0), (long)R);
-                xhi = (unsigned)std::min<long>(std::max<long>(u, (long)xlo), (long)R);
-            }
+            if (q0 + lane < a.B) clamp_pair(a.exclude, q0 + lane, (long)R, xlo, xhi);
             qxlo[lane] = xlo; qxhi[lane] = xhi;
         }
     }
@@ -241,8 +235,7 @@ __global__ __launch_bounds__(256) void nearest_merge_kernel(const key_t* __restr
         list_offer(mine, cand, lane, k);
     }
     if (lane < k) {
-        indices[b * k + lane] = mine ? (int32_t)(0xFFFFFFFFu - (unsigned)mine) : -1;
-        values[b * k + lane] = mine ? key_value(mine) : -INFINITY;
+        key_decode(mine, indices[b * k + lane], values[b * k + lane]);
     }
 }
 
@@ -273,13 +266,19 @@ int pick_slices(int B, long R) {
 
 bool bad_shape(int B, long R, int k) { return B < 0 || R < 1 || R >= 0xFFFFFFFFL || k < 1 || k > NR_KMAX; }
 
+// what the tiled and the short path ask of a search alike: its extents, then (the caller returns 0 for B == 0 in between) its operands
+bool bad_search_shape(int B, long R, int D, int k) { return bad_shape(B, R, k) || k > R || D < 64 || D > 1024 || D % 64; }
+bool bad_search_operands(const void* Q, const void* X, const int32_t* ranges, const int32_t* exclude, const float* values,
+                         const int32_t* indices) {
+    if (!Q || !X || !values || !indices) return true;
+    return ((uintptr_t)Q | (uintptr_t)X) & 15 || ((uintptr_t)values | (uintptr_t)indices | (uintptr_t)ranges | (uintptr_t)exclude) & 3;
+}
+
 int nearest_rows(const void* Q, int B, const void* X, long R, int D, int k, const int32_t* ranges, float* values, int32_t* indices,
                  void* scratch, long scratch_bytes, int S, hipStream_t stream, const int32_t* exclude = nullptr) {
-    if (bad_shape(B, R, k) || k > R || D < 64 || D > 1024 || D % 64 || S < 1) return OVMR_E_ARG;
+    if (bad_search_shape(B, R, D, k) || S < 1) return OVMR_E_ARG;
     if (B == 0) return 0;
-    if (!Q || !X || !values || !indices || !scratch) return OVMR_E_ARG;
-    if (((uintptr_t)Q | (uintptr_t)X) & 15 || (uintptr_t)scratch & 7 || ((uintptr_t)values | (uintptr_t)indices | (uintptr_t)ranges | (uintptr_t)exclude) & 3)
-        return OVMR_E_ARG;
+    if (bad_search_operands(Q, X, ranges, exclude, values, indices) || !scratch || (uintptr_t)scratch & 7) return OVMR_E_ARG;
     if (scratch_bytes < 0 || (unsigned long long)scratch_bytes < (unsigned long long)B * S * k * 8) return OVMR_E_ARG;
     // 64-query tiles where they fit the 160 KB of LDS and there are more than 32 queries, else 32-query tiles
     const int BM = (B > 32 && nearest_lds_bytes(64, D, exclude != nullptr) <= 160 * 1024) ? 64 : 32;
@@ -332,11 +331,9 @@ int ovmr_debug_neighbours_rows(const void* queries_f16, int B, const void* bank_
                                int path, int slices, ovmr_stream stream) {
     if (path == 0)
         return nearest_rows(queries_f16, B, bank_f16, R, D, k, ranges, values, indices, scratch, scratch_bytes, slices, (hipStream_t)stream, exclude);
-    if (path != 1 || bad_shape(B, R, k) || k > R || D < 64 || D > 1024 || D % 64 || max_range < 1 || max_range > NB_MAX_RANGE) return OVMR_E_ARG;
+    if (path != 1 || bad_search_shape(B, R, D, k) || max_range < 1 || max_range > NB_MAX_RANGE) return OVMR_E_ARG;
     if (B == 0) return 0;
-    if (!queries_f16 || !bank_f16 || !values || !indices || !ranges) return OVMR_E_ARG;
-    if (((uintptr_t)queries_f16 | (uintptr_t)bank_f16) & 15 || ((uintptr_t)values | (uintptr_t)indices | (uintptr_t)ranges | (uintptr_t)exclude) & 3)
-        return OVMR_E_ARG;
+    if (bad_search_operands(queries_f16, bank_f16, ranges, exclude, values, indices) || !ranges) return OVMR_E_ARG;
     return launch_neighbours_short(queries_f16, B, bank_f16, R, D, k, ranges, exclude, max_range, values, indices, (hipStream_t)stream);
 }
 

@@ -1,11 +1,14 @@
 // The sorted key list of one query, shared by the nearest-exemplar kernels (nearest.hip: nearest_tiles_kernel, nearest_merge_kernel;
-// neighbours.hip: neighbours_short_kernel).  A key is topk_key((float)score, bank row) (eval_common.h): 64 bits, larger = better, 0 = no
-// row; the keys of one query are distinct, so "the k largest" is one set in one order.
+// neighbours.hip: neighbours_short_kernel) and, one list per class, by retrieve.hip.  A key is topk_key((float)score, bank row)
+// (eval_common.h): 64 bits, larger = better, 0 = no row; the keys of one query are distinct, so "the k largest" is one set in one order.
+// Beside the list: what a key decodes to, and the clamp of a row range read from device memory.
 #pragma once
 #include "eval_common.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 namespace ovmr_list {
 
@@ -46,8 +49,19 @@ __device__ __forceinline__ float key_value(nkey_t key) {
     return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
 }
 
-}  // namespace ovmr_list
+// what a list entry says: (row, value), or (-1, -inf) for an empty one (retrieve_finish_kernel states the same with an int64 row)
+__device__ __forceinline__ void key_decode(nkey_t key, int32_t& index, float& value) {
+    index = key ? (int32_t)(0xFFFFFFFFu - (unsigned)key) : -1;
+    value = key ? key_value(key) : -INFINITY;
+}
 
-// neighbours.hip: the one-wave-per-query launch of ovmr_neighbours_rows (max_range in [1, 4096]; operands already checked by the caller)
-int launch_neighbours_short(const void* Q, int B, const void* X, long R, int D, int k, const int32_t* ranges, const int32_t* exclude,
-                            int max_range, float* values, int32_t* indices, hipStream_t stream);
+// pair b of pairs [*, 2] (a range or an exclusion, read from device memory) clamped to the R rows: 0 <= lo <= hi <= R whatever it holds
+template <typename I>   // unsigned or long
+__device__ __forceinline__ void clamp_pair(const int32_t* pairs, long b, long R, I& lo, I& hi) {
+    const long l = pairs[2 * b], u = pairs[2 * b + 1];
+    const long cl = std::min<long>(std::max<long>(l, 0), R);
+    lo = (I)cl;
+    hi = (I)std::min<long>(std::max<long>(u, cl), R);
+}
+
+}  // namespace ovmr_list

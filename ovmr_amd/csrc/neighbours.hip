@@ -13,7 +13,7 @@
 //   * fp32 accumulation; rows behind the range's end read its last row again and never become candidates;
 //   * ONE rounding to fp16, key = topk_key((float)s, r); rows that are excluded or behind hi' = min(hi, lo + max_range) get key 0;
 //     lane (g, p < PU) offers row base + 8 p + g to list_offer (nearest_list.h), lane = rank;
-//   * lanes 0 .. k-1 store index and value (decoded from the key as nearest_merge_kernel does) coalesced.
+//   * lanes 0 .. k-1 store index and value (key_decode, nearest_list.h) coalesced.
 //
 // The score of a (query, row) pair does not depend on the row's position in its range, on the pass, on PU or on what shares the workgroup:
 // a lane sums the products of its columns in ONE fixed order (column groups ascending, the eight columns of a chunk ascending), each
@@ -53,16 +53,10 @@ __global__ __launch_bounds__(256) void neighbours_short_kernel(const half_t* __r
     if (b >= B) return;
 
     // the range and the exclusion, clamped to the bank; hi' honours the host's promise whatever the device values say
-    const long R_ = (long)R;
-    const long l = ranges[2 * b], u = ranges[2 * b + 1];
-    const long lo = std::min<long>(std::max<long>(l, 0), R_);
-    const long hi = std::min<long>(std::min<long>(std::max<long>(u, lo), R_), lo + max_range);
-    long xlo = 0, xhi = 0;
-    if (exclude) {
-        const long xl = exclude[2 * b], xu = exclude[2 * b + 1];
-        xlo = std::min<long>(std::max<long>(xl, 0), R_);
-        xhi = std::min<long>(std::max<long>(xu, xlo), R_);
-    }
+    long lo, hi, xlo = 0, xhi = 0;
+    ovmr_list::clamp_pair(ranges, b, (long)R, lo, hi);
+    hi = std::min<long>(hi, lo + max_range);
+    if (exclude) ovmr_list::clamp_pair(exclude, b, (long)R, xlo, xhi);
 
     nkey_t mine = 0;
     for (long base = lo; base < hi; base += 8 * PU) {               // (an empty range: no trip, nothing is read)
@@ -117,8 +111,7 @@ __global__ __launch_bounds__(256) void neighbours_short_kernel(const half_t* __r
         ovmr_list::list_offer(mine, cand, lane, k);
     }
     if (lane < k) {
-        indices[b * k + lane] = mine ? (int32_t)(0xFFFFFFFFu - (unsigned)mine) : -1;
-        values[b * k + lane] = mine ? ovmr_list::key_value(mine) : -INFINITY;
+        ovmr_list::key_decode(mine, indices[b * k + lane], values[b * k + lane]);
     }
 }
 

@@ -10,11 +10,8 @@
 // retrieve_update_kernel<T, RT_TILE>: a 256-thread workgroup owns RT_TILE = 16 consecutive classes, wave w the RT_CPW = 4 classes 4 w .. 4 w + 3,
 // whose lists stay in registers for the whole kernel (loaded from the state once, stored once).  The rows of the batch are walked in
 // chunks of 64:
-//   * the chunk's [64 rows][16 classes] corner is loaded along the rows -- 16-byte loads where the address is aligned and the vector lies
-//     within the C classes, element loads otherwise (C odd: every second fp16 row) -- and written TRANSPOSED to LDS as fp32,
-//     tile[class][row], pitch 66 floats: ds_write_b32 and ds_read_b32 bank by (address / 4) mod 32 over groups of 32 lanes; the 32 lanes
-//     of a store group hold 16 rows x 2 vectors (fp16) or 8 rows x 4 vectors (fp32) and element e of every vector goes out in one store:
-//     bank = (2 class + row) mod 32 is distinct over the group; the read below walks consecutive addresses;
+//   * the chunk's [64 rows][16 classes] corner goes to LDS turned by ninety degrees, tile[class][row] in fp32, through
+//     load_tile_transposed (eval_common.h; the pitch of 66 floats is derived there);
 //   * per class, lane l reads the score of row l of the chunk and builds the key; rows at or past B and scores below the row's floor
 //     (compared on the value part of the key) offer key 0 = nothing; list_offer does the rest.
 // Class tiles past C and rows past B are masked: nothing outside out[0:B, 0:C], floor[0:B] and state[0:C, 0:m] is touched.
@@ -27,7 +24,8 @@
 // Measured: DESIGN.md section 4.
 //
 // retrieve_merge_kernel: one wave per class, the other list's m keys are the candidates of ONE list_offer.  retrieve_finish_kernel: one
-// thread per (class, rank) decodes key -> (value, index); the index stays unsigned to the end and widens to int64 here.
+// thread per (class, rank) decodes key -> (value, index); the index stays unsigned to the end and widens to int64 here.  It is
+// key_decode of nearest_list.h written out: through the helper the kernel's register count moved (13 -> 12 VGPRs), so it keeps its own lines.
 #include "../../include/ovmr_hip_retrieve.h"
 #include "common.h"
 #include "eval_common.h"
@@ -42,7 +40,7 @@ constexpr int RT_TILE = 16;                 // classes per workgroup: four per w
 constexpr int RT_TILE_NARROW = 4;           // ... and one per wave up to RT_NARROW_MAX_C classes, where waves are what a launch lacks
 constexpr int RT_NARROW_MAX_C = 2048;
 constexpr int RT_ROWS = 64;                 // rows per chunk: one per lane
-constexpr int RT_PITCH = RT_ROWS + 2;       // floats between two classes of the LDS tile (see above)
+constexpr int RT_PITCH = RT_ROWS + 2;       // floats between two classes of the LDS tile (eval_common.h: load_tile_transposed)
 constexpr long RT_MAX_IMAGES = 0xFFFFFFFFL; // image indices are < 2^32 - 1: the low half of a key is 0xFFFFFFFF - index >= 1
 
 using ovmr_list::list_offer; using ovmr_list::key_value;   // nearest_list.h
@@ -70,33 +68,8 @@ __global__ __launch_bounds__(256) void retrieve_update_kernel(const T* __restric
                 if (r0 + lrow < B && c < C) v = (float)out[(long)(r0 + lrow) * ld + c];
                 tile[col * RT_PITCH + lrow] = v;
             }
-        } else if (tid < RT_ROWS * (RT_TILE / V)) {
-            constexpr int SEGS = RT_TILE / V;                        // vectors per row of the tile
-            const int lrow = tid / SEGS, seg = tid % SEGS;           // the loader's row and vector
-            float v[V];
-#pragma unroll
-            for (int e = 0; e < V; ++e) v[e] = 0.f;
-            const long c = c0 + seg * V;
-            if (r0 + lrow < B && c < C) {
-                const T* p = out + (long)(r0 + lrow) * ld + c;
-                if (c + V <= C && (((uintptr_t)p) & 15) == 0) {
-                    if constexpr (sizeof(T) == 4) {
-                        const float4 q = *(const float4*)p;
-                        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-                    } else {
-                        const half8_t q = *(const half8_t*)p;
-#pragma unroll
-                        for (int e = 0; e < V; ++e) v[e] = (float)q[e];
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < V; ++e)
-                        if (c + e < C) v[e] = (float)p[e];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < V; ++e) tile[(seg * V + e) * RT_PITCH + lrow] = v[e];
-        }
+        } else
+            load_tile_transposed<T, RT_TILE, RT_ROWS, RT_PITCH>(tile, out, ld, r0, B, c0, C, tid);
         __syncthreads();
         const bool row_ok = r0 + lane < B;
         const unsigned idx = base + (unsigned)(r0 + lane);           // < 2^32 - 1 where row_ok (checked by the launcher)
@@ -130,7 +103,7 @@ __global__ __launch_bounds__(256) void retrieve_finish_kernel(const rkey_t* __re
                                                               int64_t* __restrict__ indices) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const rkey_t key = state[i];
+    const rkey_t key = state[i];                                     // ovmr_list::key_decode with an int64 index, spelled out: see above
     indices[i] = key ? (int64_t)(0xFFFFFFFFu - (unsigned)key) : -1;
     values[i] = key ? key_value(key) : -INFINITY;
 }
@@ -153,9 +126,9 @@ int ovmr_retrieve_reset(void* state, int C, int m, ovmr_stream stream) {
 
 int ovmr_retrieve_update(const void* out, int out_is_f32, long ld, int B, int C, int m, long base, const float* floor, void* state,
                          ovmr_stream stream) {
-    if (bad_lists(C, m) || B < 0 || ld < C || base < 0 || base > RT_MAX_IMAGES || base + B > RT_MAX_IMAGES) return OVMR_E_ARG;
-    if (!out || !state) return OVMR_E_ARG;
-    if ((uintptr_t)out & (out_is_f32 ? 3 : 1) || (uintptr_t)floor & 3 || (uintptr_t)state & 7) return OVMR_E_ARG;
+    if (bad_lists(C, m) || B < 0 || base < 0 || base > RT_MAX_IMAGES || base + B > RT_MAX_IMAGES) return OVMR_E_ARG;
+    if (bad_out_matrix(out, out_is_f32, ld, C) || !state) return OVMR_E_ARG;
+    if ((uintptr_t)floor & 3 || (uintptr_t)state & 7) return OVMR_E_ARG;
     if (B == 0) return 0;
     const bool narrow = C <= RT_NARROW_MAX_C;
     const int tile = narrow ? RT_TILE_NARROW : RT_TILE;

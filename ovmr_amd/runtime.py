@@ -162,8 +162,14 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _stream_on(dev):
+    """The current stream of device `dev` (None: of the current device) as the library takes it; the wrappers outside Engine follow their
+    operands' device."""
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return _stream_on(None)
 
 
 class OvmrError(RuntimeError):
@@ -224,6 +230,25 @@ def _want_rows(where: str, name: str, mo):
     _want(where, name, mo, (None, None), (torch.float16, torch.float32), "cuda")
 
 
+def _row_matrix(where: str, name: str, mo) -> int:
+    """mo [B, C] as the library reads it without a copy: unit column stride, rows at least C elements apart -> ld, the row stride to
+    hand over (a single row's stride says nothing: at least C)."""
+    B, C = mo.shape
+    if C > 1 and mo.stride(1) != 1 or B > 1 and mo.stride(0) < C:
+        _refuse(where, name, f"rows of unit column stride, at least {C} elements apart", f"strides {tuple(mo.stride())}")
+    return mo.stride(0) if B > 1 else max(C, mo.stride(0))
+
+
+def _want_out_pair(where: str, out, shape, index_dtype, dev):
+    """out = (values fp32, indices) of a selection: both of `shape`, dense, on dev; None = the wrapper allocates."""
+    if out is None:
+        return
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        _refuse(where, "out", "a pair (values, indices)", type(out).__name__)
+    _want(where, "out[0]", out[0], shape, torch.float32, dev, dense=True)
+    _want(where, "out[1]", out[1], shape, index_dtype, dev, dense=True)
+
+
 def topk_rows(mo: torch.Tensor, k: int, labels: Optional[torch.Tensor] = None, hits: Optional[torch.Tensor] = None):
     """ovmr_topk_rows on the current stream: mo [B, C] fp16 / fp32 on the GPU (rows may be strided: stride(1) == 1, stride(0) >= C, no
     copy) -> (values fp32 [B, k], indices int32 [B, k]), best first in the library's total order (include/ovmr_hip.h).  labels int64 [B]
@@ -243,9 +268,9 @@ def topk_rows(mo: torch.Tensor, k: int, labels: Optional[torch.Tensor] = None, h
     with torch.cuda.device(mo.device):
         values = torch.empty((B, int(k)), dtype=torch.float32, device=mo.device)
         indices = torch.empty((B, int(k)), dtype=torch.int32, device=mo.device)
-        ld = mo.stride(0) if B > 1 else max(C, mo.stride(0))
+        ld = _row_matrix("topk_rows", "mo", mo)
         rc = lib.ovmr_topk_rows(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, B, C, int(k), _ptr(values), _ptr(indices),
-                                _ptr(labels), _ptr(hits), ctypes.c_void_p(torch.cuda.current_stream(mo.device).cuda_stream))
+                                _ptr(labels), _ptr(hits), _stream_on(mo.device))
     if rc != 0:
         raise OvmrError(f"ovmr_topk_rows failed with {rc} (B = {B}, C = {C}, k = {k})")
     return values, indices
@@ -258,8 +283,7 @@ def eval_detail(mo: torch.Tensor, labels: torch.Tensor, k: int, counts: torch.Te
     (include/ovmr_hip.h)."""
     _want_rows("eval_detail", "mo", mo)
     B, C = mo.shape
-    if C > 1 and mo.stride(1) != 1 or B > 1 and mo.stride(0) < C:
-        _refuse("eval_detail", "mo", f"rows of unit column stride, at least {C} elements apart", f"strides {tuple(mo.stride())}")
+    ld = _row_matrix("eval_detail", "mo", mo)
     _want("eval_detail", "labels", labels, (B,), torch.int64, mo.device, dense=True)
     if counts is None:
         raise ValueError("eval_detail needs counts")
@@ -270,10 +294,8 @@ def eval_detail(mo: torch.Tensor, labels: torch.Tensor, k: int, counts: torch.Te
                 _refuse("eval_detail", name, f"of {n} elements", f"{list(t.shape)}")
     lib = load_library()
     with torch.cuda.device(mo.device):
-        ld = mo.stride(0) if B > 1 else max(C, mo.stride(0))
         rc = lib.ovmr_eval_detail(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, _ptr(labels), B, C, int(k), _ptr(counts),
-                                  _ptr(hits), _ptr(class_hits), _ptr(cmat),
-                                  ctypes.c_void_p(torch.cuda.current_stream(mo.device).cuda_stream))
+                                  _ptr(hits), _ptr(class_hits), _ptr(cmat), _stream_on(mo.device))
     if rc != 0:
         raise OvmrError(f"ovmr_eval_detail failed with {rc} (B = {B}, C = {C}, k = {k})")
 
@@ -310,8 +332,7 @@ def eval_curves(mo: torch.Tensor, labels: torch.Tensor, lo: float, hi: float, bi
     B, C = mo.shape
     if C < 1:
         _refuse(where, "mo", "of at least one column", f"{list(mo.shape)}")
-    if C > 1 and mo.stride(1) != 1 or B > 1 and mo.stride(0) < C:
-        _refuse(where, "mo", f"rows of unit column stride, at least {C} elements apart", f"strides {tuple(mo.stride())}")
+    ld = _row_matrix(where, "mo", mo)
     _want(where, "labels", labels, (B,), torch.int64, mo.device, dense=True)
     bins = _want_int(where, "bins", bins, 1, MAX_BINS)
     flo, fhi, _ = curve_scale(lo, hi, bins, where)
@@ -320,14 +341,38 @@ def eval_curves(mo: torch.Tensor, labels: torch.Tensor, lo: float, hi: float, bi
     if B == 0:
         return
     with torch.cuda.device(mo.device):
-        ld = mo.stride(0) if B > 1 else max(C, mo.stride(0))
         rc = lib.ovmr_eval_curves(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, _ptr(labels), B, C, float(flo), float(fhi), bins,
-                                  _ptr(state), ctypes.c_void_p(torch.cuda.current_stream(mo.device).cuda_stream))
+                                  _ptr(state), _stream_on(mo.device))
     if rc != 0:
         raise OvmrError(f"ovmr_eval_curves failed with {rc} (B = {B}, C = {C}, lo = {float(flo)!r}, hi = {float(fhi)!r}, bins = {bins})")
 
 
 _nearest_scratch: Dict[torch.device, torch.Tensor] = {}         # per device: the scratch of nearest_rows, grown on demand
+
+
+def _search_scratch(dev, need: int) -> torch.Tensor:
+    """The cached scratch of device dev (the current device, inside the caller's torch.cuda.device), grown to `need` bytes."""
+    key = torch.device(dev.type, torch.cuda.current_device())
+    scratch = _nearest_scratch.get(key)
+    if scratch is None or scratch.numel() * 8 < need:
+        scratch = _nearest_scratch[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+    return scratch
+
+
+def _want_search(where: str, queries, bank, k, out):
+    """The operands nearest_rows and neighbour_rows share: queries [B, D] and bank [R, D], fp16 on one GPU, D a multiple of 64 in
+    [64, 1024], 1 <= k <= min(R, 32), out None or a pair ([B, k] fp32, [B, k] int32) -> (B, D, R, k)."""
+    _want(where, "queries", queries, (None, None), torch.float16, "cuda")
+    _want(where, "bank", bank, (None, None), torch.float16, queries.device)
+    B, D = queries.shape
+    R = bank.shape[0]
+    if bank.shape[1] != D:
+        _refuse(where, "bank", f"of shape [*, {D}] (the queries' width)", f"{list(bank.shape)}")
+    if D % 64 or not 64 <= D <= 1024:
+        _refuse(where, "queries", "of a width that is a multiple of 64 in [64, 1024]", f"{list(queries.shape)}")
+    k = _want_int(where, "k", k, 1, min(R, 32))
+    _want_out_pair(where, out, (B, k), torch.int32, queries.device)
+    return B, D, R, k
 
 
 def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Optional[torch.Tensor] = None, out=None):
@@ -339,34 +384,9 @@ def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Opti
     ranges view is made contiguous.  out: (values, indices) to write into.  The scratch is one cached buffer per device: calls are
     ordered on one stream, like everything that shares a workspace."""
     where = "nearest_rows"
-    _want(where, "queries", queries, (None, None), torch.float16, "cuda")
-    _want(where, "bank", bank, (None, None), torch.float16, queries.device)
-    B, D = queries.shape
-    R = bank.shape[0]
-    if bank.shape[1] != D:
-        _refuse(where, "bank", f"of shape [*, {D}] (the queries' width)", f"{list(bank.shape)}")
-    if D % 64 or not 64 <= D <= 1024:
-        _refuse(where, "queries", "of a width that is a multiple of 64 in [64, 1024]", f"{list(queries.shape)}")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= min(R, 32):
-        _refuse(where, "k", f"an integer in [1, {min(R, 32)}]", repr(k))
-    k = int(k)
+    B, D, R, k = _want_search(where, queries, bank, k, out)
     if ranges is not None:
-        _want(where, "ranges", ranges, (B, 2))
-        if isinstance(ranges, np.ndarray):
-            ranges = torch.from_numpy(ranges)
-        if ranges.is_floating_point() or ranges.is_complex() or ranges.dtype == torch.bool:
-            _refuse(where, "ranges", "of an integer dtype", str(ranges.dtype))
-        if not ranges.is_cuda:
-            _want_range(where, "ranges", ranges, 0, R + 1, "row bounds")
-            if ranges.numel() and bool((ranges[:, 0] > ranges[:, 1]).any()):
-                _refuse(where, "ranges", "pairs lo <= hi", "a pair with lo > hi")
-        elif not _same_device(ranges.device, queries.device):
-            _refuse(where, "ranges", f"on {queries.device} or on the host", f"a tensor on {ranges.device}")
-    if out is not None:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            _refuse(where, "out", "a pair (values, indices)", type(out).__name__)
-        _want(where, "out[0]", out[0], (B, k), torch.float32, queries.device, dense=True)
-        _want(where, "out[1]", out[1], (B, k), torch.int32, queries.device, dense=True)
+        ranges = _want_pairs(where, "ranges", ranges, B, R, queries.device)
     lib = load_library()
     dev = queries.device
     with torch.cuda.device(dev):
@@ -380,12 +400,9 @@ def nearest_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Opti
         need = int(lib.ovmr_nearest_scratch_bytes(B, R, k))
         if need < 0:
             raise OvmrError(f"ovmr_nearest_scratch_bytes refuses B = {B}, R = {R}, k = {k}")
-        key = torch.device(dev.type, torch.cuda.current_device())
-        scratch = _nearest_scratch.get(key)
-        if scratch is None or scratch.numel() * 8 < need:
-            scratch = _nearest_scratch[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+        scratch = _search_scratch(dev, need)
         rc = lib.ovmr_nearest_rows(_ptr(queries), B, _ptr(bank), R, D, k, _ptr(ranges), _ptr(values), _ptr(indices), _ptr(scratch),
-                                   scratch.numel() * 8, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                   scratch.numel() * 8, _stream_on(dev))
     if rc != 0:
         raise OvmrError(f"ovmr_nearest_rows failed with {rc} (B = {B}, R = {R}, D = {D}, k = {k})")
     return values, indices
@@ -395,8 +412,9 @@ MAX_RANGE = 4096                                                  # ovmr_neighbo
 
 
 def _want_pairs(where: str, name: str, t, B: int, R: int, dev):
-    """ranges / exclude of neighbour_rows: [B, 2] of an integer dtype; host values are checked (0 <= lo <= hi <= R), device values are the
-    caller's contract (the kernels clamp what they read).  Returns the tensor (a numpy array as a tensor)."""
+    """ranges of nearest_rows, ranges / exclude of neighbour_rows: [B, 2] of an integer dtype; host values are checked
+    (0 <= lo <= hi <= R), device values are the caller's contract (the kernels clamp what they read).  Returns the tensor (a numpy array
+    as a tensor)."""
     _want(where, name, t, (B, 2))
     if isinstance(t, np.ndarray):
         t = torch.from_numpy(t)
@@ -419,20 +437,8 @@ def neighbour_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Op
     tiled launch pair; 1 .. 4096: a promise that no range is longer, which takes the one-wave-per-query launch (ranges required; host
     ranges are held to the promise, device ranges are truncated to it by the kernel).  The scratch is nearest_rows' cached buffer."""
     where = "neighbour_rows"
-    _want(where, "queries", queries, (None, None), torch.float16, "cuda")
-    _want(where, "bank", bank, (None, None), torch.float16, queries.device)
-    B, D = queries.shape
-    R = bank.shape[0]
-    if bank.shape[1] != D:
-        _refuse(where, "bank", f"of shape [*, {D}] (the queries' width)", f"{list(bank.shape)}")
-    if D % 64 or not 64 <= D <= 1024:
-        _refuse(where, "queries", "of a width that is a multiple of 64 in [64, 1024]", f"{list(queries.shape)}")
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= min(R, 32):
-        _refuse(where, "k", f"an integer in [1, {min(R, 32)}]", repr(k))
-    k = int(k)
-    if isinstance(max_range, bool) or not isinstance(max_range, (int, np.integer)) or not 0 <= int(max_range) <= MAX_RANGE:
-        _refuse(where, "max_range", f"an integer in [0, {MAX_RANGE}]", repr(max_range))
-    max_range = int(max_range)
+    B, D, R, k = _want_search(where, queries, bank, k, out)
+    max_range = _want_int(where, "max_range", max_range, 0, MAX_RANGE)
     if max_range > 0 and ranges is None:
         _refuse(where, "ranges", f"given where max_range = {max_range} promises their length", "None")
     if ranges is not None:
@@ -441,11 +447,6 @@ def neighbour_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Op
             _refuse(where, "ranges", f"pairs with hi - lo <= max_range = {max_range}", f"a range of {int((ranges[:, 1] - ranges[:, 0]).max())} rows")
     if exclude is not None:
         exclude = _want_pairs(where, "exclude", exclude, B, R, queries.device)
-    if out is not None:
-        if not isinstance(out, (tuple, list)) or len(out) != 2:
-            _refuse(where, "out", "a pair (values, indices)", type(out).__name__)
-        _want(where, "out[0]", out[0], (B, k), torch.float32, queries.device, dense=True)
-        _want(where, "out[1]", out[1], (B, k), torch.int32, queries.device, dense=True)
     lib = load_library()
     dev = queries.device
     with torch.cuda.device(dev):
@@ -461,15 +462,9 @@ def neighbour_rows(queries: torch.Tensor, bank: torch.Tensor, k: int, ranges: Op
         need = int(lib.ovmr_neighbours_scratch_bytes(B, R, k, max_range))
         if need < 0:
             raise OvmrError(f"ovmr_neighbours_scratch_bytes refuses B = {B}, R = {R}, k = {k}, max_range = {max_range}")
-        scratch = None
-        if need:
-            key = torch.device(dev.type, torch.cuda.current_device())
-            scratch = _nearest_scratch.get(key)
-            if scratch is None or scratch.numel() * 8 < need:
-                scratch = _nearest_scratch[key] = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=dev)
+        scratch = _search_scratch(dev, need) if need else None
         rc = lib.ovmr_neighbours_rows(_ptr(queries), B, _ptr(bank), R, D, k, _ptr(ranges), _ptr(exclude), max_range, _ptr(values),
-                                      _ptr(indices), _ptr(scratch), 0 if scratch is None else scratch.numel() * 8,
-                                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+                                      _ptr(indices), _ptr(scratch), 0 if scratch is None else scratch.numel() * 8, _stream_on(dev))
     if rc != 0:
         raise OvmrError(f"ovmr_neighbours_rows failed with {rc} (B = {B}, R = {R}, D = {D}, k = {k}, max_range = {max_range})")
     return values, indices
@@ -499,13 +494,10 @@ class ColumnTopM:
         self.device = torch.device(device)
         self.state = torch.zeros((self.C, self.m), dtype=torch.int64, device=self.device)
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def reset(self):
         """Empties every list (ovmr_retrieve_reset)."""
         with torch.cuda.device(self.device):
-            rc = load_library().ovmr_retrieve_reset(_ptr(self.state), self.C, self.m, self._stream())
+            rc = load_library().ovmr_retrieve_reset(_ptr(self.state), self.C, self.m, _stream_on(self.device))
         if rc != 0:
             raise OvmrError(f"ovmr_retrieve_reset failed with {rc} (C = {self.C}, m = {self.m})")
         return self
@@ -518,8 +510,7 @@ class ColumnTopM:
         _want_rows(where, "out", out)
         _want(where, "out", out, (None, self.C), device=self.device)
         B, C = out.shape
-        if C > 1 and out.stride(1) != 1 or B > 1 and out.stride(0) < C:
-            _refuse(where, "out", f"rows of unit column stride, at least {C} elements apart", f"strides {tuple(out.stride())}")
+        ld = _row_matrix(where, "out", out)
         base = _want_int(where, "base", base, 0, MAX_POOL - B)
         if floor is not None:
             _want(where, "floor", floor, (B,), torch.float32, self.device, dense=True)
@@ -527,9 +518,8 @@ class ColumnTopM:
             return self
         lib = load_library()
         with torch.cuda.device(self.device):
-            ld = out.stride(0) if B > 1 else max(C, out.stride(0))
             rc = lib.ovmr_retrieve_update(_ptr(out), F32 if out.dtype == torch.float32 else F16, ld, B, C, self.m, base, _ptr(floor),
-                                          _ptr(self.state), self._stream())
+                                          _ptr(self.state), _stream_on(self.device))
         if rc != 0:
             raise OvmrError(f"ovmr_retrieve_update failed with {rc} (B = {B}, C = {C}, m = {self.m}, base = {base})")
         return self
@@ -544,7 +534,7 @@ class ColumnTopM:
         if other.data_ptr() == self.state.data_ptr():
             _refuse(where, "other", "the state of ANOTHER stream (disjoint images)", "this object's own state")
         with torch.cuda.device(self.device):
-            rc = load_library().ovmr_retrieve_merge(_ptr(self.state), _ptr(other), self.C, self.m, self._stream())
+            rc = load_library().ovmr_retrieve_merge(_ptr(self.state), _ptr(other), self.C, self.m, _stream_on(self.device))
         if rc != 0:
             raise OvmrError(f"ovmr_retrieve_merge failed with {rc} (C = {self.C}, m = {self.m})")
         return self
@@ -553,16 +543,12 @@ class ColumnTopM:
         """(values fp32 [C, m], indices int64 [C, m]) on the device, best first; an unfilled rank is index -1, value -inf.  The state
         stays as it is.  out: (values, indices) to write into."""
         where = "ColumnTopM.finish"
-        if out is not None:
-            if not isinstance(out, (tuple, list)) or len(out) != 2:
-                _refuse(where, "out", "a pair (values, indices)", type(out).__name__)
-            _want(where, "out[0]", out[0], (self.C, self.m), torch.float32, self.device, dense=True)
-            _want(where, "out[1]", out[1], (self.C, self.m), torch.int64, self.device, dense=True)
+        _want_out_pair(where, out, (self.C, self.m), torch.int64, self.device)
         lib = load_library()
         with torch.cuda.device(self.device):
             values, indices = out if out is not None else (torch.empty((self.C, self.m), dtype=torch.float32, device=self.device),
                                                             torch.empty((self.C, self.m), dtype=torch.int64, device=self.device))
-            rc = lib.ovmr_retrieve_finish(_ptr(self.state), self.C, self.m, _ptr(values), _ptr(indices), self._stream())
+            rc = lib.ovmr_retrieve_finish(_ptr(self.state), self.C, self.m, _ptr(values), _ptr(indices), _stream_on(self.device))
         if rc != 0:
             raise OvmrError(f"ovmr_retrieve_finish failed with {rc} (C = {self.C}, m = {self.m})")
         return values, indices
