@@ -96,6 +96,7 @@ import argparse
 import os
 import os.path as osp
 import sys
+from types import SimpleNamespace
 from typing import Dict, List, Sequence, Tuple
 
 import numpy as np            # (torch is imported inside the functions: under `python -m ovmr_amd.cli` the spawned decode workers
@@ -160,18 +161,13 @@ class FolderLoader:
         self.bs, self.size = batch_size, size
         self.tfm = dict(interpolation=interpolation, mean=mean, std=std)
         self.presharded = world > 1
-        self.shots = None
-        if ragged:
-            from .shard import vocabulary_shots
-            self.shots = vocabulary_shots(items, num_classes)
+        from .shard import keep_batch_shard, ragged_batches, shard_range, vocabulary_shots
+        self.shots = vocabulary_shots(items, num_classes) if ragged else None
         if world > 1:
-            from .shard import shard_range
             lo, hi = shard_range(num_classes or (1 + max(l for _, l in items)), rank, world)
             items = [it for it in items if lo <= it[1] < hi]
-        from .shard import keep_batch_shard
         self.items, self.batch_shard, self.batch_range = keep_batch_shard(list(items), int(batch_size), batch_shard, ragged)
         if ragged:
-            from .shard import ragged_batches
             self.spans = ragged_batches(self.items, self.bs)
         else:
             self.spans = [(s, min(s + self.bs, len(self.items)), None) for s in range(0, len(self.items), self.bs)]
@@ -494,8 +490,8 @@ def write_bank_audit(out_dir: str, tables) -> None:
         _write_csv(osp.join(out_dir, name), cols, lines, floats)
 
 
-def check_audit(args, trainer_name: str, zeroshot: bool):
-    """The refusals of `--audit-bank [K]` / `--dup-threshold T`, before anything is listed or loaded."""
+def check_audit(args, trainer_name: str, zeroshot: bool, world=None):
+    """The refusals of `--audit-bank [K]` / `--dup-threshold T`, before anything is listed or loaded (world: WORLD_SIZE, if the caller read it)."""
     if args.audit_bank is None:
         if args.dup_threshold is not None:
             raise SystemExit("--dup-threshold T belongs to --audit-bank [K]: the similarity from which a neighbour counts as a duplicate")
@@ -508,7 +504,7 @@ def check_audit(args, trainer_name: str, zeroshot: bool):
         raise SystemExit(f"--audit-bank {args.audit_bank}: K must lie in [1, {MAX_NEAREST}]")
     if args.dup_threshold is not None and args.dup_threshold != args.dup_threshold:
         raise SystemExit("--dup-threshold nan: T must be a number")
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if (int(os.environ.get("WORLD_SIZE", "1")) if world is None else world) > 1:
         raise SystemExit("--audit-bank runs in one process: a sharded rank holds only its own classes' exemplar features")
 
 
@@ -738,10 +734,7 @@ def _init_process_group(args) -> bool:
         # minutes would abort the waiting ranks, and the launcher then the others)
         import datetime
         to = datetime.timedelta(seconds=float(os.environ.get("OVMR_DIST_TIMEOUT", 6 * 3600)))
-        if backend == "nccl":
-            dist.init_process_group("nccl", device_id=torch.device(args.device), timeout=to)
-        else:
-            dist.init_process_group(backend, timeout=to)
+        dist.init_process_group(backend, timeout=to, **({"device_id": torch.device(args.device)} if backend == "nccl" else {}))
         own_group = True
     return own_group
 
@@ -750,12 +743,11 @@ def _loader_factory(args, cfg, size: int, tfm: dict):
     """loader(items, batch, rank, world, n_classes, ragged=, batch_shard=): the pipelined loader, or with no decode workers the in-thread
     FolderLoader."""
     workers = cfg.DATALOADER.NUM_WORKERS if args.workers is None else args.workers
-    if workers <= 0:
-        return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False, batch_shard=None: FolderLoader(
-            items, batch, size, rank, world, n_classes, ragged=ragged, batch_shard=batch_shard, **tfm)
-    from .loader import PipelinedFolderLoader
-    kw = dict(workers=workers, prefetch=args.prefetch, device=args.device, fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
-    return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False, batch_shard=None: PipelinedFolderLoader(
+    cls, kw = FolderLoader, tfm
+    if workers > 0:
+        from .loader import PipelinedFolderLoader as cls
+        kw = dict(workers=workers, prefetch=args.prefetch, device=args.device, fast_decode=args.fast_decode, device_resize=not args.host_resize, **tfm)
+    return lambda items, batch, rank=0, world=1, n_classes=0, ragged=False, batch_shard=None: cls(
         items, batch, size, rank, world, n_classes, ragged=ragged, batch_shard=batch_shard, **kw)
 
 
@@ -768,29 +760,26 @@ def _report_pipeline(results: dict, name: str, loader) -> None:
         results[f"pipeline_{name.split()[0]}"] = st
 
 
-def main(argv=None) -> Dict[str, float]:
-    """train.py:183-255 on the evaluation path: build_trainer(cfg) and test().  MM_CLS_OP generates the classifiers from the exemplar set,
-    writes mm_classifiers.pt / visual_tokens.pt and evaluates the test set; the zero-shot trainers take the classes and test items of the
-    same job (build_splits; no exemplar is decoded) and the text classifier from DATASET.NAME's template(s), and write no model file.
-    The result block and acc_per_class.csv / f1_per_class.csv land in OUTPUT_DIR; --per-class-result adds the per-class block and
-    results["perclass_accuracy"], --confusion-matrix adds OUTPUT_DIR/cmat.pt, --score-curves adds two result lines, results["mAP"] /
-    ["mean_auroc"], curves_per_class.csv and score_hist.pt."""
-    from . import config, templates
-    args = parse(argv)
-    cfg = config.setup_cfg(args)                              # train.py:134-155
-    zeroshot = cfg.TRAINER.NAME in templates.ZEROSHOT_TRAINERS
-    if not (zeroshot or cfg.TRAINER.NAME == "MM_CLS_OP") or not args.eval_only:
+def plan_job(args, cfg):
+    """Stage 1, before torch is imported: every refusal that needs neither a process group, a bank's contents nor the data set, in the
+    order a user meets them, then what the job is, as one record for the stages (the fields: the SimpleNamespace below).  mode "audit" is
+    the bank's audit and nothing else; lift_shots: no exemplar of the data set is decoded, so its class list (the label set of the few-shot
+    draw) is drawn with NUM_SHOTS >= 1 whatever the configuration says; skip: the job would write mm_classifiers.pt where one exists."""
+    from . import templates
+    name = cfg.TRAINER.NAME
+    zeroshot = name in templates.ZEROSHOT_TRAINERS
+    if not (zeroshot or name == "MM_CLS_OP") or not args.eval_only:
         raise SystemExit("only `--eval-only --trainer MM_CLS_OP` (classifier generation / evaluation) and `--eval-only --trainer "
                          "ZeroshotCLIP | ZeroshotCLIP2` (zero-shot evaluation) are on the hot path")
-    shots, batch, seed = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE, cfg.SEED
-    split_cfg = cfg
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    shots, batch = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE
     edits = bool(args.add_classes or args.replace_classes or args.remove_classes)
     if edits and not args.bank:
         raise SystemExit("--add-classes / --replace-classes / --remove-classes edit a reference bank: give --bank FILE")
     if zeroshot and (args.bank or args.save_bank):
-        raise SystemExit(f"--bank / --save-bank: --trainer {cfg.TRAINER.NAME} has no generated vocabulary to bank (MM_CLS_OP only; a zero-shot "
+        raise SystemExit(f"--bank / --save-bank: --trainer {name} has no generated vocabulary to bank (MM_CLS_OP only; a zero-shot "
                          "vocabulary is a text call away)")
-    if (args.bank or args.save_bank) and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if (args.bank or args.save_bank) and world > 1:
         raise SystemExit("--bank / --save-bank run in one process: a sharded rank holds only its own classes' exemplar features")
     if args.bank and args.save_bank:
         raise SystemExit("--save-bank belongs to a generation job: a --bank run writes OUTPUT_DIR/reference_bank.pt whenever it edits")
@@ -798,58 +787,52 @@ def main(argv=None) -> Dict[str, float]:
         raise SystemExit("--bank holds the classifiers already: not together with --classifiers")
     if args.bank and not osp.isfile(args.bank):
         raise SystemExit(f"--bank {args.bank!r}: no such file")
-    predict, images, k = args.predict is not None, [], None
-    retrieve = args.retrieve is not None
-    check_retrieve(args, cfg.TRAINER.NAME, zeroshot, cfg.EVAL_MODE)
+    predict, retrieve = args.predict is not None, args.retrieve is not None
+    check_retrieve(args, name, zeroshot, cfg.EVAL_MODE)
     pool = predict or retrieve                                # unlabelled images instead of the labelled test split
-    curve_bins, curve_range = check_score_curves(args, cfg.TRAINER.NAME, zeroshot)
-    check_nearest(args, cfg.TRAINER.NAME, zeroshot)
-    check_audit(args, cfg.TRAINER.NAME, zeroshot)
-    audit_only = args.audit_bank is not None and bool(args.bank) and not edits and not pool      # the bank alone: no data set, no test pass
-    if predict and cfg.EVAL_MODE == "all" and not zeroshot:
-        raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
+    curve_bins, curve_range = check_score_curves(args, name, zeroshot)
+    check_nearest(args, name, zeroshot)
+    check_audit(args, name, zeroshot, world)
+    images, k, m = [], None, (MAX_PER_CLASS if args.per_class is None else args.per_class) if retrieve else None
     if predict:
+        if cfg.EVAL_MODE == "all" and not zeroshot:
+            raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
         for flag, on in (("--per-class-result", args.per_class_result), ("--confusion-matrix", args.confusion_matrix)):
             if on:
                 raise SystemExit(f"{flag} belongs to the test pass: --predict ranks unlabelled images, there is nothing to count")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        if world > 1:
             raise SystemExit(PREDICT_ONE_PROCESS)
         k = 5 if args.topk is None else args.topk
         if not 1 <= k <= MAX_TOPK:
             raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, number of classes)]")
+    if pool:
         if args.classifiers and zeroshot:
-            raise SystemExit(f"--classifiers {args.classifiers!r}: --trainer {cfg.TRAINER.NAME} has no generated classifiers to load (MM_CLS_OP only)")
+            raise SystemExit(f"--classifiers {args.classifiers!r}: --trainer {name} has no generated classifiers to load (MM_CLS_OP only)")
         if args.classifiers and not osp.isfile(args.classifiers):
             raise SystemExit(f"--classifiers {args.classifiers!r}: no such file")
-        images = list_predict_images(args.predict)
-    elif retrieve:
-        if args.classifiers and zeroshot:
-            raise SystemExit(f"--classifiers {args.classifiers!r}: --trainer {cfg.TRAINER.NAME} has no generated classifiers to load (MM_CLS_OP only)")
-        if args.classifiers and not osp.isfile(args.classifiers):
-            raise SystemExit(f"--classifiers {args.classifiers!r}: no such file")
-        images = list_predict_images(args.retrieve, "--retrieve")
-        check_pool_size(len(images), args.retrieve)
+        images = list_predict_images(args.predict, "--predict") if predict else list_predict_images(args.retrieve, "--retrieve")
+        if retrieve:
+            check_pool_size(len(images), args.retrieve)
     elif args.topk is not None or args.classifiers:
         raise SystemExit("--topk / --classifiers belong to --predict PATH (the test pass takes TEST.TOPK)")
-    load_classifiers = pool and bool(args.classifiers)
-    from_bank = bool(args.bank)
-    if from_bank and edits and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
-        print(f"Oops! The results exist at {cfg.OUTPUT_DIR} (so skip this job)")           # generate_classifier.sh:27-28
-        return {}
-    if zeroshot or load_classifiers or from_bank:
-        import copy
-        split_cfg = copy.deepcopy(cfg)
-        split_cfg.DATASET.NUM_SHOTS = max(1, shots)       # the class list is the label set of the few-shot draw (any NUM_SHOTS >= 1 yields the same set)
+    vocabulary = "zeroshot" if zeroshot else "classifiers" if args.classifiers else "bank" if args.bank else "generate"
+    audit_only = args.audit_bank is not None and vocabulary == "bank" and not edits and not pool      # the bank alone: no data set, no test pass
+    p = SimpleNamespace(args=args, cfg=cfg, zeroshot=zeroshot, world=world, vocabulary=vocabulary, edits=edits, images=images,
+                        mode="audit" if audit_only else "predict" if predict else "retrieve" if retrieve else "test",
+                        k=k, m=m, within_top=args.within_top, nearest=args.nearest, audit=args.audit_bank,
+                        dup_threshold=0.995 if args.dup_threshold is None else args.dup_threshold, curve_bins=curve_bins, curve_range=curve_range,
+                        ragged=bool(args.ragged_shots) and vocabulary in ("generate", "bank"), lift_shots=vocabulary != "generate", skip=False)
+    decodes = vocabulary == "generate" or edits               # exemplars are decoded and mm_classifiers.pt is written
+    if decodes and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
+        p.skip = True
+        return p
     if zeroshot:
         try:
             templates.check_dataset(cfg.DATASET.NAME)
         except KeyError as e:
             raise SystemExit(e.args[0]) from None
         # (nothing of the few-shot draw is decoded)
-    elif not load_classifiers and not (from_bank and not edits):
-        if not from_bank and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
-            print(f"Oops! The results exist at {cfg.OUTPUT_DIR} (so skip this job)")       # generate_classifier.sh:27-28
-            return {}
+    elif decodes:
         if shots < 1:
             raise SystemExit("DATASET.NUM_SHOTS must be >= 1: the eval-set loader draws NUM_SHOTS rows per class (data_manager.py:157-170)")
         if batch < shots:
@@ -857,46 +840,60 @@ def main(argv=None) -> Dict[str, float]:
                              f"(RandomClassSampler needs one class per batch), raise TEST.BATCH_SIZE to at least {shots}")
         if cfg.DATALOADER.K_TRANSFORMS != 1:
             raise SystemExit("DATALOADER.K_TRANSFORMS > 1 only applies to training transforms; the test transform has one view")
+    return p
 
+
+def _open_job(p):
+    """Stage 2: the process group, the seed, the bank and the edits it is asked for, the splits -> the job's state (rank, world,
+    own_group, bank, edit_plan, classnames, exemplars, test_items).  The refusals that need one of these stand here."""
     import torch
     import torch.distributed as dist
-    from types import SimpleNamespace
-    from . import checkpoint, modules, trainer
-    from .tokenizer import BPETokenizer
+    args, cfg, pool = p.args, p.cfg, p.mode in ("predict", "retrieve")
     own_group = _init_process_group(args)
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
-    if predict and world > 1:                                 # (a group the caller opened: WORLD_SIZE > 1 was refused above)
+    if p.mode == "predict" and world > 1:                     # (a group the caller opened: WORLD_SIZE > 1 was refused by the plan)
         raise SystemExit(PREDICT_ONE_PROCESS)
-    if seed >= 0:
-        print(f"Setting fixed seed: {seed}")                  # train.py:157-159
-        torch.manual_seed(seed)
-    ragged = bool(args.ragged_shots) and not zeroshot and not load_classifiers
-    bank_obj = plan = None
-    if from_bank:
+    if cfg.SEED >= 0:
+        print(f"Setting fixed seed: {cfg.SEED}")              # train.py:157-159
+        torch.manual_seed(cfg.SEED)
+    split_cfg = cfg
+    if p.lift_shots:
+        import copy
+        split_cfg = copy.deepcopy(cfg)
+        split_cfg.DATASET.NUM_SHOTS = max(1, cfg.DATASET.NUM_SHOTS)          # (any NUM_SHOTS >= 1 yields the same label set)
+    bank_obj = edit_plan = None
+    if p.vocabulary == "bank":
         from . import bank as bank_format
         try:
-            bank_obj = bank_format.read(args.bank)            # (checked against the model by load_bank below)
+            bank_obj = bank_format.read(args.bank)            # (checked against the model by load_bank)
         except ValueError as e:
             raise SystemExit(str(e)) from None
         if bank_obj["classnames"] is None:
             raise SystemExit(f"--bank {args.bank!r}: the bank holds no class names (it was written by a model built from token rows)")
-        plan = plan_vocabulary_edits(args, bank_obj["classnames"], shots, seed, ragged)
-        classnames, exemplars, test_items = plan[3], [], []
-        if not pool and not audit_only:                       # the data set the test pass runs on must speak of the same classes
+        edit_plan = plan_vocabulary_edits(args, bank_obj["classnames"], cfg.DATASET.NUM_SHOTS, cfg.SEED, p.ragged)
+        classnames, exemplars, test_items = edit_plan[3], [], []
+        if p.mode == "test":                                  # the data set the test pass runs on must speak of the same classes
             set_names, _, test_items = build_splits(split_cfg, args.eval_split, args.test_split, "", False)
             diff = bank_format.first_difference(classnames, set_names)
             if diff is not None:
-                raise SystemExit(f"--bank {args.bank!r}: its class names" + (" (after the edits)" if edits else "") + f" are not the data set's: {diff}")
+                raise SystemExit(f"--bank {args.bank!r}: its class names" + (" (after the edits)" if p.edits else "") + f" are not the data set's: {diff}")
     else:
-        classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if pool else args.test_split, args.exemplar_list, ragged)
-    if predict:
-        if k > len(classnames):
-            raise SystemExit(f"--topk {k}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
-    if retrieve and args.within_top is not None and args.within_top > len(classnames):
-        raise SystemExit(f"--within-top {args.within_top}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
+        classnames, exemplars, test_items = build_splits(split_cfg, args.eval_split, None if pool else args.test_split, args.exemplar_list, p.ragged)
+    for flag, v in (("--topk", p.k), ("--within-top", p.within_top)):           # (each is None without its mode)
+        if v is not None and v > len(classnames):
+            raise SystemExit(f"{flag} {v}: K must lie in [1, min({MAX_TOPK}, {len(classnames)} classes)]")
     if pool:
-        test_items = [(p, 0) for p in images]             # the loader protocol carries a label: a dummy one, never read
+        test_items = [(path, 0) for path in p.images]         # the loader protocol carries a label: a dummy one, never read
+    return SimpleNamespace(own_group=own_group, rank=rank, world=world, bank=bank_obj, edit_plan=edit_plan, classnames=classnames,
+                           exemplars=exemplars, test_items=test_items, audit_tables=None)
 
+
+def _build_trainer(p, run):
+    """Stage 3: the CLIP weights, the loaders (run.eval_loader or None, run.edit_loaders, run.test_loader) and the trainer (run.tr)."""
+    from . import checkpoint, modules, trainer
+    from .tokenizer import BPETokenizer
+    args, cfg, classnames, rank, world = p.args, p.cfg, run.classnames, run.rank, run.world
+    shots, batch, ragged = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE, p.ragged
     # what the loaders need to know of the model is in the weights' shapes: the decode workers start before the engine exists
     clip_sd = checkpoint.load_clip_state_dict(args.clip_weights)
     spec = modules.infer_spec(clip_sd)
@@ -905,7 +902,7 @@ def main(argv=None) -> Dict[str, float]:
     tfm = dict(interpolation=cfg.INPUT.INTERPOLATION, mean=tuple(cfg.INPUT.PIXEL_MEAN) if normalize else None,
                std=tuple(cfg.INPUT.PIXEL_STD) if normalize else None)
     kw = {}
-    if not zeroshot:
+    if not p.zeroshot:
         pl_state = None
         if cfg.MODEL.INIT_WEIGHTS:                            # load_pretrained_weights (trainers/mm_classifier_one_prompt.py:403-404)
             ck = checkpoint._torch_load(cfg.MODEL.INIT_WEIGHTS)
@@ -916,26 +913,23 @@ def main(argv=None) -> Dict[str, float]:
             print("Note that load_model() is skipped as no pretrained model is given")       # :464-466
         kw["prompt_learner_state"] = pl_state
     loader = _loader_factory(args, cfg, spec.image_resolution, tfm)
-    edit_loaders = {}
-    if zeroshot or load_classifiers or from_bank:
-        eval_loader = None
-        for key, part in (("replace", plan[1]), ("add", plan[2])) if from_bank else ():
-            if part is not None:                              # the loaders of the edited classes only: nothing of an old class is listed
-                try:
-                    edit_loaders[key] = loader(part[1], batch if ragged else batch // shots * shots, 0, 1, len(part[0]), ragged=ragged)
-                except ValueError as e:
-                    raise SystemExit(str(e)) from None
-    elif ragged:
+    eval_loader, edit_loaders = None, {}
+    if p.vocabulary == "generate" and not ragged:
+        eval_loader = loader(run.exemplars, batch // shots * shots, rank, world, len(classnames))
+    else:                                                     # (zero-shot, --classifiers: no exemplar loader at all)
         try:
-            eval_loader = loader(exemplars, batch, rank, world, len(classnames), ragged=True)
+            if p.vocabulary == "generate":
+                eval_loader = loader(run.exemplars, batch, rank, world, len(classnames), ragged=True)
+            for key, part in (("replace", run.edit_plan[1]), ("add", run.edit_plan[2])) if p.vocabulary == "bank" else ():
+                if part is not None:                          # the loaders of the edited classes only: nothing of an old class is listed
+                    edit_loaders[key] = loader(part[1], batch if ragged else batch // shots * shots, 0, 1, len(part[0]), ragged=ragged)
         except ValueError as e:
             raise SystemExit(str(e)) from None
-        n = np.sort(eval_loader.shots.numpy())
-        print(f"ragged exemplar set: {int(n.sum()):,} images of {len(n):,} classes, shots per class min {int(n[0])} / median {float(np.median(n)):g} / max {int(n[-1])}")
-    else:
-        eval_loader = loader(exemplars, batch // shots * shots, rank, world, len(classnames))
+        if eval_loader is not None:
+            n = np.sort(eval_loader.shots.numpy())
+            print(f"ragged exemplar set: {int(n.sum()):,} images of {len(n):,} classes, shots per class min {int(n[0])} / median {float(np.median(n)):g} / max {int(n[-1])}")
     # the test pass is sharded by batches: every rank evaluates its contiguous range of the one-process pass's batches (shard.shard_test_batches)
-    test_loader = loader(test_items, batch, batch_shard=(rank, world) if world > 1 else None)
+    test_loader = loader(run.test_items, batch, batch_shard=(rank, world) if world > 1 else None)
     # the decode workers start while the engine takes the weights; one ring, sized for the larger batch, serves both loaders of a rank
     # (a rank whose share of the test batches is empty decodes exemplars alone: its ring is sized for those)
     first = eval_loader if eval_loader is not None and (len(test_loader) == 0 or eval_loader.bs > test_loader.bs) else test_loader
@@ -945,106 +939,131 @@ def main(argv=None) -> Dict[str, float]:
     if hasattr(first, "warm"):
         first.warm()
     dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
-    tr = trainer.build_trainer(cfg, dm, clip_weights=clip_sd, tokenizer=BPETokenizer(args.bpe_path), device=args.device,
-                               reserve=(batch, 256, max(1024, len(classnames))), per_class_result=args.per_class_result,
-                               compute_cmat=args.confusion_matrix, score_curves=curve_bins, score_range=curve_range, **kw)
-    if load_classifiers:
-        tr.model.load_classifiers(args.classifiers)
-    elif from_bank:
+    run.tr = trainer.build_trainer(cfg, dm, clip_weights=clip_sd, tokenizer=BPETokenizer(args.bpe_path), device=args.device,
+                                   reserve=(batch, 256, max(1024, len(classnames))), per_class_result=args.per_class_result,
+                                   compute_cmat=args.confusion_matrix, score_curves=p.curve_bins, score_range=p.curve_range, **kw)
+    run.eval_loader, run.edit_loaders, run.test_loader = eval_loader, edit_loaders, test_loader
+
+
+def _install_vocabulary(p, run):
+    """Stage 4: the model's classifiers -- loaded from --classifiers, taken from --bank and edited (and then saved), or generated from the
+    exemplar set (and banked under --save-bank).  A zero-shot model has its text classifier already."""
+    from .bank import BANK_FILE
+    args, cfg, model = p.args, p.cfg, run.tr.model
+    if p.vocabulary == "classifiers":
+        model.load_classifiers(args.classifiers)
+    elif p.vocabulary == "bank":
         # (the trainer and its evaluator were built for the FINAL class names; the bank replaces the model's class list, the edits lead to it)
         try:
-            tr.model.load_bank(args.bank, bank_obj)
+            model.load_bank(args.bank, run.bank)
         except ValueError as e:
             raise SystemExit(str(e)) from None
-        remove, replace, add, _ = plan
+        remove, replace, add, _ = run.edit_plan
         if remove:
-            tr.model.remove_classes(remove)
+            model.remove_classes(remove)
         if replace is not None:
-            tr.model.replace_classes(list(replace[0]), edit_loaders["replace"], exemplar_paths=_paths_per_class(replace[1], len(replace[0])))
+            model.replace_classes(list(replace[0]), run.edit_loaders["replace"], exemplar_paths=_paths_per_class(replace[1], len(replace[0])))
         if add is not None:
-            tr.model.add_classes(list(add[0]), edit_loaders["add"], exemplar_paths=_paths_per_class(add[1], len(add[0])))
-        assert tr.model.classnames == classnames
-        if edits:
-            tr.model.save_classifiers()
-            tr.model.save_bank(osp.join(cfg.OUTPUT_DIR, bank_format.BANK_FILE))
-    elif not zeroshot:
+            model.add_classes(list(add[0]), run.edit_loaders["add"], exemplar_paths=_paths_per_class(add[1], len(add[0])))
+        assert model.classnames == run.classnames
+        if p.edits:
+            model.save_classifiers()
+            model.save_bank(osp.join(cfg.OUTPUT_DIR, BANK_FILE))
+    elif p.vocabulary == "generate":
         # the reference does this inside the first forward (:341-342); up front it keeps the two loaders' statistics apart.  Rank 0's two
         # files are written by a worker thread while the test set runs (CustomCLIP._write_files), joined at the end of test().  The
         # classifiers are complete on every rank: each goes on to its own batches of the test set
-        tr.model.forward_prompt(eval_loader, wait_files=False)
+        model.forward_prompt(run.eval_loader, wait_files=False)
         if args.save_bank:
-            from . import bank as bank_format
-            tr.model.save_bank(osp.join(cfg.OUTPUT_DIR, bank_format.BANK_FILE), exemplar_paths=_label_order_paths(exemplars))
-    audit_tables = None
-    if args.audit_bank is not None:
-        m = tr.model
+            model.save_bank(osp.join(cfg.OUTPUT_DIR, BANK_FILE), exemplar_paths=_label_order_paths(run.exemplars))
+
+
+def _run_mode(p, run) -> dict:
+    """Stage 5: under --audit-bank the three tables of the state the vocabulary was left in (kept as run.audit_tables), then the mode's pass
+    and its files -> the results (the audit alone has none)."""
+    images, classnames, out_dir = p.images, run.classnames, p.cfg.OUTPUT_DIR
+    bank_rows = lambda: run.tr.model.exemplar_rows(_label_order_paths(run.exemplars))      # the bank's own paths (after the edits), or this run's
+    if p.audit is not None:
         try:
-            audit = m.audit_bank(args.audit_bank, dup_threshold=0.995 if args.dup_threshold is None else args.dup_threshold)
+            audit = run.tr.model.audit_bank(p.audit, dup_threshold=p.dup_threshold)
         except ValueError as e:
             raise SystemExit(str(e)) from None
-        n_rows = m._exemplar_bank()[0].shape[0]
-        per_class = m._exemplar_paths
-        bank_paths = [p for ps in per_class for p in ps] if per_class is not None else (_label_order_paths(exemplars) if exemplars else None)
-        if bank_paths is not None and len(bank_paths) != n_rows:
-            bank_paths = None                                 # (no path per row: the column stays empty)
-        starts, _ = m._bank_starts_host()
-        audit_tables = bank_audit_tables(audit, classnames, [b - a for a, b in zip(starts, starts[1:])], bank_paths)
-        write_bank_audit(cfg.OUTPUT_DIR, audit_tables)
-        suspects, dups = sum(r[10] for r in audit_tables[0]), sum(r[11] >= 0 for r in audit_tables[0])
-        print(f"=> bank audit: {len(audit_tables[0]):,} exemplars, {suspects:,} suspects in {sum(c[3] > 0 for c in audit_tables[2]):,} classes, "
+        run.audit_tables = tables = bank_audit_tables(audit, classnames, *bank_rows())
+        write_bank_audit(out_dir, tables)
+        suspects, dups = sum(r[10] for r in tables[0]), sum(r[11] >= 0 for r in tables[0])
+        print(f"=> bank audit: {len(tables[0]):,} exemplars, {suspects:,} suspects in {sum(c[3] > 0 for c in tables[2]):,} classes, "
               f"{dups:,} duplicates")
-        print(f"=> {', '.join(osp.join(cfg.OUTPUT_DIR, n) for n in AUDIT_FILES)}")
-    if audit_only:
-        results = {}
-    elif predict:
-        if args.nearest is not None:
-            values, indices, sims, rows = tr.predict_explained(test_loader, k, args.nearest)
-        else:
-            values, indices = tr.predict(test_loader, k)
-        results = {"predictions": ranked_predictions(images, values, indices, classnames)}
-        out_csv = osp.join(cfg.OUTPUT_DIR, "predictions.csv")
-        write_predictions(out_csv, results["predictions"])
-        print(f"=> top-{k} predictions of {len(images):,} images: {out_csv}")
-        if args.nearest is not None:
-            # one path per bank row in label order: the bank's own (after the edits), or this run's exemplar items
-            per_class = tr.model._exemplar_paths
-            bank_paths = [p for ps in per_class for p in ps] if per_class is not None else (_label_order_paths(exemplars) if exemplars else None)
-            if bank_paths is not None and len(bank_paths) != tr.model._exemplar_bank()[0].shape[0]:
-                bank_paths = None                             # (no path per row: the column stays empty)
-            results["neighbours"] = nearest_neighbours(images, indices, sims, rows, classnames, bank_paths)
-            out_csv = osp.join(cfg.OUTPUT_DIR, "neighbours.csv")
-            write_neighbours(out_csv, results["neighbours"])
-            print(f"=> the {args.nearest} nearest exemplars of every predicted class: {out_csv}")
-    elif retrieve:
+        print(f"=> {', '.join(osp.join(out_dir, n) for n in AUDIT_FILES)}")
+    if p.mode == "audit":
+        return {}
+    if p.mode == "test":
+        run.tr.test()
+        return dict(run.tr.results)
+    if p.mode == "retrieve":
         # every rank walks its own batches of the pool and ends with the job's lists (trainer.retrieve); rank 0 writes
-        m = MAX_PER_CLASS if args.per_class is None else args.per_class
-        values, indices = tr.retrieve(test_loader, m, args.within_top)
+        values, indices = run.tr.retrieve(run.test_loader, p.m, p.within_top)
         results = {"retrieval": retrieval_rows(values, indices, images, classnames)}
-        if rank == 0:
-            out_csv = osp.join(cfg.OUTPUT_DIR, "retrieval.csv")
+        if run.rank == 0:
+            out_csv = osp.join(out_dir, "retrieval.csv")
             write_retrieval(out_csv, results["retrieval"])
             filled = len({r[0] for r in results["retrieval"]})
-            print(f"=> the {m} best of {len(images):,} images for each of {len(classnames):,} classes"
-                  + (f" (within each image's top {args.within_top})" if args.within_top is not None else "")
+            print(f"=> the {p.m} best of {len(images):,} images for each of {len(classnames):,} classes"
+                  + (f" (within each image's top {p.within_top})" if p.within_top is not None else "")
                   + f": {len(results['retrieval']):,} lines, {filled:,} classes with an image: {out_csv}")
+        return results
+    if p.nearest is not None:
+        values, indices, sims, rows = run.tr.predict_explained(run.test_loader, p.k, p.nearest)
     else:
-        tr.test()
-        results = dict(tr.results)
-    if eval_loader is not None:
-        _report_pipeline(results, "exemplar set", eval_loader)
-    for key, ld in edit_loaders.items():
+        values, indices = run.tr.predict(run.test_loader, p.k)
+    results = {"predictions": ranked_predictions(images, values, indices, classnames)}
+    out_csv = osp.join(out_dir, "predictions.csv")
+    write_predictions(out_csv, results["predictions"])
+    print(f"=> top-{p.k} predictions of {len(images):,} images: {out_csv}")
+    if p.nearest is not None:
+        results["neighbours"] = nearest_neighbours(images, indices, sims, rows, classnames, bank_rows()[1])
+        out_csv = osp.join(out_dir, "neighbours.csv")
+        write_neighbours(out_csv, results["neighbours"])
+        print(f"=> the {p.nearest} nearest exemplars of every predicted class: {out_csv}")
+    return results
+
+
+def _close_job(p, run, results: dict) -> dict:
+    """Stage 6: the loaders' reports, what every job's results carry, and the end of a process group opened here."""
+    if run.eval_loader is not None:
+        _report_pipeline(results, "exemplar set", run.eval_loader)
+    for key, ld in run.edit_loaders.items():
         _report_pipeline(results, f"{key} set", ld)
-    if not audit_only:
-        _report_pipeline(results, "predict set" if predict else "retrieve set" if retrieve else "test set", test_loader)
-    if audit_tables is not None:
-        results["bank_audit"] = {"exemplars": audit_tables[0], "neighbours": audit_tables[1], "classes": audit_tables[2]}
-    results["classnames"] = classnames
-    if test_loader.batch_shard is not None:
-        results["test_shard"] = {"rank": rank, "world": world, "batches": list(test_loader.batch_range), "images": len(test_loader.items)}
-    if own_group:                                # (a rank that raised inside the pass never gets here: its peers end at the group's timeout)
+    if p.mode != "audit":
+        _report_pipeline(results, f"{p.mode} set", run.test_loader)
+    if run.audit_tables is not None:
+        results["bank_audit"] = dict(zip(("exemplars", "neighbours", "classes"), run.audit_tables))
+    results["classnames"] = run.classnames
+    if run.test_loader.batch_shard is not None:
+        results["test_shard"] = {"rank": run.rank, "world": run.world, "batches": list(run.test_loader.batch_range), "images": len(run.test_loader.items)}
+    if run.own_group:                            # (a rank that raised inside the pass never gets here: its peers end at the group's timeout)
+        import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
     return results
+
+
+def main(argv=None) -> Dict[str, float]:
+    """train.py:183-255 on the evaluation path: build_trainer(cfg) and test().  MM_CLS_OP generates the classifiers from the exemplar set,
+    writes mm_classifiers.pt / visual_tokens.pt and evaluates the test set; the zero-shot trainers take the classes and test items of the
+    same job (build_splits; no exemplar is decoded) and the text classifier from DATASET.NAME's template(s), and write no model file.
+    The result block and acc_per_class.csv / f1_per_class.csv land in OUTPUT_DIR; --per-class-result adds the per-class block and
+    results["perclass_accuracy"], --confusion-matrix adds OUTPUT_DIR/cmat.pt, --score-curves adds two result lines, results["mAP"] /
+    ["mean_auroc"], curves_per_class.csv and score_hist.pt."""
+    from . import config
+    args = parse(argv)
+    p = plan_job(args, config.setup_cfg(args))                # train.py:134-155; nothing below the plan runs for a refused job
+    if p.skip:
+        print(f"Oops! The results exist at {p.cfg.OUTPUT_DIR} (so skip this job)")         # generate_classifier.sh:27-28
+        return {}
+    run = _open_job(p)                                        # process group, seed, bank, splits
+    _build_trainer(p, run)                                    # weights, loaders, trainer
+    _install_vocabulary(p, run)                               # generate | --classifiers | --bank and its edits
+    return _close_job(p, run, _run_mode(p, run))                # the audit, the mode's pass and files; then reports, results, barrier
 
 
 if __name__ == "__main__":

@@ -312,7 +312,8 @@ class PromptLearner:
 # ----------------------------------------------------------------------------- two test batches in flight
 class _TwoInFlight:
     """The model calls of an evaluation loop, software-pipelined over two handles / two streams (CustomCLIP.forward_batches,
-    ZeroshotCLIP.inference_batches).  A user defines `engine`, `device`, `_forward_on(engine, image[, out])` and `_twin_state()`."""
+    ZeroshotCLIP.inference_batches).  A user defines `engine`, `device`, `_forward_on(engine, image[, out])`, `_twin_state()` and the hook
+    `_before_outputs(what, eval_set_loader=None, one_mode=None)`: what the model owes before its first output -> the number of classes."""
 
     OVERLAP_MAX_TILES = 1024      # two batches in flight while the narrowest GEMM grid of ONE batch (ceil(rows / 256) x width / 256
                                   # workgroups of 256 x 256) stays within 4 rounds of the 256 CUs; beyond that a batch's partial last round is
@@ -365,10 +366,18 @@ class _TwoInFlight:
         values, indices = runtime.topk_rows(out, k)
         return values, indices.long()
 
-    def _retrieve_outputs(self, what: str, batches, eval_set_loader, overlap, stable_inputs):
-        """(number of classes, the [B, C] outputs of `batches` in order) for retrieve_batches; whatever the model owes before its first
-        output (CustomCLIP: one mode, generated classifiers) happens here, in the call."""
-        raise NotImplementedError
+    @torch.no_grad()
+    def output_batches(self, batches: Iterable, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
+        """CustomCLIP.forward_batches and ZeroshotCLIP.inference_batches under one name (their docstrings say the rest): the model's output
+        for every image batch, in order, two in flight.  What the model owes before its first output is the first next()'s, not the call's."""
+        self._before_outputs("output_batches", eval_set_loader)
+        yield from self._run_batches(batches, overlap, stable_inputs)
+
+    def predict_topk_batches(self, batches: Iterable, k: int, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
+        """predict_topk for every image batch, in order, over forward_batches / inference_batches (two batches in flight): one (values,
+        indices) pair per batch.  (The zero-shot models accept eval_set_loader for CustomCLIP's signature and do not read it.)"""
+        outs = self.output_batches(batches, eval_set_loader, overlap, stable_inputs)
+        return (self._topk(out, k) for out in outs)
 
     @torch.no_grad()
     def retrieve_batches(self, batches, m: int, within_top: Optional[int] = None, base: int = 0, eval_set_loader=None,
@@ -384,7 +393,7 @@ class _TwoInFlight:
         same score."""
         from . import runtime
         what = "retrieve_batches"
-        C, outs = self._retrieve_outputs(what, batches, eval_set_loader, overlap, stable_inputs)
+        C, outs = self._before_outputs(what, eval_set_loader, "a search by class"), self._run_batches(batches, overlap, stable_inputs)   # (owed in the call)
         m = runtime._want_int(what, "m", m, 1, runtime.MAX_PER_CLASS)
         if within_top is not None:
             within_top = runtime._want_int(what, "within_top", within_top, 1, min(32, C))
@@ -907,11 +916,8 @@ class CustomCLIP(_TwoInFlight):
     def forward(self, image, label=None, eval_set_loader=None, scale_no=None):
         """:294-364, evaluation branch: [B,3,R,R] -> [B,C] fp32; with cfg.EVAL_MODE == "all" [4,B,C], the four modes of :348-363 in
         runtime.ALL_MODES order (fusion, text, vision, multimodal), each plane bit-equal to what its own EVAL_MODE returns."""
-        if eval_set_loader is None and self.mm_classifier is None:
-            raise NotImplementedError("the training branch of CustomCLIP.forward (autograd) is out of scope; "
-                                      "pass eval_set_loader= to generate the classifiers")
-        if self.mm_classifier is None:                                              # :341-342 (the features of `image` do not depend on it)
-            self.forward_prompt(eval_set_loader, wait_files=False)                  # the files land while this batch and the next ones run
+        self._classifiers_or(eval_set_loader, NotImplementedError, "the training branch of CustomCLIP.forward (autograd) is out of scope; "
+                             "pass eval_set_loader= to generate the classifiers")    # :341-342 (the features of `image` do not depend on it)
         B = image.shape[0]
         if self.SPLIT_FORWARD and 2 * self.SPLIT_MIN_HALF <= B <= self._split_cap() and self._split_keeps_bits(B):
             return self._forward_split(image)
@@ -983,41 +989,58 @@ class CustomCLIP(_TwoInFlight):
         self._one_mode("predict_topk")
         return self._topk(self.forward(image, eval_set_loader=eval_set_loader), k)
 
-    @torch.no_grad()
     def predict_topk_batches(self, batches: Iterable, k: int, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
-        """predict_topk for every image batch, in order, over forward_batches (two batches in flight): one (values, indices) pair per batch."""
-        self._one_mode("predict_topk_batches")               # (raised by the call, not by the first next())
-        outs = self.forward_batches(batches, eval_set_loader=eval_set_loader, overlap=overlap, stable_inputs=stable_inputs)
-        return (self._topk(out, k) for out in outs)
+        self._one_mode("predict_topk_batches")               # (raised by the call; the classifiers are the first next()'s, as in forward_batches)
+        return super().predict_topk_batches(batches, k, eval_set_loader, overlap, stable_inputs)
 
-    def _retrieve_outputs(self, what: str, batches, eval_set_loader, overlap, stable_inputs):
-        self._one_mode(what, "a search by class")
+    def _classifiers_or(self, eval_set_loader, error, text: str):
+        """The classifiers exist, or are generated from eval_set_loader now (the files land while the caller goes on), or error(text)."""
         if self.mm_classifier is None:
             if eval_set_loader is None:
-                raise NotImplementedError("pass eval_set_loader= to generate the classifiers")
+                raise error(text)
             self.forward_prompt(eval_set_loader, wait_files=False)
-        return int(self.mm_classifier.shape[0]), self._run_batches(batches, overlap, stable_inputs)
+
+    def _before_outputs(self, what: str, eval_set_loader=None, one_mode: Optional[str] = None) -> int:
+        if one_mode is not None:                             # (what `what` yields needs one mode: `one_mode` is the noun of the refusal)
+            self._one_mode(what, one_mode)
+        self._classifiers_or(eval_set_loader, NotImplementedError, "pass eval_set_loader= to generate the classifiers")
+        return int(self.mm_classifier.shape[0])
 
     # ------------------------------------------------------------------ nearest exemplars (no counterpart in the reference's API)
     MAX_NEAREST = 32              # ovmr_nearest_rows (include/ovmr_hip_nearest.h)
 
-    def _exemplar_bank(self):
-        """(bank [R, D] fp16, starts int64 [C + 1] on the device): the exemplar features class after class in label order -- the uniform
-        [C, S, D] store viewed as [C S, D], the packed store as it is once its rows are in label order (load_bank and the edits leave it
-        so; a ragged generation's loader order is sorted once and kept) -- and the prefix sum of the classes' shots."""
+    def _bank_view(self):
+        """(bank [R, D] fp16, starts int64 [C + 1] on the device, starts as a host list, the longest class): the exemplar features class
+        after class in label order -- the uniform [C, S, D] store viewed as [C S, D], the packed store as it is once its rows are in label
+        order (load_bank and the edits leave it so; a ragged generation's loader order is sorted once and kept) -- and the prefix sum of
+        the classes' shots.  Kept with the store it describes, so the packed store's class sizes are read back once per store."""
         src, lab = self.eval_feat4cls, getattr(self, "eval_row_labels", None)
         kept = self.__dict__.get("_nearest_bank")
-        if kept is not None and kept[0] is src and kept[1] is lab:
-            return kept[2], kept[3]
-        if lab is None:
-            C, S, D = src.shape
-            bank, shots = src.reshape(C * S, D), torch.full((C,), S, dtype=torch.int64)
-        else:
-            per_class = self._class_rows()
-            bank, shots = torch.cat(per_class).contiguous(), torch.tensor([int(r.shape[0]) for r in per_class], dtype=torch.int64)
-        starts = torch.cat([torch.zeros(1, dtype=torch.int64), shots.cumsum(0)]).to(self.device)
-        self._nearest_bank = (src, lab, bank, starts)
-        return bank, starts
+        if kept is None or kept[0] is not src or kept[1] is not lab:
+            if lab is None:
+                C, S, D = src.shape
+                bank, shots = src.reshape(C * S, D), [S] * C
+            else:
+                per_class = self._class_rows()
+                bank, shots = torch.cat(per_class).contiguous(), [int(r.shape[0]) for r in per_class]
+            starts = np.concatenate([[0], np.cumsum(shots, dtype=np.int64)]).tolist()
+            kept = self._nearest_bank = (src, lab, bank, torch.tensor(starts, dtype=torch.int64).to(self.device), starts, max(shots, default=0))
+        return kept[2:]
+
+    def _exemplar_bank(self):
+        """(bank [R, D] fp16, starts int64 [C + 1] on the device) of _bank_view()."""
+        return self._bank_view()[:2]
+
+    def _bank_starts_host(self):
+        """(starts: list of C + 1 ints, the longest class) of _bank_view(), on the host."""
+        return self._bank_view()[2:]
+
+    def exemplar_rows(self, label_order_paths: Optional[Sequence[str]] = None):
+        """(exemplars per class: C ints, the path of every bank row in label order: R strings, or None where there is no path per row).
+        The paths are the model's own if it holds them (load_bank, the edits), else `label_order_paths`, dropped unless it counts R."""
+        starts, own = self._bank_starts_host()[0], self._exemplar_paths
+        paths = [p for ps in own for p in ps] if own is not None else list(label_order_paths or ())
+        return [b - a for a, b in zip(starts, starts[1:])], paths if paths and len(paths) == starts[-1] else None
 
     @torch.no_grad()
     def nearest_exemplars(self, feats_or_image, k: int, classes=None):
@@ -1066,10 +1089,7 @@ class CustomCLIP(_TwoInFlight):
         int64 [B, k], similarities fp32 [B, k, n], rows int64 [B, k, n]): the first two are predict_topk's, bit for bit; rows index the
         bank's features / exemplar_paths, -1 (similarity -inf) where a class has fewer than n exemplars."""
         self._one_mode("predict_explained")
-        if self.mm_classifier is None:
-            if eval_set_loader is None:
-                raise ValueError("predict_explained: the model has no classifiers yet (pass eval_set_loader=, or load_bank)")
-            self.forward_prompt(eval_set_loader, wait_files=False)
+        self._classifiers_or(eval_set_loader, ValueError, "predict_explained: the model has no classifiers yet (pass eval_set_loader=, or load_bank)")
         self._needs_state("predict_explained")
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= int(n) <= self.MAX_NEAREST:
             raise ValueError(f"predict_explained: n must be an integer in [1, {self.MAX_NEAREST}], got {n!r}")
@@ -1079,20 +1099,6 @@ class CustomCLIP(_TwoInFlight):
         return values, indices, sims, rows
 
     # ------------------------------------------------------------------ auditing the reference bank (no counterpart in the reference's API)
-    def _bank_starts_host(self):
-        """(starts: list of C + 1 ints, the longest class) of _exemplar_bank()'s view, on the host; kept with the store it describes (the
-        packed store's class sizes are read back once)."""
-        src, lab = self.eval_feat4cls, getattr(self, "eval_row_labels", None)
-        kept = self.__dict__.get("_audit_starts")
-        if kept is not None and kept[0] is src and kept[1] is lab:
-            return kept[2], kept[3]
-        shots = [int(src.shape[1])] * int(src.shape[0]) if lab is None else [int(n) for n in self._ragged_n_label.tolist()]
-        starts = [0]
-        for n in shots:
-            starts.append(starts[-1] + n)
-        self._audit_starts = (src, lab, starts, max(shots) if shots else 0)
-        return starts, self._audit_starts[3]
-
     @torch.no_grad()
     def audit_bank(self, k: int = 5, classes=None, dup_threshold: float = 0.995, batch: int = 1024):
         """Every exemplar's nearest neighbours inside its own class (itself left out) and outside it, by h(row . row) on the view of
@@ -1123,11 +1129,10 @@ class CustomCLIP(_TwoInFlight):
             raise ValueError(f"audit_bank: batch must be a positive integer, got {batch!r}")
         if isinstance(dup_threshold, bool) or not isinstance(dup_threshold, (int, float, np.floating, np.integer)) or dup_threshold != dup_threshold:
             raise ValueError(f"audit_bank: dup_threshold must be a number, got {dup_threshold!r}")
-        bank, starts = self._exemplar_bank()
+        bank, starts, hstarts, longest = self._bank_view()
         R, C, dev = bank.shape[0], starts.shape[0] - 1, self.device
         if k > R:
             raise ValueError(f"audit_bank: k = {k} exceeds the bank's {R} exemplar rows")
-        hstarts, longest = self._bank_starts_host()
         if classes is None:
             rows, queries = torch.arange(R, dtype=torch.int64, device=dev), bank
         else:
@@ -1596,11 +1601,7 @@ class CustomCLIP(_TwoInFlight):
         tensor is not overwritten before its output has been handed over (a resident data set); otherwise each batch is first
         copied on the current stream, so that loaders which recycle their device buffers (loader.PipelinedFolderLoader)
         stay correct."""
-        if self.mm_classifier is None:
-            if eval_set_loader is None:
-                raise NotImplementedError("pass eval_set_loader= to generate the classifiers")
-            self.forward_prompt(eval_set_loader, wait_files=False)
-        yield from self._run_batches(batches, overlap, stable_inputs)
+        return self.output_batches(batches, eval_set_loader, overlap, stable_inputs)
 
 
 class ZeroshotCLIP(_TwoInFlight):
@@ -1661,20 +1662,13 @@ class ZeroshotCLIP(_TwoInFlight):
         """model_inference(image) followed by ovmr_topk_rows on its logits, on the same stream: (values fp32 [B, k], indices int64 [B, k])."""
         return self._topk(self.model_inference(image), k)
 
-    @torch.no_grad()
-    def predict_topk_batches(self, batches: Iterable, k: int, eval_set_loader=None, overlap: Optional[bool] = None, stable_inputs: bool = False):
-        """predict_topk for every image batch, in order, over inference_batches (two batches in flight)."""
-        for out in self.inference_batches(batches, overlap=overlap, stable_inputs=stable_inputs):
-            yield self._topk(out, k)
+    def _before_outputs(self, what: str, eval_set_loader=None, one_mode: Optional[str] = None) -> int:
+        return int(self.text_features.shape[0])              # (the text classifier exists since __init__, and there is one mode)
 
-    def _retrieve_outputs(self, what: str, batches, eval_set_loader, overlap, stable_inputs):
-        return int(self.text_features.shape[0]), self._run_batches(batches, overlap, stable_inputs)
-
-    @torch.no_grad()
     def inference_batches(self, batches: Iterable, overlap: Optional[bool] = None, stable_inputs: bool = False):
         """model_inference for every image batch of the test loop (Dassl.pytorch/dassl/engine/trainer.py:461-482), in order and bit-identical
         to calling it per batch, two batches in flight on two handles / streams (as CustomCLIP.forward_batches)."""
-        yield from self._run_batches(batches, overlap, stable_inputs)
+        return self.output_batches(batches, None, overlap, stable_inputs)
 
 
 class ZeroshotCLIP2(ZeroshotCLIP):

@@ -18,7 +18,7 @@ hands the trainer: `dataset.classnames`, `test_loader`, `val_loader` (may be Non
 
 `ZeroshotCLIP` / `ZeroshotCLIP2` (trainers/zsclip.py) are registered next to it with the same Dassl-facing methods; they need only
 `dataset.classnames` and `test_loader`.  What Dassl's SimpleTrainer gives all three lives in `_EvalTrainer`; a trainer class states
-`check_cfg`, `build_model`, `model_inference` and how its model turns the test batches into outputs.
+`check_cfg`, `build_model`, `model_inference` and what differs from the shared passes (`explained`, `after_test`, `output_modes`).
 """
 from __future__ import annotations
 
@@ -108,9 +108,10 @@ class _EvalTrainer:
             print(f'Loading weights to {name} from "{path}" (epoch = {saved_epoch})')
             self._models[name].load_state_dict(state, strict=False)
 
+    # the three passes over input batches, on the models' shared methods (modules._TwoInFlight; a zero-shot model ignores the exemplar loader)
     def outputs(self, inputs):
-        """model_inference for every input batch of the test pass, in order (a model may keep further batches in flight)."""
-        raise NotImplementedError
+        """model_inference for every input batch of the test pass, in order (the model keeps two batches in flight)."""
+        return self.model.output_batches(inputs, eval_set_loader=self.eval_set_loader)
 
     def after_test(self):
         """What a trainer still owes once the last output has been counted."""
@@ -210,7 +211,7 @@ class _EvalTrainer:
 
     def ranked(self, inputs, k):
         """predict_topk for every input batch, in order: (values fp32 [B, k], indices int64 [B, k]) pairs."""
-        raise NotImplementedError
+        return self.model.predict_topk_batches(inputs, k, eval_set_loader=self.eval_set_loader)
 
     @torch.no_grad()
     def predict(self, data_loader, k: int = 5):
@@ -226,7 +227,7 @@ class _EvalTrainer:
 
     def searched(self, inputs, m, within_top, base):
         """retrieve_batches over the input batches: the model's runtime.ColumnTopM."""
-        raise NotImplementedError
+        return self.model.retrieve_batches(inputs, m, within_top, base, eval_set_loader=self.eval_set_loader)
 
     @torch.no_grad()
     def retrieve(self, data_loader, m: int = 32, within_top=None):
@@ -323,15 +324,6 @@ class MM_CLS_OP(_EvalTrainer):
             return self.model(input, eval_set_loader=self.eval_set_loader, scale_no=scale_no, label=label)
         return self.model(input, label=label)
 
-    def outputs(self, inputs):
-        return self.model.forward_batches(inputs, eval_set_loader=self.eval_set_loader)
-
-    def ranked(self, inputs, k):
-        return self.model.predict_topk_batches(inputs, k, eval_set_loader=self.eval_set_loader)
-
-    def searched(self, inputs, m, within_top, base):
-        return self.model.retrieve_batches(inputs, m, within_top, base, eval_set_loader=self.eval_set_loader)
-
     def explained(self, inputs, k, n):
         return (self.model.predict_explained(image, k, n, eval_set_loader=self.eval_set_loader) for image in inputs)
 
@@ -373,17 +365,8 @@ class ZeroshotCLIP(_EvalTrainer):
     def model_inference(self, image):
         return self.model.model_inference(image)                             # :55-60
 
-    def outputs(self, inputs):
-        return self.model.inference_batches(inputs)
-
     def output_modes(self):
         return None                                  # (the zero-shot trainers ignore EVAL_MODE: [B, C] logits whatever it says)
-
-    def ranked(self, inputs, k):
-        return self.model.predict_topk_batches(inputs, k)
-
-    def searched(self, inputs, m, within_top, base):
-        return self.model.retrieve_batches(inputs, m, within_top, base)
 
 
 class ZeroshotCLIP2(ZeroshotCLIP):
