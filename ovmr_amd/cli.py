@@ -403,6 +403,26 @@ def check_score_curves(args, trainer_name: str, zeroshot: bool):
     return bins, (lo, hi)
 
 
+DEFAULT_EXACT_GIB = 16.0
+
+
+def check_exact_curves(args):
+    """The refusals of `--exact-curves [--exact-budget GIB]`, before anything is listed or loaded -> (on, bytes of the score store's
+    budget or None).  Any trainer will do: the exact figures take the scores as they are and need no range."""
+    import math
+    if not args.exact_curves:
+        if args.exact_budget is not None:
+            raise SystemExit("--exact-budget GIB belongs to --exact-curves: the memory the kept scores of the test pass may take")
+        return False, None
+    for flag, v in (("--predict", args.predict), ("--retrieve", args.retrieve)):
+        if v is not None:
+            raise SystemExit(f"--exact-curves belongs to the test pass: {flag} reads unlabelled images, a score has no label to be held against")
+    gib = DEFAULT_EXACT_GIB if args.exact_budget is None else args.exact_budget
+    if not (math.isfinite(gib) and gib > 0):
+        raise SystemExit(f"--exact-budget {gib}: GIB must be a positive number of GiB")
+    return True, int(gib * (1 << 30))
+
+
 def check_pool_size(n: int, path: str):
     """An image's position in the pool takes the 32 low bits of a key, 2^32 - 1 excluded (include/ovmr_hip_retrieve.h)."""
     if n >= MAX_POOL:
@@ -592,6 +612,12 @@ def parse(argv=None):
                     "mAP and mean AUROC and writes OUTPUT_DIR/curves_per_class.csv and score_hist.pt (per mode under --eval_mode all)")
     ap.add_argument("--score-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --score-curves: the scores the bins "
                     "cover (default 0 1 for MM_CLS_OP's probabilities; required for the zero-shot trainers' logits)")
+    ap.add_argument("--exact-curves", action="store_true", help="the test pass also keeps every score on the GPU and, when it ends, counts "
+                    "them against each class's own positive scores (ovmr_eval_ranks): reports exact_mAP and exact_mean_auroc -- the figures "
+                    "sklearn gives on the raw scores, from any trainer, no range needed -- and writes OUTPUT_DIR/ranks_per_class.csv and "
+                    "rank_state.pt (per mode under --eval_mode all)")
+    ap.add_argument("--exact-budget", type=float, default=None, metavar="GIB", help="with --exact-curves: the most memory the kept scores may "
+                    "take, in GiB (default 16; 50 000 images x 1000 classes are 0.2 GiB in fp32); the batch that would pass it ends the run")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode worker processes of the pipelined loader (default: DATALOADER.NUM_WORKERS); 0 = decode in this thread")
@@ -791,6 +817,7 @@ def plan_job(args, cfg):
     check_retrieve(args, name, zeroshot, cfg.EVAL_MODE)
     pool = predict or retrieve                                # unlabelled images instead of the labelled test split
     curve_bins, curve_range = check_score_curves(args, name, zeroshot)
+    exact, exact_bytes = check_exact_curves(args)
     check_nearest(args, name, zeroshot)
     check_audit(args, name, zeroshot, world)
     images, k, m = [], None, (MAX_PER_CLASS if args.per_class is None else args.per_class) if retrieve else None
@@ -821,6 +848,7 @@ def plan_job(args, cfg):
                         mode="audit" if audit_only else "predict" if predict else "retrieve" if retrieve else "test",
                         k=k, m=m, within_top=args.within_top, nearest=args.nearest, audit=args.audit_bank,
                         dup_threshold=0.995 if args.dup_threshold is None else args.dup_threshold, curve_bins=curve_bins, curve_range=curve_range,
+                        exact=exact, exact_bytes=exact_bytes,
                         ragged=bool(args.ragged_shots) and vocabulary in ("generate", "bank"), lift_shots=vocabulary != "generate", skip=False)
     decodes = vocabulary == "generate" or edits               # exemplars are decoded and mm_classifiers.pt is written
     if decodes and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
@@ -941,7 +969,8 @@ def _build_trainer(p, run):
     dm = SimpleNamespace(dataset=SimpleNamespace(classnames=classnames), test_loader=test_loader, val_loader=None, eval_set_loader=eval_loader)
     run.tr = trainer.build_trainer(cfg, dm, clip_weights=clip_sd, tokenizer=BPETokenizer(args.bpe_path), device=args.device,
                                    reserve=(batch, 256, max(1024, len(classnames))), per_class_result=args.per_class_result,
-                                   compute_cmat=args.confusion_matrix, score_curves=p.curve_bins, score_range=p.curve_range, **kw)
+                                   compute_cmat=args.confusion_matrix, score_curves=p.curve_bins, score_range=p.curve_range,
+                                   exact_curves=p.exact, exact_max_bytes=p.exact_bytes, **kw)
     run.eval_loader, run.edit_loaders, run.test_loader = eval_loader, edit_loaders, test_loader
 
 
@@ -1053,7 +1082,8 @@ def main(argv=None) -> Dict[str, float]:
     same job (build_splits; no exemplar is decoded) and the text classifier from DATASET.NAME's template(s), and write no model file.
     The result block and acc_per_class.csv / f1_per_class.csv land in OUTPUT_DIR; --per-class-result adds the per-class block and
     results["perclass_accuracy"], --confusion-matrix adds OUTPUT_DIR/cmat.pt, --score-curves adds two result lines, results["mAP"] /
-    ["mean_auroc"], curves_per_class.csv and score_hist.pt."""
+    ["mean_auroc"], curves_per_class.csv and score_hist.pt, --exact-curves two more, results["exact_mAP"] / ["exact_mean_auroc"],
+    ranks_per_class.csv and rank_state.pt."""
     from . import config
     args = parse(argv)
     p = plan_job(args, config.setup_cfg(args))                # train.py:134-155; nothing below the plan runs for a refused job

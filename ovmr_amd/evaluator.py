@@ -18,6 +18,15 @@ class's average precision, AUROC and best-F1 operating point from it, adds `mAP`
 result block, and writes `curves_per_class.csv` and `score_hist.pt`.  With `curves=None` nothing of this is allocated, launched, printed
 or written.
 
+Exact ranking figures (`exact=True`; no counterpart in the reference): the figures of the binned scores above are not those a paper reports.
+For one class every exact figure depends only on where each negative falls relative to the class's own positive scores, and those are known
+when the pass ends.  So `process()` keeps every batch's outputs on their device (under `exact_max_bytes`), and at the end of the pass
+`count_ranks()` builds per class the table of its distinct positive scores (`rank_edges`) and counts every kept batch against it -- ONE
+`ovmr_eval_ranks` launch per batch (csrc/eval_ranks.hip, include/ovmr_hip_ranks.h) into an int32 [2, 2E + C] state -- and frees the scores.
+evaluate() derives every class's average precision, AUROC and best-F1 operating point from the counts (`rank_figures`: sklearn's figures on
+the raw scores), adds `exact_mAP` and `exact_mean_auroc` to the results and two lines to the result block, and writes `ranks_per_class.csv`
+and `rank_state.pt`.  With `exact=False` nothing of this is kept, launched, printed or written.
+
 Outputs that live on the GPU go through the kernel and nothing else: without libovmr_hip.so `process` raises.  Host
 tensors (an evaluator built with device="cpu": host-side callers, the CPU tests of evaluate()'s arithmetic) are counted
 on the host.
@@ -85,10 +94,145 @@ def curve_figures(hist, lo: float, hi: float, bins: int) -> dict:
                 threshold=np.where(have, thr, np.nan), precision=np.where(have, prec[rows, slot], np.nan), recall=np.where(have, rec, np.nan))
 
 
+RANK_COLUMNS = ["label", "classname", "positives", "negatives", "ap", "auroc", "best_f1", "threshold", "precision", "recall"]
+
+
+def rank_keys(x):
+    """The value part of the library's selection key (csrc/eval_common.h: topk_key) of fp32 values, as numpy uint32 of the same shape:
+    x above y in the library's order <=> key(x) > key(y); every NaN is one key, the largest; -0.0 and +0.0 share theirs; a denormal keeps
+    its own."""
+    import numpy as np
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    u = x.view(np.uint32).copy()
+    u[u == 0x80000000] = 0
+    u = np.where(u & 0x80000000, ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+    u[np.isnan(x)] = 0xFFFFFFFF
+    return u
+
+
+def _key_values(k):
+    """rank_keys inverted: the canonical fp32 of every key (one NaN, +0.0 for either zero)."""
+    import numpy as np
+    k = np.asarray(k, dtype=np.uint32)
+    u = np.where(k & 0x80000000, k ^ np.uint32(0x80000000), ~k).astype(np.uint32)
+    u[k == 0xFFFFFFFF] = 0x7FC00000
+    return u.view(np.float32)
+
+
+def rank_edges(pos_scores, pos_labels, C: int):
+    """The edge table of include/ovmr_hip_ranks.h from the positives of a pass: pos_scores [n] (any float dtype; the score every image
+    gave its own class) and pos_labels [n] -> (edges fp32 [E], estart int32 [C + 1]) on the host.  Scores are canonicalised first (-0
+    becomes +0, any NaN the one NaN 0x7FC00000); class c's edges are its distinct scores, strictly descending in the library's value order
+    (NaN first).  Labels outside [0, C) have no class and are left out.  Deterministic in the MULTISET of (score, label) pairs: their
+    order, and which rank sent which, do not matter."""
+    import numpy as np
+    s = torch.as_tensor(pos_scores).detach().float().cpu().reshape(-1).numpy()
+    y = torch.as_tensor(pos_labels).detach().cpu().reshape(-1).numpy().astype(np.int64)
+    if s.shape != y.shape:
+        raise ValueError(f"rank_edges: pos_scores and pos_labels must be of one length, got {s.shape[0]} and {y.shape[0]}")
+    ok = (y >= 0) & (y < C)
+    # ascending in (label, 2^32 - 1 - key) = by class, then descending by value; np.unique leaves each (class, value) once
+    pairs = np.unique((y[ok].astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - rank_keys(s[ok]).astype(np.uint64)))
+    cls = (pairs >> np.uint64(32)).astype(np.int64)
+    edges = _key_values((np.uint64(0xFFFFFFFF) - (pairs & np.uint64(0xFFFFFFFF))).astype(np.uint32))
+    estart = np.zeros(C + 1, dtype=np.int64)
+    estart[1:] = np.cumsum(np.bincount(cls, minlength=C))
+    if estart[-1] >= 2 ** 31:
+        raise ValueError(f"rank_edges: {int(estart[-1])} edges do not fit estart's int32")
+    return torch.from_numpy(edges.copy()), torch.from_numpy(estart.astype(np.int32))
+
+
+def rank_cells(mo, edges, estart, max_edges: Optional[int] = None) -> torch.Tensor:
+    """The cell rule of include/ovmr_hip_ranks.h on the host: mo [B, C] (any float dtype), edges fp32 [E], estart int32 [C + 1] -> int64
+    [B, C], the cell of mo[b, c] WITHIN class c (add 2 estart[c] + c for its place in a plane): with k the number of the class's edges
+    strictly above the score in the library's value order, 2 k + 1 where edge k equals the score, else 2 k.  estart is clamped as the
+    kernel clamps it, and a class is searched against its first min(E_c, max_edges) edges (None: all of them)."""
+    import numpy as np
+    x = rank_keys(torch.as_tensor(mo).detach().float().cpu().numpy())
+    B, C = x.shape
+    ek = rank_keys(torch.as_tensor(edges).detach().float().cpu().numpy())
+    es = torch.as_tensor(estart).cpu().numpy().astype(np.int64)
+    E = ek.shape[0]
+    cells = np.zeros((B, C), dtype=np.int64)
+    for c in range(C):
+        lo = min(max(int(es[c]), 0), E)
+        hi = min(max(int(es[c + 1]), lo), E)
+        n = hi - lo if max_edges is None else min(hi - lo, int(max_edges))
+        if n == 0:
+            continue
+        asc = ek[lo:lo + n][::-1]                                            # ascending keys
+        above = n - np.searchsorted(asc, x[:, c], side="right")              # edges strictly above the score
+        tied = np.searchsorted(asc, x[:, c], side="right") > np.searchsorted(asc, x[:, c], side="left")
+        cells[:, c] = 2 * above + tied
+    return torch.from_numpy(cells)
+
+
+def rank_count(state: torch.Tensor, mo, gt, edges, estart, max_edges: Optional[int] = None) -> None:
+    """ovmr_eval_ranks for host tensors: adds one batch to state int32 [2, 2E + C] in place, by rank_cells."""
+    B, C = mo.shape
+    gt = torch.as_tensor(gt).long().cpu()
+    ok = (gt >= 0) & (gt < C)
+    es = torch.as_tensor(estart).long().cpu()
+    E = int(torch.as_tensor(edges).shape[0])
+    base = 2 * es[:C].clamp(0, E) + torch.arange(C)
+    cell = (rank_cells(mo, edges, estart, max_edges) + base.unsqueeze(0))[ok]
+    own = (gt[ok].unsqueeze(1) == torch.arange(C).unsqueeze(0)).long()
+    flat = (own * (2 * E + C) + cell).reshape(-1)
+    state += torch.bincount(flat, minlength=2 * (2 * E + C)).to(state.dtype).view(2, 2 * E + C)
+
+
+def rank_figures(state, edges, estart) -> dict:
+    """state: integer [2, 2E + C] (plane 0 negatives, plane 1 positives; class c's 2 E_c + 1 cells from 2 estart[c] + c), edges fp32 [E],
+    estart int32 [C + 1] -> per-class numpy arrays, computed from int64 counts in fp64.  With pos_k and neq_k the counts tied with edge k
+    of a class (edges descending: k = 0 is the highest score), ngap_k the negatives in the gap above it, P and N the class's totals:
+      TP_k = cumsum(pos), FP_k = cumsum(neq + ngap): what a cut AT edge k admits;
+      ap      sum_k pos_k / P x TP_k / (TP_k + FP_k)            (sklearn's average_precision_score on the raw scores); NaN where P == 0;
+      auroc   sum_k pos_k x ((N - FP_k) + neq_k / 2) / (P N)    (roc_auc_score, ties at half); NaN where P N == 0;
+      best_f1 max_k 2 TP_k / (2 TP_k + FP_k + P - TP_k), ties to the HIGHER threshold, with threshold = that edge itself (a real score),
+              precision and recall of the cut; NaN where P == 0.
+    A positive in an even cell (a gap) raises: every positive IS an edge, so the kept scores or labels changed under the evaluator."""
+    import numpy as np
+    st = torch.as_tensor(state).cpu().numpy().astype(np.int64)
+    ed = torch.as_tensor(edges).cpu().numpy().astype(np.float32)
+    es = torch.as_tensor(estart).cpu().numpy().astype(np.int64)
+    C, E = es.shape[0] - 1, ed.shape[0]
+    if st.shape != (2, 2 * E + C):
+        raise ValueError(f"rank_figures: state must be of shape [2, {2 * E + C}] for {E} edges and {C} classes, got {list(st.shape)}")
+    out = {k: np.full(C, np.nan) for k in ("ap", "auroc", "best_f1", "threshold", "precision", "recall")}
+    P, N = np.zeros(C, dtype=np.int64), np.zeros(C, dtype=np.int64)
+    for c in range(C):
+        n, base = int(es[c + 1] - es[c]), 2 * int(es[c]) + c
+        neg, own = st[0, base:base + 2 * n + 1], st[1, base:base + 2 * n + 1]
+        if own[0::2].any():
+            raise ValueError(f"rank_figures: class {c} holds {int(own[0::2].sum())} positive(s) between its edges: the kept scores or labels "
+                             "changed after the edges were built")
+        pos, neq, ngap = own[1::2].astype(np.float64), neg[1::2].astype(np.float64), neg[0:2 * n:2].astype(np.float64)
+        P[c], N[c] = own.sum(), neg.sum()
+        if P[c] == 0:
+            continue
+        p, q = float(P[c]), float(N[c])
+        tp, fp = np.cumsum(pos), np.cumsum(neq + ngap)
+        prec = tp / (tp + fp)                                                # (tp >= 1 at every edge: an edge is a positive's score)
+        out["ap"][c] = float((pos / p * prec).sum())
+        if N[c] > 0:
+            out["auroc"][c] = float((pos * ((q - fp) + neq / 2)).sum() / (p * q))
+        f1 = 2 * tp / (2 * tp + fp + p - tp)
+        k = int(np.argmax(f1))                                               # (the first maximum: the highest threshold)
+        out["best_f1"][c], out["precision"][c], out["recall"][c] = f1[k], prec[k], tp[k] / p
+        out["threshold"][c] = ed[int(es[c]) + k]
+    return dict(positives=P, negatives=N, **out)
+
+
 class Classification:
     def __init__(self, num_classes: int, classnames: Optional[Sequence[str]] = None, device="cuda", per_class: bool = False,
-                 confusion: bool = False, curves: Optional[int] = None, score_range=(0.0, 1.0)):
+                 confusion: bool = False, curves: Optional[int] = None, score_range=(0.0, 1.0), exact: bool = False,
+                 exact_max_bytes: int = 16 << 30):
         self.num_classes = num_classes
+        if not isinstance(exact, bool):
+            raise ValueError(f"Classification: exact must be True or False, got {exact!r}")
+        if isinstance(exact_max_bytes, bool) or not isinstance(exact_max_bytes, int) or exact_max_bytes < 0:
+            raise ValueError(f"Classification: exact_max_bytes must be a number of bytes >= 0, got {exact_max_bytes!r}")
+        self.exact, self.exact_max_bytes = exact, int(exact_max_bytes)
         self.curve_bins, self.score_range = None, None
         if curves is not None:
             from .runtime import MAX_BINS, curve_scale
@@ -115,6 +259,11 @@ class Classification:
         self._curves = None                          # int32 [C, 2, bins + 3], curves=: allocated by begin() (include/ovmr_hip_curves.h)
         self.score_hist = None                       # int64 [C, 2, bins + 3] on the host, and
         self.curves = None                           # curve_figures() of it, both set by evaluate()
+        self._kept = []                              # exact=: (outputs [B, C] as they arrived, labels int64 [B]) of every batch of the pass
+        self._kept_bytes = 0                         # bytes of the kept outputs, held under exact_max_bytes
+        self._rank = None                            # (edges fp32 [E], estart int32 [C + 1], state int32 [2, 2E + C]) once counted
+        self.rank_state = None                       # the same three on the host, state as int64, and
+        self.ranks = None                            # rank_figures() of them, both set by evaluate()
 
     def begin(self, topk: int = 1):
         """Allocates the state of a pass that uses `topk`, without a batch: what the first process() of a pass does by itself.  A pass
@@ -142,7 +291,9 @@ class Classification:
         holds the job's counters.  The small counters of all of them travel in one all-reduce, each confusion matrix in one of its own
         (shard.all_reduce_eval_state).  Every evaluator has begun its pass (begin(), or a first process()), with the same topk and the
         same flags on every rank: the collectives' shapes then do not depend on what a rank counted.  A score-curve state travels like a
-        confusion matrix, in an all-reduce of its own."""
+        confusion matrix, in an all-reduce of its own.  An exact evaluator (exact=True) then counts its kept scores (count_ranks): one
+        all-gather of the lengths and one of the padded (score, label) pairs of the positives, every rank builds the same edges and counts
+        its own batches, and one all-reduce sums the int32 state."""
         from .shard import all_reduce_eval_state
         small, cmats = [], []
         for ev in evaluators:
@@ -155,6 +306,9 @@ class Classification:
             if ev._curves is not None:
                 cmats.append(ev._curves)
         all_reduce_eval_state(small, cmats, dist)
+        for ev in evaluators:
+            if ev.exact:
+                ev.count_ranks(dist)
 
     @torch.no_grad()
     def process(self, mo: torch.Tensor, gt: torch.Tensor, topk: int = 1):
@@ -175,6 +329,8 @@ class Classification:
         if self.device.type == "cpu":
             pred, ok = self._process_host(mo, gt)
             gt = gt.long()
+            if self.exact:
+                self._keep(mo, gt)
             if self._curves is not None:
                 self._curves_host(mo, gt, ok)
             if topk > 1:
@@ -196,6 +352,8 @@ class Classification:
         gt = gt.to(self.device, non_blocking=True)
         if gt.dtype != torch.int64 or not gt.is_contiguous():
             gt = gt.long().contiguous()
+        if self.exact:
+            self._keep(mo, gt)
         if self._curves is not None:                                      # ONE launch: every score into its class's two histograms
             runtime.eval_curves(mo, gt, self.score_range[0], self.score_range[1], self.curve_bins, self._curves)
         if self.per_class or self.confusion:                              # ONE launch: counts, hits, per-class matches, confusion counts
@@ -231,6 +389,56 @@ class Classification:
         cell = (torch.arange(C).unsqueeze(0) * 2 + own) * S + slot
         self._curves += torch.bincount(cell.reshape(-1), minlength=C * 2 * S).int().view(C, 2, S)
 
+    def _keep(self, mo, gt):
+        """exact=: keeps the batch's outputs in the dtype they arrived in, on their device, with the labels, until the pass ends -- a copy
+        of their own, since a model may write its next batch where this one stands.  The batch that would pass exact_max_bytes raises."""
+        if self._rank is not None:
+            raise ValueError("Classification.process after the exact figures of the pass were counted: reset() starts the next")
+        if mo.dtype not in (torch.float16, torch.float32):
+            mo = mo.float()
+        need = mo.shape[0] * mo.shape[1] * mo.element_size()
+        if self._kept_bytes + need > self.exact_max_bytes:
+            raise ValueError(f"Classification(exact=True): keeping this batch's {list(mo.shape)} {mo.dtype} outputs takes the score store to "
+                             f"{self._kept_bytes + need:,} bytes, beyond exact_max_bytes = {self.exact_max_bytes:,}")
+        self._kept_bytes += need
+        self._kept.append((mo.detach().clone(memory_format=torch.contiguous_format), gt.detach().clone()))
+
+    def count_ranks(self, dist=None) -> None:
+        """exact=: the end of the pass.  Takes the positives of the kept batches (the score every image gave its own class), builds the
+        edge table (rank_edges), counts every kept batch into the state of include/ovmr_hip_ranks.h -- ONE ovmr_eval_ranks launch per
+        batch on the device, rank_count on the host -- and frees the kept scores.  With a process group `dist` the positives of all ranks
+        are gathered first, so that every rank builds the same edges, and the int32 state is summed over the ranks afterwards."""
+        if not self.exact or self._rank is not None:
+            return
+        C, dev = self.num_classes, self.device
+        scores, labels = [], []
+        for mo, gt in self._kept:
+            ok = (gt >= 0) & (gt < C)
+            at = torch.where(ok, gt, torch.zeros_like(gt))
+            scores.append(mo.gather(1, at.unsqueeze(1)).squeeze(1)[ok].float())
+            labels.append(gt[ok])
+        s = torch.cat(scores).cpu() if scores else torch.zeros(0, dtype=torch.float32)
+        y = torch.cat(labels).cpu() if labels else torch.zeros(0, dtype=torch.int64)
+        if dist is not None:
+            from .shard import all_gather_positives
+            s, y = all_gather_positives(s, y, dist)
+        edges, estart = rank_edges(s, y, C)
+        E = edges.shape[0]
+        max_edges = int((estart[1:] - estart[:-1]).max())
+        edges, estart = edges.to(dev), estart.to(dev)
+        state = torch.zeros((2, 2 * E + C), dtype=torch.int32, device=dev)
+        for mo, gt in self._kept:
+            if dev.type == "cpu":
+                rank_count(state, mo, gt, edges, estart, max_edges)
+            else:
+                from . import runtime
+                runtime.eval_ranks(mo, gt, edges, estart, state, max_edges)
+        if dist is not None:
+            from .shard import all_reduce_eval_state
+            all_reduce_eval_state([], [state], dist)
+        self._kept, self._kept_bytes = [], 0                              # the score store is freed
+        self._rank = (edges, estart, state)
+
     def counts(self):
         """(tp, n_pred, n_label) as int64 host tensors [C]; raises if a label outside [0, C) was seen."""
         c = self._counts.cpu().long()
@@ -264,6 +472,8 @@ class Classification:
               f"* error: {100.0 - acc:.1f}%\n* macro_f1: {macro_f1:.1f}%")       # the format parse_test_res.py greps for
         if self.curve_bins is not None:
             self._evaluate_curves(res, output_dir, say)
+        if self.exact:
+            self._evaluate_ranks(res, output_dir, say)
         if output_dir:                                                    # evaluator.py:84-113 (csv module formats)
             import csv
             os.makedirs(output_dir, exist_ok=True)
@@ -339,3 +549,32 @@ class Classification:
                                 cell(fig["best_f1"][c]), int(fig["slot"][c]) if have else "",
                                 (repr(float(fig["threshold"][c])) if have else ""), cell(fig["precision"][c]), cell(fig["recall"][c])])
             torch.save({"hist": hist, "lo": lo, "hi": hi, "bins": bins}, os.path.join(output_dir, "score_hist.pt"))
+
+    def _evaluate_ranks(self, res, output_dir, say):
+        """The exact part of evaluate(): counts the kept scores unless all_reduce did, figures from the int64 state on the host, two more
+        lines of the result block, two files."""
+        import numpy as np
+        self.count_ranks()
+        edges, estart, state = (t.cpu() for t in self._rank)
+        state = state.long()
+        self.rank_state = (edges, estart, state)
+        fig = self.ranks = rank_figures(state, edges, estart)
+        ranked, separated = fig["positives"] > 0, (fig["positives"] > 0) & (fig["negatives"] > 0)
+        res["exact_mAP"] = 100.0 * float(fig["ap"][ranked].mean()) if ranked.any() else 0.0
+        res["exact_mean_auroc"] = float(fig["auroc"][separated].mean()) if separated.any() else 0.0
+        say(f"* exact_mAP: {res['exact_mAP']:.1f}%\n* exact_mean_auroc: {res['exact_mean_auroc']:.4f}")
+        if output_dir:
+            import csv
+            os.makedirs(output_dir, exist_ok=True)
+
+            def cell(v):                                                  # a figure a class does not have is an empty field
+                return "" if v != v else float(v)
+            with open(os.path.join(output_dir, "ranks_per_class.csv"), "w", newline="") as f:
+                w = csv.writer(f, delimiter=",")
+                w.writerow(RANK_COLUMNS)
+                for c in range(self.num_classes):
+                    w.writerow([c, self.classnames[c], int(fig["positives"][c]), int(fig["negatives"][c]), cell(fig["ap"][c]), cell(fig["auroc"][c]),
+                                cell(fig["best_f1"][c]), (repr(float(fig["threshold"][c])) if ranked[c] else ""), cell(fig["precision"][c]),
+                                cell(fig["recall"][c])])
+            torch.save({"edges": edges, "estart": estart, "state": state, "classnames": list(self.classnames)},
+                       os.path.join(output_dir, "rank_state.pt"))

@@ -133,6 +133,12 @@ CURVES_SIGNATURES = {
     "ovmr_eval_curves": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, ctypes.c_float, ctypes.c_float, c_i, c_p, c_p]),
 }
 
+# the fifth extension header include/ovmr_hip_ranks.h (tests/test_ranks_cpu.py holds the pair to each other)
+RANKS_SIGNATURES = {
+    "ovmr_eval_ranks_state_cells": (ctypes.c_long, [c_i, ctypes.c_long]),
+    "ovmr_eval_ranks": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, c_p, c_p, ctypes.c_long, c_i, c_p, c_p]),
+}
+
 _lib = None
 
 
@@ -147,7 +153,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                            "ovmr_amd has no CPU fallback.")
     lib = ctypes.CDLL(p)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(AUDIT_SIGNATURES.items())
-                              + list(RETRIEVE_SIGNATURES.items()) + list(CURVES_SIGNATURES.items())):
+                              + list(RETRIEVE_SIGNATURES.items()) + list(CURVES_SIGNATURES.items()) + list(RANKS_SIGNATURES.items())):
         fn = getattr(lib, name)          # AttributeError if the .so does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -345,6 +351,34 @@ def eval_curves(mo: torch.Tensor, labels: torch.Tensor, lo: float, hi: float, bi
                                   _ptr(state), _stream_on(mo.device))
     if rc != 0:
         raise OvmrError(f"ovmr_eval_curves failed with {rc} (B = {B}, C = {C}, lo = {float(flo)!r}, hi = {float(fhi)!r}, bins = {bins})")
+
+
+def eval_ranks(mo: torch.Tensor, labels: torch.Tensor, edges: torch.Tensor, estart: torch.Tensor, state: torch.Tensor, max_edges: int):
+    """ovmr_eval_ranks on the current stream (include/ovmr_hip_ranks.h): mo [B, C] fp16 / fp32 on the GPU (stride(1) == 1, stride(0) >= C,
+    no copy), labels int64 [B]; edges fp32 [E] and estart int32 [C + 1] on the same device (class c owns edges[estart[c]:estart[c + 1]],
+    its distinct positive scores, descending: evaluator.rank_edges); state int32 [2, 2E + C] accumulates: for every row whose label lies
+    in [0, C) and every class c, state[labels[b] == c, 2 estart[c] + c + cell] += 1 with the cell rule of the header.  max_edges: the
+    largest number of edges of one class, in [0, E].  One launch; an empty batch launches nothing."""
+    where = "eval_ranks"
+    _want_rows(where, "mo", mo)
+    B, C = mo.shape
+    if C < 1:
+        _refuse(where, "mo", "of at least one column", f"{list(mo.shape)}")
+    ld = _row_matrix(where, "mo", mo)
+    _want(where, "labels", labels, (B,), torch.int64, mo.device, dense=True)
+    _want(where, "edges", edges, (None,), torch.float32, mo.device, dense=True)
+    E = edges.shape[0]
+    _want(where, "estart", estart, (C + 1,), torch.int32, mo.device, dense=True)
+    _want(where, "state", state, (2, 2 * E + C), torch.int32, mo.device, dense=True)
+    max_edges = _want_int(where, "max_edges", max_edges, 0, E)
+    lib = load_library()
+    if B == 0:
+        return
+    with torch.cuda.device(mo.device):
+        rc = lib.ovmr_eval_ranks(_ptr(mo), F32 if mo.dtype == torch.float32 else F16, ld, _ptr(labels), B, C, _ptr(edges) if E else None,
+                                 _ptr(estart), E, max_edges, _ptr(state), _stream_on(mo.device))
+    if rc != 0:
+        raise OvmrError(f"ovmr_eval_ranks failed with {rc} (B = {B}, C = {C}, E = {E}, max_edges = {max_edges})")
 
 
 _nearest_scratch: Dict[torch.device, torch.Tensor] = {}         # per device: the scratch of nearest_rows, grown on demand

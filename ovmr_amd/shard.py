@@ -156,6 +156,29 @@ def all_gather_retrieve_state(state: torch.Tensor, dist) -> torch.Tensor:
     return out.view(world, s.shape[0], s.shape[1]).to(state.device)
 
 
+def all_gather_positives(scores: torch.Tensor, labels: torch.Tensor, dist) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The positives of an exact test pass (evaluator.Classification.count_ranks) from every rank: scores fp32 [n] and labels int64 [n]
+    on the host, n the rank's own count -> (scores [sum n], labels [sum n]) on the host, rank-major.  Ragged: ONE all-gather of the
+    lengths, then ONE of the pairs padded to the longest rank, each as int64 [max n, 2] = (the score's bits, the label) so that a NaN or a
+    -0.0 arrives as it left.  A rank without a batch sends nothing but padding."""
+    world, backend = dist.get_world_size(), dist.get_backend()
+    dev = torch.device("cpu") if backend == "gloo" else torch.device("cuda", torch.cuda.current_device())
+    n = torch.tensor([scores.numel()], dtype=torch.int64, device=dev)
+    lengths = torch.empty(world, dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(lengths, n)
+    lengths = lengths.cpu().tolist()
+    longest = max(max(lengths), 1)
+    block = torch.zeros((longest, 2), dtype=torch.int64)
+    block[:scores.numel(), 0] = scores.float().contiguous().view(torch.int32).long()
+    block[:scores.numel(), 1] = labels.long()
+    block = block.to(dev)
+    out = torch.empty((world * longest, 2), dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(out, block)
+    out = out.cpu().view(world, longest, 2)
+    pairs = torch.cat([out[r, :lengths[r]] for r in range(world)])
+    return pairs[:, 0].int().view(torch.float32), pairs[:, 1].contiguous()
+
+
 def all_reduce_counts(counts: torch.Tensor, dist) -> torch.Tensor:
     """ONE all-reduce (sum) of the int32 [3, 2, C] argmax counters."""
     c = _staged(counts, dist)

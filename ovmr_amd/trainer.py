@@ -45,7 +45,7 @@ class _EvalTrainer:
     NOT_TRAINED = ""              # the NotImplementedError of forward_backward / train / save_model
 
     def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, per_class_result=False,
-                 compute_cmat=False, score_curves=None, score_range=None):
+                 compute_cmat=False, score_curves=None, score_range=None, exact_curves=False, exact_max_bytes=None):
         self.check_cfg(cfg)
         self.cfg, self.dm, self.device = cfg, dm, torch.device(device)
         self._clip_weights, self._tokenizer, self._reserve = clip_weights, tokenizer, reserve
@@ -65,6 +65,12 @@ class _EvalTrainer:
             raise ValueError("score_range= belongs to score_curves=BINS")
         if score_curves is not None:
             self._evaluator_args.update(curves=score_curves, **({} if score_range is None else {"score_range": tuple(score_range)}))
+        # exact_curves: every evaluator of the pass keeps its outputs and derives the exact per-class AP / AUROC from them at the end
+        # (evaluator.Classification: exact=, exact_max_bytes=; None = its default budget).  Any score will do: no range
+        if exact_max_bytes is not None and not exact_curves:
+            raise ValueError("exact_max_bytes= belongs to exact_curves=True")
+        if exact_curves:
+            self._evaluator_args.update(exact=True, **({} if exact_max_bytes is None else {"exact_max_bytes": int(exact_max_bytes)}))
         self.evaluator = self._new_evaluator()
         self.mode_evaluators = None                  # EVAL_MODE all: one Classification per mode of ALL_MODES, made by the first such test()
 
@@ -288,9 +294,10 @@ class MM_CLS_OP(_EvalTrainer):
     NOT_TRAINED = "training (autograd through CustomCLIP.forward, :310-338) is out of scope of the HIP hot path"
 
     def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, prompt_learner_state=None,
-                 per_class_result=False, compute_cmat=False, score_curves=None, score_range=None):
+                 per_class_result=False, compute_cmat=False, score_curves=None, score_range=None, exact_curves=False, exact_max_bytes=None):
         self._prompt_learner_state = prompt_learner_state
-        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve, per_class_result, compute_cmat, score_curves, score_range)
+        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve, per_class_result, compute_cmat, score_curves, score_range,
+                         exact_curves, exact_max_bytes)
 
     # :369-370
     def check_cfg(self, cfg):
