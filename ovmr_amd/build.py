@@ -43,7 +43,8 @@ def build(verbose: bool = True, force: bool = False) -> str:
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     hdrs += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("ovmr_hip.h", "ovmr_hip_nearest.h", "ovmr_hip_audit.h",
-                                                                           "ovmr_hip_retrieve.h", "ovmr_hip_curves.h", "ovmr_hip_ranks.h")]
+                                                                           "ovmr_hip_retrieve.h", "ovmr_hip_curves.h", "ovmr_hip_ranks.h",
+                                                                           "ovmr_hip_probe.h")]
     jobs = []
     for f in srcs:
         src, obj = os.path.join(CSRC, f), os.path.join(OBJ, f[:-4] + ".o")

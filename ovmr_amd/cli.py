@@ -528,6 +528,58 @@ def check_audit(args, trainer_name: str, zeroshot: bool, world=None):
         raise SystemExit("--audit-bank runs in one process: a sharded rank holds only its own classes' exemplar features")
 
 
+PROBE_TRAINER = "LinearProbe"
+DEFAULT_PROBE_STEPS = 8
+
+
+def check_probe(args, trainer_name: str):
+    """The refusals of `--probe-c VALUE | search`, `--probe-val-split NAME`, `--probe-steps N` and `--probe FILE`, before anything is listed
+    or loaded -> (c: a float, "search", or None under --probe FILE; steps), or (None, None) for another trainer."""
+    import math
+    if trainer_name != PROBE_TRAINER:
+        for flag, v in (("--probe-c", args.probe_c), ("--probe-val-split", args.probe_val_split), ("--probe-steps", args.probe_steps),
+                        ("--probe", args.probe or None)):
+            if v is not None:
+                raise SystemExit(f"{flag} belongs to --trainer {PROBE_TRAINER}: the logistic regression on the exemplars' image features")
+        return None, None
+    if args.probe and args.probe_c is not None:
+        raise SystemExit("--probe FILE installs a fitted probe: not together with --probe-c, which fits one")
+    search = args.probe_c == "search"
+    if args.probe_steps is not None and not search:
+        raise SystemExit("--probe-steps N belongs to --probe-c search: the rounds of its left / right comparison")
+    if args.probe_val_split is not None and not search:
+        raise SystemExit("--probe-val-split NAME belongs to --probe-c search: the split that scores its candidates")
+    if search and not args.probe_val_split:
+        raise SystemExit("--probe-c search needs --probe-val-split NAME: the split that scores its candidates")
+    if args.nearest is not None or args.audit_bank is not None:
+        raise SystemExit(f"--nearest / --audit-bank: --trainer {PROBE_TRAINER} keeps no exemplar features to search (MM_CLS_OP only)")
+    for flag, on in (("--save-bank", args.save_bank), ("--classifiers", args.classifiers),
+                     ("--add-classes / --replace-classes / --remove-classes", args.add_classes or args.replace_classes or args.remove_classes),
+                     ("--ragged-shots", args.ragged_shots)):
+        if on:
+            raise SystemExit(f"{flag}: --trainer {PROBE_TRAINER} generates no vocabulary (MM_CLS_OP only)")
+    if args.probe and args.bank:
+        raise SystemExit("--probe FILE installs a fitted probe: not together with --bank, which is fitted from")
+    if args.probe and not osp.isfile(args.probe):
+        raise SystemExit(f"--probe {args.probe!r}: no such file")
+    if args.probe:
+        return None, None
+    if search:
+        steps = DEFAULT_PROBE_STEPS if args.probe_steps is None else args.probe_steps
+        if not 0 <= steps <= 64:
+            raise SystemExit(f"--probe-steps {steps}: N must lie in [0, 64]")
+        if args.bank:
+            raise SystemExit("--probe-c search fits on the exemplars of --root: not together with --bank")
+        return "search", steps
+    try:
+        c = 1.0 if args.probe_c is None else float(args.probe_c)
+    except ValueError:
+        c = float("nan")
+    if not (math.isfinite(c) and c > 0):
+        raise SystemExit(f"--probe-c {args.probe_c}: VALUE must be a positive number, or `search`")
+    return c, None
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     # the reference's flags, with the reference's defaults (train.py:183-255)
@@ -618,6 +670,16 @@ def parse(argv=None):
                     "rank_state.pt (per mode under --eval_mode all)")
     ap.add_argument("--exact-budget", type=float, default=None, metavar="GIB", help="with --exact-curves: the most memory the kept scores may "
                     "take, in GiB (default 16; 50 000 images x 1000 classes are 0.2 GiB in fp32); the batch that would pass it ends the run")
+    ap.add_argument("--probe-c", default=None, metavar="VALUE", help="--trainer LinearProbe: the strength C of the logistic regression fitted on the "
+                    "exemplars' image features (scikit-learn's C; default 1.0), or `search`: the reference's search of C against "
+                    "--probe-val-split (lpclip/linear_probe.py)")
+    ap.add_argument("--probe-val-split", default=None, metavar="NAME", help="with --probe-c search: the split whose images score the candidates; "
+                    "min(NUM_SHOTS, 4) images per class of it (the reference's table), drawn with the job's seed, encoded once")
+    ap.add_argument("--probe-steps", type=int, default=None, metavar="N", help="with --probe-c search: rounds of left / right comparison after the "
+                    "7-point sweep (default 8)")
+    ap.add_argument("--probe", metavar="FILE", default="", help="--trainer LinearProbe: install this linear_probe.pt and fit nothing; with --predict / "
+                    "--retrieve the class names come from the file and no --root is needed.  (--bank FILE with this trainer fits from the "
+                    "bank's features and shots instead of decoding exemplars; the bank is held to the model by embed_dim only)")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--workers", type=int, default=None,
                     help="decode worker processes of the pipelined loader (default: DATALOADER.NUM_WORKERS); 0 = decode in this thread")
@@ -794,11 +856,14 @@ def plan_job(args, cfg):
     from . import templates
     name = cfg.TRAINER.NAME
     zeroshot = name in templates.ZEROSHOT_TRAINERS
-    if not (zeroshot or name == "MM_CLS_OP") or not args.eval_only:
+    probe = name == PROBE_TRAINER
+    if not (zeroshot or probe or name == "MM_CLS_OP") or not args.eval_only:
         raise SystemExit("only `--eval-only --trainer MM_CLS_OP` (classifier generation / evaluation) and `--eval-only --trainer "
                          "ZeroshotCLIP | ZeroshotCLIP2` (zero-shot evaluation) are on the hot path")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     shots, batch = cfg.DATASET.NUM_SHOTS, cfg.DATALOADER.TEST.BATCH_SIZE
+    probe_c, probe_steps = check_probe(args, name)
+    logits = zeroshot or probe                                # [B, C] scores whatever EVAL_MODE says, and no natural range
     edits = bool(args.add_classes or args.replace_classes or args.remove_classes)
     if edits and not args.bank:
         raise SystemExit("--add-classes / --replace-classes / --remove-classes edit a reference bank: give --bank FILE")
@@ -814,15 +879,15 @@ def plan_job(args, cfg):
     if args.bank and not osp.isfile(args.bank):
         raise SystemExit(f"--bank {args.bank!r}: no such file")
     predict, retrieve = args.predict is not None, args.retrieve is not None
-    check_retrieve(args, name, zeroshot, cfg.EVAL_MODE)
+    check_retrieve(args, name, logits, cfg.EVAL_MODE)
     pool = predict or retrieve                                # unlabelled images instead of the labelled test split
-    curve_bins, curve_range = check_score_curves(args, name, zeroshot)
+    curve_bins, curve_range = check_score_curves(args, name, logits)
     exact, exact_bytes = check_exact_curves(args)
     check_nearest(args, name, zeroshot)
     check_audit(args, name, zeroshot, world)
     images, k, m = [], None, (MAX_PER_CLASS if args.per_class is None else args.per_class) if retrieve else None
     if predict:
-        if cfg.EVAL_MODE == "all" and not zeroshot:
+        if cfg.EVAL_MODE == "all" and not logits:
             raise SystemExit("--predict ranks the classes under ONE mode: --eval_mode all belongs to the test pass (fusion, text, vision or multimodal here)")
         for flag, on in (("--per-class-result", args.per_class_result), ("--confusion-matrix", args.confusion_matrix)):
             if on:
@@ -842,14 +907,14 @@ def plan_job(args, cfg):
             check_pool_size(len(images), args.retrieve)
     elif args.topk is not None or args.classifiers:
         raise SystemExit("--topk / --classifiers belong to --predict PATH (the test pass takes TEST.TOPK)")
-    vocabulary = "zeroshot" if zeroshot else "classifiers" if args.classifiers else "bank" if args.bank else "generate"
+    vocabulary = ("probe-file" if args.probe else "probe-bank" if args.bank else "probe-fit") if probe else "zeroshot" if zeroshot else "classifiers" if args.classifiers else "bank" if args.bank else "generate"
     audit_only = args.audit_bank is not None and vocabulary == "bank" and not edits and not pool      # the bank alone: no data set, no test pass
     p = SimpleNamespace(args=args, cfg=cfg, zeroshot=zeroshot, world=world, vocabulary=vocabulary, edits=edits, images=images,
                         mode="audit" if audit_only else "predict" if predict else "retrieve" if retrieve else "test",
                         k=k, m=m, within_top=args.within_top, nearest=args.nearest, audit=args.audit_bank,
                         dup_threshold=0.995 if args.dup_threshold is None else args.dup_threshold, curve_bins=curve_bins, curve_range=curve_range,
-                        exact=exact, exact_bytes=exact_bytes,
-                        ragged=bool(args.ragged_shots) and vocabulary in ("generate", "bank"), lift_shots=vocabulary != "generate", skip=False)
+                        exact=exact, exact_bytes=exact_bytes, probe=probe, probe_c=probe_c, probe_steps=probe_steps,
+                        ragged=bool(args.ragged_shots) and vocabulary in ("generate", "bank"), lift_shots=vocabulary not in ("generate", "probe-fit"), skip=False)
     decodes = vocabulary == "generate" or edits               # exemplars are decoded and mm_classifiers.pt is written
     if decodes and osp.isdir(cfg.OUTPUT_DIR) and osp.exists(osp.join(cfg.OUTPUT_DIR, "mm_classifiers.pt")):
         p.skip = True
@@ -860,7 +925,7 @@ def plan_job(args, cfg):
         except KeyError as e:
             raise SystemExit(e.args[0]) from None
         # (nothing of the few-shot draw is decoded)
-    elif decodes:
+    elif decodes or vocabulary == "probe-fit":
         if shots < 1:
             raise SystemExit("DATASET.NUM_SHOTS must be >= 1: the eval-set loader draws NUM_SHOTS rows per class (data_manager.py:157-170)")
         if batch < shots:
@@ -889,8 +954,30 @@ def _open_job(p):
         import copy
         split_cfg = copy.deepcopy(cfg)
         split_cfg.DATASET.NUM_SHOTS = max(1, cfg.DATASET.NUM_SHOTS)          # (any NUM_SHOTS >= 1 yields the same label set)
-    bank_obj = edit_plan = None
-    if p.vocabulary == "bank":
+    bank_obj = edit_plan = probe_state = None
+    if p.vocabulary in ("probe-file", "probe-bank"):
+        # the class names come from the file: a pool needs no data set at all, the test pass one that speaks of the same classes
+        from . import bank as bank_format
+        from . import probe as probe_format
+        flag, path = ("--probe", args.probe) if p.vocabulary == "probe-file" else ("--bank", args.bank)
+        try:
+            if p.vocabulary == "probe-file":
+                probe_state = probe_format.LinearProbeState.read(path)
+                classnames = list(probe_state.classnames)
+            else:
+                bank_obj = bank_format.read(path)
+                classnames = bank_obj["classnames"]
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+        if classnames is None:
+            raise SystemExit(f"--bank {path!r}: the bank holds no class names (it was written by a model built from token rows)")
+        exemplars, test_items = [], []
+        if p.mode == "test":
+            set_names, _, test_items = build_splits(split_cfg, args.eval_split, args.test_split, "", False)
+            diff = bank_format.first_difference(classnames, set_names)
+            if diff is not None:
+                raise SystemExit(f"{flag} {path!r}: its class names are not the data set's: {diff}")
+    elif p.vocabulary == "bank":
         from . import bank as bank_format
         try:
             bank_obj = bank_format.read(args.bank)            # (checked against the model by load_bank)
@@ -913,7 +1000,7 @@ def _open_job(p):
     if pool:
         test_items = [(path, 0) for path in p.images]         # the loader protocol carries a label: a dummy one, never read
     return SimpleNamespace(own_group=own_group, rank=rank, world=world, bank=bank_obj, edit_plan=edit_plan, classnames=classnames,
-                           exemplars=exemplars, test_items=test_items, audit_tables=None)
+                           exemplars=exemplars, test_items=test_items, audit_tables=None, probe_state=probe_state)
 
 
 def _build_trainer(p, run):
@@ -930,7 +1017,9 @@ def _build_trainer(p, run):
     tfm = dict(interpolation=cfg.INPUT.INTERPOLATION, mean=tuple(cfg.INPUT.PIXEL_MEAN) if normalize else None,
                std=tuple(cfg.INPUT.PIXEL_STD) if normalize else None)
     kw = {}
-    if not p.zeroshot:
+    if p.probe:
+        kw["probe_c"] = p.probe_c if isinstance(p.probe_c, float) else 1.0
+    elif not p.zeroshot:
         pl_state = None
         if cfg.MODEL.INIT_WEIGHTS:                            # load_pretrained_weights (trainers/mm_classifier_one_prompt.py:403-404)
             ck = checkpoint._torch_load(cfg.MODEL.INIT_WEIGHTS)
@@ -942,7 +1031,21 @@ def _build_trainer(p, run):
         kw["prompt_learner_state"] = pl_state
     loader = _loader_factory(args, cfg, spec.image_resolution, tfm)
     eval_loader, edit_loaders = None, {}
-    if p.vocabulary == "generate" and not ragged:
+    val_loader = None
+    if p.vocabulary == "probe-fit":
+        # every rank decodes every exemplar and fits the same probe (the fit is not sharded: DESIGN.md section 5)
+        eval_loader = loader(run.exemplars, batch // shots * shots, 0, 1, len(classnames))     # (MM_CLS_OP's batches: the same features, bit for bit)
+        if p.probe_c == "search":
+            from .probe import val_shots
+            if cfg.DATASET.SUBSAMPLE_CLASSES != "all":
+                raise SystemExit("--probe-c search scores on the classes of --probe-val-split: DATASET.SUBSAMPLE_CLASSES must be all")
+            if not osp.isdir(osp.join(cfg.DATASET.ROOT, args.probe_val_split)):
+                raise SystemExit(f"--probe-val-split {args.probe_val_split!r}: no such split below {cfg.DATASET.ROOT!r}")
+            val_items = fewshot_items(list_split(cfg.DATASET.ROOT, args.probe_val_split)[1], val_shots(shots), cfg.SEED)
+            if not val_items or max(l for _, l in val_items) >= len(classnames):
+                raise SystemExit(f"--probe-val-split {args.probe_val_split!r}: its class folders are not the {len(classnames)} classes of {args.eval_split!r}")
+            val_loader = loader(val_items, batch, 0, 1, len(classnames))
+    elif p.vocabulary == "generate" and not ragged:
         eval_loader = loader(run.exemplars, batch // shots * shots, rank, world, len(classnames))
     else:                                                     # (zero-shot, --classifiers: no exemplar loader at all)
         try:
@@ -971,7 +1074,7 @@ def _build_trainer(p, run):
                                    reserve=(batch, 256, max(1024, len(classnames))), per_class_result=args.per_class_result,
                                    compute_cmat=args.confusion_matrix, score_curves=p.curve_bins, score_range=p.curve_range,
                                    exact_curves=p.exact, exact_max_bytes=p.exact_bytes, **kw)
-    run.eval_loader, run.edit_loaders, run.test_loader = eval_loader, edit_loaders, test_loader
+    run.eval_loader, run.edit_loaders, run.test_loader, run.val_loader = eval_loader, edit_loaders, test_loader, val_loader
 
 
 def _install_vocabulary(p, run):
@@ -979,7 +1082,27 @@ def _install_vocabulary(p, run):
     exemplar set (and banked under --save-bank).  A zero-shot model has its text classifier already."""
     from .bank import BANK_FILE
     args, cfg, model = p.args, p.cfg, run.tr.model
-    if p.vocabulary == "classifiers":
+    if p.probe:
+        # the probe: read from --probe, fitted from --bank's features, or fitted (at --probe-c, or searched) from the exemplar loader;
+        # every fit writes OUTPUT_DIR/linear_probe.pt and one `=> linear probe:` line behind the test pass
+        tr = run.tr
+        try:
+            if p.vocabulary == "probe-file":
+                tr.model.install(run.probe_state)
+                tr.probe_state = run.probe_state
+            elif p.vocabulary == "probe-bank":
+                if int(run.bank["features"].shape[1]) != tr.model.engine.spec.embed_dim:
+                    raise ValueError(f'"{args.bank}": features are {int(run.bank["features"].shape[1])} wide, the model\'s embed_dim is '
+                                     f"{tr.model.engine.spec.embed_dim}")
+                tr.fit_probe(features=run.bank["features"], shots=run.bank["shots"])
+            elif p.probe_c == "search":
+                vx, vy = tr.model.encode_loader(run.val_loader)
+                tr.search_probe(vx, vy, p.probe_steps)
+            else:
+                tr.fit_probe()
+        except ValueError as e:
+            raise SystemExit(str(e)) from None
+    elif p.vocabulary == "classifiers":
         model.load_classifiers(args.classifiers)
     elif p.vocabulary == "bank":
         # (the trainer and its evaluator were built for the FINAL class names; the bank replaces the model's class list, the edits lead to it)

@@ -1684,3 +1684,121 @@ class ZeroshotCLIP2(ZeroshotCLIP):
             raise ValueError(f"ZeroshotCLIP2 takes token ids [templates, classes, context_length], got {tuple(tokenized_prompts.shape)}")
         print(f"Prompt ensembling (n={tokenized_prompts.shape[0]})")                # :85-86
         return e.encode_text_ensemble(tokenized_prompts)
+
+
+class LinearProbe(_TwoInFlight):
+    """lpclip/feat_extractor.py + lpclip/linear_probe.py: a logistic regression on image features, fitted on the device (ovmr_amd.probe,
+    csrc/probe.hip) and evaluated through the engine's batch path.  The reference probes the raw features of its RN50 tower; this path
+    probes the L2-NORMALISED features of the ViT tower -- what encode_image(normalize=True) returns and what a reference bank holds
+    (DESIGN.md section 6).  Outputs are fp32 [B, C] scores x W^T + b of ovmr_probe_logits, the GEMM the fit itself evaluates."""
+
+    TRAINER = "LinearProbe"
+    TOL = 1e-4                    # scikit-learn's default gtol
+    MAX_ITER = 1000               # lpclip/linear_probe.py:57
+
+    def __init__(self, clip_model: CLIPModel, classnames: Sequence[str], n_ctx: int = 2, reserve=(256, 256, 1024)):
+        self.clip_model = clip_model
+        self.engine = e = clip_model.engine(n_ctx)
+        self.device = e.device
+        if not hasattr(e, "_pl_loaded"):                   # (as ZeroshotCLIP: the handle wants the aggregator's weights)
+            self._pl_state = {k: torch.from_numpy(v) for k, v in synth.prompt_learner_state_dict(clip_model.spec, n_ctx, 0).items()}
+            e.load_state_dict({}, self._pl_state)
+            e._pl_loaded = True
+        if not e.finalized:
+            e._reserve = tuple(reserve)
+            e.finalize(*reserve)
+        self.classnames = [str(n) for n in classnames]
+        self.W = self.b = self.state = None
+
+    _twin_state = ZeroshotCLIP._twin_state
+
+    def _labels_of(self, shots) -> torch.Tensor:
+        shots = torch.as_tensor(shots, dtype=torch.int64).reshape(-1).cpu()
+        if len(shots) != len(self.classnames) or bool((shots < 0).any()):
+            raise ValueError(f"LinearProbe: shots must hold one count per class ({len(self.classnames)}), none negative, got {len(shots)} entries")
+        return torch.repeat_interleave(torch.arange(len(shots)), shots)
+
+    @torch.no_grad()
+    def fit_features(self, features_f16: torch.Tensor, shots, c: float = 1.0, tol: Optional[float] = None, max_iter: Optional[int] = None,
+                     install: bool = True):
+        """Fits the probe at strength c on exemplar features packed class after class: features_f16 [R, D] (any float dtype; a bank's
+        `features`), shots [C] rows per class.  The features are converted to fp32 ONCE and stay on the device.  -> probe.LinearProbeState
+        (installed unless install=False)."""
+        from . import probe
+        labels = self._labels_of(shots)
+        D = self.engine.spec.embed_dim
+        if features_f16.dim() != 2 or tuple(features_f16.shape) != (len(labels), D):
+            raise ValueError(f"LinearProbe.fit_features: features must be of shape [{len(labels)}, {D}] (sum(shots) rows of embed_dim), got "
+                             f"{list(features_f16.shape)}")
+        if len(labels) == 0:
+            raise ValueError("LinearProbe.fit_features: no exemplar row to fit on")
+        with torch.cuda.device(self.device):
+            x = features_f16.to(self.device).float().contiguous()
+            y = labels.to(self.device)
+            tol, max_iter = self.TOL if tol is None else tol, self.MAX_ITER if max_iter is None else max_iter
+            r = probe.fit(probe.device_loss_grad(x, y), len(self.classnames), D, float(c), tol=tol, max_iter=max_iter, device=self.device)
+        state = probe.LinearProbeState(r.W, r.b, c, tol, r.n_iter, r.converged, self.classnames, torch.as_tensor(shots), None)
+        state.loss, state.n_eval = r.loss, r.n_eval
+        if install:
+            self.install(state)
+        return state
+
+    @torch.no_grad()
+    def encode_loader(self, loader: Iterable):
+        """Every batch of a loader through encode_image(normalize=True), in the order of the walk -> (features fp16 [R, D] on the device,
+        labels int64 [R] on the host)."""
+        feats, labels = [], []
+        for batch in loader:
+            image = CustomCLIP._batch_images(batch, self.device)
+            feats.append(self.engine.encode_image(image, normalize=True).clone())
+            labels.append(batch["label"].reshape(-1).to(torch.int64).cpu())
+        if not feats:
+            raise ValueError("LinearProbe: the loader holds no batch")
+        labels = torch.cat(labels)
+        C = len(self.classnames)
+        if bool(((labels < 0) | (labels >= C)).any()):
+            raise ValueError(f"LinearProbe: labels must lie in [0, {C}), got values from {int(labels.min())} to {int(labels.max())}")
+        return torch.cat(feats), labels
+
+    def exemplar_features(self, eval_set_loader: Iterable):
+        """The one loader walk MM_CLS_OP uses for its exemplars (encode_loader); the rows are then packed class after class, a class's
+        rows in the order of the walk -- a reference bank's layout.  -> (features fp16 [R, D] on the device, shots int64 [C] on the host)."""
+        feats, labels = self.encode_loader(eval_set_loader)
+        order = torch.sort(labels, stable=True).indices
+        return feats[order.to(self.device)], torch.bincount(labels, minlength=len(self.classnames))
+
+    def fit_exemplars(self, eval_set_loader: Iterable, c: float = 1.0, **kw):
+        """exemplar_features + fit_features: the probe of the images an eval-set loader yields."""
+        feats, shots = self.exemplar_features(eval_set_loader)
+        return self.fit_features(feats, shots, c, **kw)
+
+    def install(self, state):
+        """Makes a fitted or read probe.LinearProbeState the model's classifier (held to the model by class count and embed_dim)."""
+        C, D = len(self.classnames), self.engine.spec.embed_dim
+        if tuple(state.W.shape) != (C, D):
+            raise ValueError(f"LinearProbe.install: the probe's W is {list(state.W.shape)}, this model has {C} classes and embed_dim {D}")
+        with torch.cuda.device(self.device):
+            self.W, self.b = state.W.to(self.device).contiguous(), state.b.to(self.device).contiguous()
+        self.state = state
+
+    def _forward_on(self, engine: Engine, image, out=None):
+        from . import runtime
+        if self.W is None:
+            raise RuntimeError("LinearProbe has no probe yet: fit_exemplars / fit_features / install come first")
+        f = engine.encode_image(image, normalize=True)
+        return runtime.probe_logits(f.float(), self.W, self.b)
+
+    def model_inference(self, image):
+        return self._forward_on(self.engine, image)
+
+    @torch.no_grad()
+    def predict_topk(self, image, k: int, eval_set_loader=None):
+        """model_inference(image) followed by ovmr_topk_rows on its scores: (values fp32 [B, k], indices int64 [B, k])."""
+        return self._topk(self.model_inference(image), k)
+
+    def _before_outputs(self, what: str, eval_set_loader=None, one_mode: Optional[str] = None) -> int:
+        if self.W is None:
+            if eval_set_loader is None:
+                raise RuntimeError(f"{what}: LinearProbe has no probe yet and no exemplar loader to fit one from")
+            self.fit_exemplars(eval_set_loader)
+        return len(self.classnames)

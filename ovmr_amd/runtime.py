@@ -139,6 +139,15 @@ RANKS_SIGNATURES = {
     "ovmr_eval_ranks": (c_i, [c_p, c_i, ctypes.c_long, c_p, c_i, c_i, c_p, c_p, ctypes.c_long, c_i, c_p, c_p]),
 }
 
+# the sixth extension header include/ovmr_hip_probe.h (tests/test_probe_cpu.py holds the pair to each other)
+PROBE_SIGNATURES = {
+    "ovmr_probe_logits": (c_i, [c_p, ctypes.c_long, c_i, c_p, c_p, c_i, c_i, c_p, ctypes.c_long, c_p]),
+    "ovmr_probe_row_quantum": (c_i, []),
+    "ovmr_probe_workspace_bytes": (ctypes.c_long, [c_i, c_i, c_i]),
+    "ovmr_probe_loss_grad": (c_i, [c_p, ctypes.c_long, c_p, c_i, c_i, c_i, c_p, c_p, ctypes.c_float, ctypes.c_float, c_i, c_p, c_p, c_p, c_p,
+                                   c_p]),
+}
+
 _lib = None
 
 
@@ -153,7 +162,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
                            "ovmr_amd has no CPU fallback.")
     lib = ctypes.CDLL(p)
     for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(AUDIT_SIGNATURES.items())
-                              + list(RETRIEVE_SIGNATURES.items()) + list(CURVES_SIGNATURES.items()) + list(RANKS_SIGNATURES.items())):
+                              + list(RETRIEVE_SIGNATURES.items()) + list(CURVES_SIGNATURES.items()) + list(RANKS_SIGNATURES.items())
+                              + list(PROBE_SIGNATURES.items())):
         fn = getattr(lib, name)          # AttributeError if the .so does not export the symbol
         fn.restype = res
         fn.argtypes = args
@@ -381,7 +391,124 @@ def eval_ranks(mo: torch.Tensor, labels: torch.Tensor, edges: torch.Tensor, esta
         raise OvmrError(f"ovmr_eval_ranks failed with {rc} (B = {B}, C = {C}, E = {E}, max_edges = {max_edges})")
 
 
-_nearest_scratch: Dict[torch.device, torch.Tensor] = {}         # per device: the scratch of nearest_rows, grown on demand
+PROBE_WORKSPACE_CAP = 1 << 30                                     # bytes of logits workspace probe_workspace allocates at most
+
+
+def _want_probe(where: str, x, W, b):
+    """The operands every probe entry point shares (include/ovmr_hip_probe.h): x fp32 [N, D] on the GPU, unit column stride, rows a
+    multiple of 4 and at least D elements apart, 16-byte aligned; W fp32 [C, D] and b fp32 [C], dense, on x's device; D % 32 == 0.
+    -> (N, C, D, ldx)."""
+    _want(where, "x", x, (None, None), torch.float32, "cuda")
+    N, D = x.shape
+    if D < 32 or D % 32:
+        _refuse(where, "x", "of a width D that is a positive multiple of 32", f"{list(x.shape)}")
+    ldx = _row_matrix(where, "x", x)
+    if ldx % 4:
+        _refuse(where, "x", "rows a multiple of 4 elements apart", f"strides {tuple(x.stride())}")
+    _want(where, "W", W, (None, D), torch.float32, x.device, dense=True)
+    C = W.shape[0]
+    if C < 1:
+        _refuse(where, "W", "of at least one row", f"{list(W.shape)}")
+    _want(where, "b", b, (C,), torch.float32, x.device, dense=True)
+    for name, t in (("x", x), ("W", W)):
+        if t.data_ptr() % 16:
+            _refuse(where, name, "16-byte aligned", f"an address ending in {t.data_ptr() % 16:#x}")
+    return N, C, D, ldx
+
+
+def probe_logits(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ovmr_probe_logits on the current stream (include/ovmr_hip_probe.h): x fp32 [B, D] (stride(1) == 1, stride(0) >= D and a multiple
+    of 4, no copy), W fp32 [C, D], b fp32 [C] -> out fp32 [B, C] = x W^T + b, the library's fp32 GEMM with its bias epilogue.  out: the
+    caller's [B, C] (rows at least C apart: a column slice of a wider buffer is written in place and the rest left alone)."""
+    where = "probe_logits"
+    B, C, D, ldx = _want_probe(where, x, W, b)
+    if out is not None:
+        _want(where, "out", out, (B, C), torch.float32, x.device)
+        ldo = _row_matrix(where, "out", out)
+    lib = load_library()
+    with torch.cuda.device(x.device):
+        if out is None:
+            out, ldo = torch.empty((B, C), dtype=torch.float32, device=x.device), C
+        if B == 0:
+            return out
+        rc = lib.ovmr_probe_logits(_ptr(x), ldx, B, _ptr(W), _ptr(b), C, D, _ptr(out), ldo, _stream_on(x.device))
+    if rc != 0:
+        raise OvmrError(f"ovmr_probe_logits failed with {rc} (B = {B}, C = {C}, D = {D})")
+    return out
+
+
+def probe_rows_per_call(N: int, C: int, D: int, max_bytes: int = PROBE_WORKSPACE_CAP) -> int:
+    """Rows one ovmr_probe_loss_grad call takes so that its logits stay within max_bytes: N where they fit, else the largest multiple of
+    the library's row quantum that does (at least one quantum)."""
+    lib = load_library()
+    N, C, D = _want_int("probe_workspace", "N", N, 0, 2 ** 31 - 1), _want_int("probe_workspace", "C", C, 1, 2 ** 31 - 4), int(D)
+    if lib.ovmr_probe_workspace_bytes(0, C, D) < 0:
+        _refuse("probe_workspace", "D", "a positive multiple of 32", repr(D))
+    q = lib.ovmr_probe_row_quantum()
+    per_row = lib.ovmr_probe_workspace_bytes(1, C, D)
+    return N if N * per_row <= max_bytes else max(q, int(max_bytes) // (per_row * q) * q)
+
+
+def probe_workspace(N: int, C: int, D: int, device, max_bytes: int = PROBE_WORKSPACE_CAP) -> torch.Tensor:
+    """The fp32 workspace of probe_loss_grad for N rows, at most max_bytes of it (or one row quantum's worth, if that is more): where
+    the logits of all rows would take more, probe_loss_grad walks the rows in cuts that fit."""
+    rows = probe_rows_per_call(N, C, D, max_bytes)
+    nbytes = load_library().ovmr_probe_workspace_bytes(rows, C, D)
+    with torch.cuda.device(device):
+        return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def probe_loss_grad(x: torch.Tensor, labels: torch.Tensor, W: torch.Tensor, b: torch.Tensor, inv_n: float, l2: float,
+                    workspace: Optional[torch.Tensor] = None, gW: Optional[torch.Tensor] = None, gb: Optional[torch.Tensor] = None,
+                    row_loss: Optional[torch.Tensor] = None):
+    """ovmr_probe_loss_grad on the current stream (include/ovmr_hip_probe.h): the objective
+    f = inv_n * sum_n (lse(z_n) - z_n[y_n]) + l2 / 2 * ||W||^2, z = x W^T + b, over x fp32 [N, D] and labels int64 [N] (a label outside
+    [0, C) leaves its row out) -> (loss, gW, gb, row_loss): loss a 0-dim fp64 tensor on the device (row_loss summed in fp64, nothing is
+    read back), gW fp32 [C, D] and gb fp32 [C] the gradient, row_loss fp32 [N] the per-row terms.  workspace: fp32, dense, from
+    probe_workspace; where it holds fewer than N rows of logits the rows are walked in cuts that are multiples of the library's row
+    quantum, the later ones with accumulate = 1 -- bit for bit the one-call result (the header says why)."""
+    where = "probe_loss_grad"
+    N, C, D, ldx = _want_probe(where, x, W, b)
+    _want(where, "labels", labels, (N,), torch.int64, x.device, dense=True)
+    for name, v in (("inv_n", inv_n), ("l2", l2)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+            _refuse(where, name, "a finite number, not negative", repr(v))
+    lib = load_library()
+    q = lib.ovmr_probe_row_quantum()
+    per_row = lib.ovmr_probe_workspace_bytes(1, C, D) // 4
+    if workspace is not None:
+        _want(where, "workspace", workspace, (None,), torch.float32, x.device, dense=True)
+        rows = N if workspace.numel() >= N * per_row else workspace.numel() // (per_row * q) * q
+        if rows == 0 and N > 0:
+            _refuse(where, "workspace", f"of at least {min(N, q) * per_row} elements (the logits of {min(N, q)} rows of {C} classes)",
+                    f"{list(workspace.shape)}")
+        if workspace.data_ptr() % 16:
+            _refuse(where, "workspace", "16-byte aligned", f"an address ending in {workspace.data_ptr() % 16:#x}")
+    for name, t, shape in (("gW", gW, (C, D)), ("gb", gb, (C,)), ("row_loss", row_loss, (N,))):
+        if t is not None:
+            _want(where, name, t, shape, torch.float32, x.device, dense=True)
+    if gW is not None and gW.data_ptr() % 16:
+        _refuse(where, "gW", "16-byte aligned", f"an address ending in {gW.data_ptr() % 16:#x}")
+    with torch.cuda.device(x.device):
+        if workspace is None:
+            workspace = probe_workspace(N, C, D, x.device)
+            rows = N if workspace.numel() >= N * per_row else workspace.numel() // (per_row * q) * q
+        gW = torch.empty((C, D), dtype=torch.float32, device=x.device) if gW is None else gW
+        gb = torch.empty((C,), dtype=torch.float32, device=x.device) if gb is None else gb
+        row_loss = torch.empty((N,), dtype=torch.float32, device=x.device) if row_loss is None else row_loss
+        stream = _stream_on(x.device)
+        for n0 in range(0, max(N, 1), max(rows, 1)):
+            n = min(rows, N - n0)
+            rc = lib.ovmr_probe_loss_grad(_ptr(x[n0:]) if n else None, ldx, _ptr(labels[n0:]) if n else None, n, C, D, _ptr(W), _ptr(b),
+                                          float(inv_n), float(l2), int(n0 > 0), _ptr(workspace) if n else None,
+                                          _ptr(row_loss[n0:]) if n else None, _ptr(gW), _ptr(gb), stream)
+            if rc != 0:
+                raise OvmrError(f"ovmr_probe_loss_grad failed with {rc} (rows {n0} .. {n0 + n} of {N}, C = {C}, D = {D})")
+        loss = row_loss.sum(dtype=torch.float64) * float(inv_n) + W.double().square().sum() * (0.5 * float(l2))
+    return loss, gW, gb, row_loss
+
+
+_nearest_scratch: Dict[torch.device, torch.Tensor] = {}       # per device: the scratch of nearest_rows, grown on demand
 
 
 def _search_scratch(dev, need: int) -> torch.Tensor:

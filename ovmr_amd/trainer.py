@@ -386,6 +386,114 @@ TRAINER_REGISTRY["ZeroshotCLIP"] = ZeroshotCLIP
 TRAINER_REGISTRY["ZeroshotCLIP2"] = ZeroshotCLIP2
 
 
+class LinearProbe(_EvalTrainer):
+    """lpclip/linear_probe.py on the device: a logistic regression on the image features of the exemplars `dm.eval_set_loader` yields
+    (or of a reference bank: fit_probe(features=, shots=)), evaluated by the shared test pass.  probe_c: the strength C of a fixed fit.
+    Nothing is registered, so load_model has nothing to load.  Under torch.distributed every rank fits the same probe from the same
+    exemplars -- the kernels are deterministic, so the ranks' probes are bit-equal -- and only the test pass is sharded."""
+
+    CLIP_FETCHED_BY = "lpclip/feat_extractor.py"
+    NOT_TRAINED = "the linear probe is fitted by fit_probe (L-BFGS on the device), not by Dassl's training loop"
+
+    def __init__(self, cfg, dm, clip_weights=None, tokenizer=None, device: str = "cuda:0", reserve=None, probe_c: float = 1.0, **kw):
+        self.probe_c = float(probe_c)
+        super().__init__(cfg, dm, clip_weights, tokenizer, device, reserve, **kw)
+
+    def build_model(self):
+        cfg = self.cfg
+        classnames = self.dm.dataset.classnames
+        self.clip_model = self.load_clip()
+        reserve = self._reserve
+        if reserve is None:
+            batch = getattr(getattr(cfg.DATALOADER, "TEST", None), "BATCH_SIZE", 256)
+            reserve = (batch, 256, max(1024, len(classnames)))
+        self.model = modules.LinearProbe(self.clip_model, classnames, reserve=reserve)
+
+    def _fitted(self, state, search=None):
+        """A fitted state becomes the model's probe, OUTPUT_DIR/linear_probe.pt and one line of the result block."""
+        from . import probe
+        state.search = search
+        self.model.install(state)
+        self.probe_state = state
+        if self.output_dir and self._is_rank0():
+            state.write(os.path.join(self.output_dir, probe.PROBE_FILE))
+        self.probe_line = (f"=> linear probe: C {state.c:g} iterations {state.n_iter} converged {state.converged} "
+                           f"train loss {getattr(state, 'loss', float('nan')):.6f}")
+        return state
+
+    @staticmethod
+    def _is_rank0() -> bool:
+        import torch.distributed as dist
+        return not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+
+    def _exemplars(self, features, shots):
+        if features is not None:
+            return features, shots
+        if self.eval_set_loader is None:
+            raise ValueError("LinearProbe.fit_probe needs exemplars: dm.eval_set_loader, or features= and shots= of a reference bank")
+        return self.model.exemplar_features(self.eval_set_loader)
+
+    @torch.no_grad()
+    def fit_probe(self, c=None, features=None, shots=None):
+        """Fits at strength c (default: probe_c) on the exemplar loader's images, or on features fp16 [R, D] / shots [C] packed class
+        after class (a reference bank's fields).  -> probe.LinearProbeState, installed and written."""
+        features, shots = self._exemplars(features, shots)
+        return self._fitted(self.model.fit_features(features, shots, self.probe_c if c is None else float(c), install=False))
+
+    @torch.no_grad()
+    def search_probe(self, val_features, val_labels, steps: int = 8, features=None, shots=None):
+        """The reference's search of C (probe.search_c) against validation features fp16 / fp32 [V, D] and labels int64 [V], both kept on
+        the device: every candidate is fitted on the exemplars and scored by its top-1 accuracy there (the library's tie rule)."""
+        from . import probe, runtime
+        features, shots = self._exemplars(features, shots)
+        vx = val_features.to(self.device).float().contiguous()
+        vy = val_labels.to(self.device).reshape(-1, 1)
+
+        def accuracy_at(state):
+            scores = runtime.probe_logits(vx, state.W.to(self.device), state.b.to(self.device))
+            return float((runtime.topk_rows(scores, 1)[1].long() == vy).double().mean())
+        c, state, trace = probe.search_c(lambda c: self.model.fit_features(features, shots, c, install=False), accuracy_at, steps)
+        return self._fitted(state, trace)
+
+    def install_probe(self, path: str):
+        """Installs a written linear_probe.pt; nothing is fitted."""
+        from . import probe
+        state = probe.LinearProbeState.read(path)
+        if state.classnames != [str(n) for n in self.dm.dataset.classnames]:
+            raise ValueError(f'"{path}": classnames are not this run\'s {self.num_classes} classes')
+        self.model.install(state)
+        self.probe_state = state
+        return state
+
+    def outputs(self, inputs):
+        if self.model.W is None:
+            self.fit_probe()
+        return super().outputs(inputs)
+
+    def ranked(self, inputs, k):
+        if self.model.W is None:
+            self.fit_probe()
+        return super().ranked(inputs, k)
+
+    def searched(self, inputs, m, within_top, base):
+        if self.model.W is None:
+            self.fit_probe()
+        return super().searched(inputs, m, within_top, base)
+
+    def after_test(self):
+        if getattr(self, "probe_line", None) and self._is_rank0():
+            print(self.probe_line)
+
+    def model_inference(self, image):
+        return self.model.model_inference(image)
+
+    def output_modes(self):
+        return None
+
+
+TRAINER_REGISTRY["LinearProbe"] = LinearProbe
+
+
 def build_trainer(cfg, dm, **kw):
     """dassl.engine.build_trainer: look the class up by cfg.TRAINER.NAME."""
     name = getattr(cfg.TRAINER, "NAME", "MM_CLS_OP")
